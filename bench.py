@@ -18,7 +18,10 @@ N > 1   the corpus is tweet-hash sharded over the N ranks (one process per GPU);
         reference ann/.../common/ShardApi.scala:71-87).  Per-GPU posting work is constant in N:
         "scaling": "weak".
 
-Prints ONE JSON line on rank 0 (see the task contract) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`); --full also measures and checks everything beside it, after the timed steps: per-kernel
+timings (`roofline`), the `end_to_end` and `micro_batched` legs, oracle parity, both recall fields, `cpu_baseline` and,
+sharded, the comparison with the unsharded index.  --dump-outputs DIR writes what the last timed step returned.
 """
 import argparse
 import ctypes
@@ -32,6 +35,29 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, ids, scores, counts, map_sizes, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the answer a caller of the timed path receives (ids, scores, counts, map sizes per query) as float64
+    DIR/<name>.npy.  Tweet ids are 63-bit snowflakes, beyond float64's 53-bit mantissa: they are written as their high and
+    low 32 bits.  Entries past a query's count are not part of its answer and are written as 0.  When the whole answer
+    would exceed `limit_bytes`, a fixed seeded sample of query rows is written; `query_index` names the rows either way."""
+    ids, scores = np.asarray(ids, np.int64), np.asarray(scores, np.float64)
+    counts, map_sizes = np.asarray(counts), np.asarray(map_sizes)
+    nq, k = ids.shape
+    rows = np.arange(nq)
+    max_rows = (limit_bytes - 6 * 4096) // ((3 * k + 3) * 8)  # (six files: a header allowance each)
+    if nq > max_rows:
+        rows = np.sort(np.random.default_rng(20260105).choice(nq, size=max_rows, replace=False))
+    ids, scores, counts, map_sizes = ids[rows], scores[rows].copy(), counts[rows], map_sizes[rows]
+    past = np.arange(k)[None, :] >= counts[:, None]
+    ids = np.where(past, 0, ids)
+    scores[past] = 0.0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("query_index", rows), ("tweet_ids_hi32", ids >> 32), ("tweet_ids_lo32", ids & 0xFFFFFFFF), ("scores", scores),
+                    ("counts", counts), ("map_sizes", map_sizes)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, np.float64))
 
 
 def traffic_bytes(args, nq, world):
@@ -90,9 +116,11 @@ def run_cluster_range(args, pkg, lib, index, comm, dist, torch, rank, world, loc
     tc = torch.tensor([cand, int(d_bad.item()), sent, scanned], dtype=torch.int64, device="cuda")
     dist.all_reduce(tc, op=dist.ReduceOp.SUM)
     elapsed = float(tt.item())
-    # the last batch against the unsharded index (rank 0's own queries)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_ids.cpu().numpy(), out_sc.cpu().numpy(), out_cnt.cpu().numpy(), out_msz.cpu().numpy())
+    # --full: the last batch against the unsharded index (rank 0's own queries)
     same = None
-    if rank == 0:
+    if args.full and rank == 0:
         o, c, s = qsets[(args.steps - 1) % len(qsets)]
         qf = pkg.QueryBatch(index, o[:nql + 1], c[:o[nql]], s[:o[nql]], cfg, now_ms=now_ms)
         qf.run(); qf.finish()
@@ -116,7 +144,7 @@ def run_cluster_range(args, pkg, lib, index, comm, dist, torch, rank, world, loc
             "exchange_postings_per_step_all_gpus": int(tc[2].item()) / max(args.steps, 1),
             "exchange_bytes_per_gpu_per_step": int(tc[2].item()) * 16 / max(args.steps, 1) / world,
             "sharded_equals_unsharded": same, "fallback_units": info["fallback_units"] if info else 0,
-            "roofline": None, "cpu_baseline": None, "corpus_build_s": t_corpus,
+            "roofline": None, "cpu_baseline": None, "corpus_build_s": t_corpus, "full": args.full,
         }
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     dist.barrier()
@@ -176,7 +204,17 @@ def main():
     ap.add_argument("--mb-wait-us", type=int, default=200, help="max_wait_us of the micro-batching queue in that leg")
     ap.add_argument("--mb-dispatchers", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = min(cpu_count, 16))")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: per-kernel timings "
+                         "(roofline), the end-to-end and micro-batched legs, oracle parity, both recall fields, the CPU baseline "
+                         "and, sharded, the comparison with the unsharded index (the options above tune these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (ids, scores, counts, map sizes) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.workload != "sann" and args.dump_outputs:
+        ap.error("--dump-outputs is for --workload sann")
     if args.workload != "sann":
         import subprocess
         tool = os.path.join(ROOT, "tools", "dense_bench.py" if args.workload == "dense" else "hnsw_bench.py")
@@ -449,7 +487,8 @@ def main():
         for _ in range(args.warmup):
             step()
         # the timed region carries HIP events around the dominant kernel only (two per step; each event costs the
-        # stream ~5 us); the descriptor and merge kernels are timed over a few extra steps afterwards
+        # stream ~5 us), with or without --full, so that ms_per_step is the same measurement either way; --full times
+        # the descriptor and merge kernels over a few extra steps afterwards
         sync()
         for qb in qbs:
             qb.set_profiling(1)
@@ -461,20 +500,26 @@ def main():
         sync()
         elapsed = time.perf_counter() - t0
         runs_timed = list(runs)
+        if args.dump_outputs and rank == 0:
+            # the last timed step's answer (sharded: the owner's merged answer of this rank's queries)
+            last = ((out_ids.cpu().numpy(), out_sc.cpu().numpy(), out_cnt.cpu().numpy(), out_msz.cpu().numpy()) if sharded
+                    else qbs[prev[0]].results())
+            dump_outputs(args.dump_outputs, *last)
         unit_ms = sum(qb.kernel_times()[0] for qb in qbs)
         n_timed = sum(qb.kernel_times()[2] for qb in qbs)
-        for qb in qbs:
-            qb.set_profiling(2)
-        alone[0] = True  # a few more steps, one batch at a time: each kernel's duration with the GPU to itself
-        n_aux = max(3, min(10, args.steps))
-        for _ in range(n_aux):
-            step()
-        sync()
-        alone[0] = False
-        unit_alone_ms = sum(qb.kernel_times()[0] for qb in qbs) / n_aux
-        merge_ms = sum(qb.kernel_times()[1] for qb in qbs)
-        desc_ms = sum(qb.desc_time() for qb in qbs)
-        merge_ms, desc_ms = merge_ms * n_timed / n_aux, desc_ms * n_timed / n_aux  # reported as per-launch averages below
+        if args.full:
+            for qb in qbs:
+                qb.set_profiling(2)
+            alone[0] = True  # a few more steps, one batch at a time: each kernel's duration with the GPU to itself
+            n_aux = max(3, min(10, args.steps))
+            for _ in range(n_aux):
+                step()
+            sync()
+            alone[0] = False
+            unit_alone_ms = sum(qb.kernel_times()[0] for qb in qbs) / n_aux
+            merge_ms = sum(qb.kernel_times()[1] for qb in qbs)
+            desc_ms = sum(qb.desc_time() for qb in qbs)
+            merge_ms, desc_ms = merge_ms * n_timed / n_aux, desc_ms * n_timed / n_aux  # reported as per-launch averages below
         for qb in qbs:
             qb.set_profiling(False)
         # ---- results: candidates every prepared batch returns (the rotated batches differ), and batch 0's answer (query
@@ -524,7 +569,7 @@ def main():
     # its own pooled batch object and stream.  Reported beside `value`, never instead of it: PCIe-inclusive.
     e2e = None
     n_e2e = args.steps if args.e2e_steps < 0 else args.e2e_steps
-    if not sharded and n_e2e > 0:
+    if args.full and not sharded and n_e2e > 0:
         import threading
 
         sa = pkg.simclusters_ann
@@ -612,7 +657,7 @@ def main():
     # pthreads; Python only sets it up.  Reported beside `value`, never instead of it.
     mb_leg = None
     load_so = os.path.join(ROOT, "tools", "micro", "libbatcher_load.so")
-    if not sharded and n_e2e > 0 and args.mb_threads > 0 and os.path.exists(load_so):
+    if args.full and not sharded and n_e2e > 0 and args.mb_threads > 0 and os.path.exists(load_so):
         load = ctypes.CDLL(load_so)
         load.batcher_load_run.restype = ctypes.c_int
         load.batcher_load_run.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
@@ -647,9 +692,9 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- parity spot check against the oracle (outside the timed region) -----------------------
-    oracle = ge.load_oracle()
-    n_check = min(args.check_queries, nql) if (co is not None or world == 1) else 0
+    # ---- --full: parity spot check against the oracle (outside the timed region) ----------------
+    oracle = ge.load_oracle() if args.full else None
+    n_check = min(args.check_queries, nql) if args.full and (co is not None or world == 1) else 0
     exact = 0
     if n_check:
         L = host_lists(n_check)
@@ -662,7 +707,7 @@ def main():
 
     # ---- quality recall@400: approximate top-400 vs the exact full-embedding cosine top-400 --
     recall_quality = None
-    if world == 1 and co is None and args.quality_queries > 0 and args.alg == "cosine":
+    if args.full and world == 1 and co is None and args.quality_queries > 0 and args.alg == "cosine":
         nqq = min(args.quality_queries, nq)
         e_ids, _e_cos, e_cnt = index.exact_cosine_topk(offs[:nqq + 1], cids[:offs[nqq]], scs[:offs[nqq]], 400)
         hit = tot = 0
@@ -677,7 +722,7 @@ def main():
     #      users draw 90 % of their clusters from their topic's 64), host-generated at --quality-topical-tweets, the operator on
     #      the GPU vs the exact full cosine by scipy over every tweet's full embedding (tools/quality_topics.py) -----------------
     recall_topical = None
-    if world == 1 and co is None and args.quality_topical_tweets > 0 and args.alg == "cosine":
+    if args.full and world == 1 and co is None and args.quality_topical_tweets > 0 and args.alg == "cosine":
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
         import quality_topics
         r = quality_topics.run(pkg, args.quality_topical_tweets, 32, 2000, 400, alg)
@@ -686,7 +731,7 @@ def main():
 
     # ---- CPU baseline: the C restatement of the Scala path on the host cores, bounded sample ---
     cpu = None
-    if not args.no_cpu_baseline and (co is not None or world == 1):
+    if args.full and not args.no_cpu_baseline and (co is not None or world == 1):
         # a 1-GPU box's CPU share is 16 cores even when 256 logical CPUs are visible
         cores = args.cpu_threads or min(os.cpu_count() or 1, 16)
         n_s = min(nq, 256)
@@ -710,25 +755,27 @@ def main():
                          f"{legs['optimized'][1]:.1f} s = `optimized_value`; {cores} threads; C restatement of the Scala CPU path, "
                          f"not the JVM (no boxing, allocation or GC modelled)"}
 
-    # ---- roofline of the dominant kernel (unit kernel: gather + accumulate + select) -----------
+    # ---- --full: roofline of the dominant kernel (unit kernel: gather + accumulate + select) ---
     # algorithmic bytes per launch: sum_q P_q*16 + n*12 + k_out*16
-    unit_avg_ms = unit_ms / max(n_timed, 1)
-    achieved = alg_bytes / (unit_avg_ms * 1e-3) / 1e9 if unit_avg_ms > 0 else 0.0
     distinct_clusters = int(len(np.unique(np.concatenate([q[1] for q in qsets[:n_rot]]))))
-    roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            "traffic": traffic_bytes(args, nq, world), "kernel": "sann::unit_fast_kernel (gather+accumulate+select)",
-            "kernel_avg_ms": unit_avg_ms, "desc_kernel_avg_ms": desc_ms / max(n_timed, 1),
-            "merge_kernel_avg_ms": merge_ms / max(n_timed, 1), "algorithmic_bytes_per_launch": alg_bytes,
-            # the timed region keeps batches in flight, so its unit kernel shares the GPU with the previous batch's
-            # merge kernel and the next batch's descriptor kernel; *_alone = the same launch with the GPU to itself
-            # (steps after the timed region, one batch at a time), as are the desc / merge figures above
-            "frac_against": ("HBM3E 8 TB/s: the timed loop rotates %d distinct prepared batches (%d distinct scanned clusters, up to "
-                             "%.2f GB of distinct postings between two runs of the same batch), beyond L2 32 MB + Infinity Cache "
-                             "256 MB; the corpus's hottest clusters (Zipf head, shared by all batches) still hit in cache, as they "
-                             "would in service" % (n_rot, distinct_clusters, distinct_clusters * 800 * 16 / 1e9)) if n_rot >= 8 else
-                            "HBM3E 8 TB/s, but the loop replays %d batch(es): their postings can stay in the 256 MB Infinity Cache" % n_rot,
-            "kernel_avg_ms_alone": unit_alone_ms,
-            "frac_alone": (alg_bytes / (unit_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if unit_alone_ms > 0 else 0.0}
+    roof = None
+    if args.full:
+        unit_avg_ms = unit_ms / max(n_timed, 1)
+        achieved = alg_bytes / (unit_avg_ms * 1e-3) / 1e9 if unit_avg_ms > 0 else 0.0
+        roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic_bytes(args, nq, world), "kernel": "sann::unit_fast_kernel (gather+accumulate+select)",
+                "kernel_avg_ms": unit_avg_ms, "desc_kernel_avg_ms": desc_ms / max(n_timed, 1),
+                "merge_kernel_avg_ms": merge_ms / max(n_timed, 1), "algorithmic_bytes_per_launch": alg_bytes,
+                # the timed region keeps batches in flight, so its unit kernel shares the GPU with the previous batch's
+                # merge kernel and the next batch's descriptor kernel; *_alone = the same launch with the GPU to itself
+                # (steps after the timed region, one batch at a time), as are the desc / merge figures above
+                "frac_against": ("HBM3E 8 TB/s: the timed loop rotates %d distinct prepared batches (%d distinct scanned clusters, up to "
+                                 "%.2f GB of distinct postings between two runs of the same batch), beyond L2 32 MB + Infinity Cache "
+                                 "256 MB; the corpus's hottest clusters (Zipf head, shared by all batches) still hit in cache, as they "
+                                 "would in service" % (n_rot, distinct_clusters, distinct_clusters * 800 * 16 / 1e9)) if n_rot >= 8 else
+                                "HBM3E 8 TB/s, but the loop replays %d batch(es): their postings can stay in the 256 MB Infinity Cache" % n_rot,
+                "kernel_avg_ms_alone": unit_alone_ms,
+                "frac_alone": (alg_bytes / (unit_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if unit_alone_ms > 0 else 0.0}
 
     line = {
         "metric": "candidates/sec + recall@400, 100M-tweet SimClusters-ANN @1/2/4/8 GPU",
@@ -761,12 +808,13 @@ def main():
         "quality_checked_queries": (min(args.quality_queries, nq) if recall_quality is not None else 0),
         "parity_checked_queries": n_check,
         "fallback_units": n_fallback_units,
-        "sharded_equals_unsharded": check_sharded_against_unsharded() if world > 1 else None,
+        "sharded_equals_unsharded": check_sharded_against_unsharded() if world > 1 and args.full else None,
         "roofline": roof,
         "end_to_end": e2e,
         "micro_batched": mb_leg,
         "cpu_baseline": cpu,
         "corpus_build_s": t_corpus,
+        "full": args.full,
     }
     if json_fd is not None:
         os.write(json_fd, (json.dumps(line) + "\n").encode())

@@ -90,7 +90,7 @@ def test_bench_sharded_modes_with_one_rank(sharding):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--exercise-exchange", "--sharding", sharding, "--tweets", "2000000",
-                        "--queries-per-gpu", "128", "--steps", "3", "--warmup", "1", "--rotate", "2", "--no-cpu-baseline", "--e2e-steps", "0"],
+                        "--queries-per-gpu", "128", "--steps", "3", "--warmup", "1", "--rotate", "2", "--full", "--no-cpu-baseline", "--e2e-steps", "0"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
