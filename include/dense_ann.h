@@ -56,6 +56,23 @@ int dann_index_build_exact(int32_t device, int32_t metric, int64_t n, int32_t d,
                            dann_index_t **out);
 /* Synthetic index generated on the device: i.i.d. N(0,1) components (BASELINE configs[3]: 50M x 256). */
 int dann_index_build_synthetic(int32_t device, int32_t metric, int64_t n, int32_t d, uint64_t seed, dann_index_t **out);
+/* BruteForceIndex.append (BruteForceIndex.scala:40-64) for n more rows (row-major fp32 [n][d], the index's d), on the device.
+ * An index built with ids needs ids (n of them); one built without needs ids = NULL, its ids being positions.  The rows are
+ * prepared as at build time (fp16 fragments, Cosine normalised, the L2 bias; in exact mode the fp32 rows and the largest
+ * norm too) into positions n_old .., a build's id order within the call, filling the partly used last tile first; the
+ * index grows by whole tiles and its padding rows stay inert.  Buffers grow by 1.5x at least, device to device (exactly to
+ * the capacity after dann_index_reserve).  The contract: a search on build(X0) + append(X1) + ... returns the ids, distance
+ * bits and counts of a search on build(X0 ++ X1 ++ ...), fast and exact mode alike.  Ties order by id (positions follow
+ * ids in a build; when an append's ids are not all at or above the largest stored id, the index keeps the rank of every
+ * position in (id, position) order on the device and selection orders ties by it).  Pass A's sample depends on how the rows
+ * arrived, but it only sets the threshold pass B emits above: what is selected is the same.  Ids present or absent contrary
+ * to the index, or a count out of range: DANN_EINVAL with the index unchanged.  One call at a time per index, appends and
+ * searches alike. */
+int dann_index_append(dann_index_t *index, int64_t n, const float *vectors, const int64_t *ids);
+/* Room for `capacity` rows (rounded up to whole tiles) without reallocating; never shrinks. */
+int dann_index_reserve(dann_index_t *index, int64_t capacity);
+/* Rows, dimension and metric of the index (any pointer may be NULL). */
+int dann_index_info(const dann_index_t *index, int64_t *n, int32_t *d, int32_t *metric);
 /* The stored (fp16-rounded, for Cosine normalised) vectors [i0, i0+n) as fp32: audit / oracle input. */
 int dann_index_get_vectors(const dann_index_t *index, int64_t i0, int64_t n, float *out);
 int dann_index_destroy(dann_index_t *index);

@@ -91,8 +91,41 @@ int hnsw_index_build_insert_gpu(int32_t device, int32_t metric, int64_t n, int32
                                 int32_t max_m, int32_t ef_construction, uint64_t seed, int32_t batch, hnsw_index_t **out);
 int hnsw_index_build_insert_gpu_levels(int32_t device, int32_t metric, int64_t n, int32_t d, const float *vectors, const int64_t *ids,
                                        int32_t max_m, int32_t ef_construction, const int32_t *levels, int32_t batch, hnsw_index_t **out);
-/* Counters of the last device build of this index (any pointer may be NULL): rounds run, additions a re-selection did not see,
- * candidate-queue prunes, candidates dropped because a pruned queue was still full. */
+/* Hnsw.append / HnswIndex.insert (Hnsw.scala:86-114, HnswIndex.java:153-200) for n more rows, on the device, with the rounds
+ * of the device builder above continued on the live graph.  Works on an index from any constructor (a loaded graph, the host
+ * builder, the device builder).
+ *   rows    the new rows take positions n_old .. n_old + n - 1; vectors is row-major fp32 [n][d] with the index's d, prepared
+ *           as at build time (fp16 rows, normalised for Cosine)
+ *   keys    an index created with ids needs ids (n keys); one created without needs ids = NULL, its keys being positions.  A
+ *           key already in the index or repeated among the n is IllegalDuplicateInsertException: HNSW_EINVAL, message naming it.
+ *           The check runs on the device against a sorted copy of the index's keys, kept on the handle from the first append
+ *   levels  _levels: given, each in 0..60.  Otherwise drawn with the builder's formula at the row's GLOBAL position, so that
+ *           build(X0, seed) then append(X1, seed) draws the levels of build(X0 ++ X1, seed)
+ *   order   the new rows by (level descending, position ascending)
+ *   rounds  the builder's schedule continued: min(batch, max(1, linked / 8), remaining) rows per round, linked = n_old at the
+ *           start; batch 0 = 4096.  Each round is phases A and B of the builder against one snapshot
+ *   entry   a new row above the graph's maxLevel is wired on the layers up to the old maxLevel from the old entry point, within
+ *           its round's snapshot; after that round it is the entry point and maxLevel is its level (HnswIndex.java:163-198 with
+ *           the round as the unit of interleaving; of several such rows in one round the first in order wins).  Later rounds
+ *           walk from it.  Appending to an empty index makes the first new row in order the entry point, as a build does
+ * So append(build_gpu(X0), X1) with every new row at level 0 and n_old on a round boundary of the schedule is the device
+ * build of X0 ++ X1 (tests/test_hnsw_append_gpu.py holds it against oracle_hnsw_build_batched).
+ * Refused with HNSW_EINVAL before anything changes: a duplicate key, ids present or absent contrary to the index, a level
+ * outside 0..60, ef_construction outside 1..256, batch outside 0..2^20, n_old + n >= 2^31 - 1.  A device error part-way
+ * leaves the index unusable: every later call on it fails with HNSW_EDEVICE.
+ * Room: the buffers grow by 1.5x at least, device to device (exactly to the capacity after hnsw_index_reserve).  The host copy
+ * of the graph that exports and files read is refreshed by the first such call after an append, not by the append.
+ * One call at a time per index, appends and searches alike (the handle's scratch is shared), as for hnsw_search.
+ * hnsw_index_build_stats reports the last append. */
+int hnsw_index_append(hnsw_index_t *index, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction,
+                      uint64_t seed, int32_t batch);
+int hnsw_index_append_levels(hnsw_index_t *index, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction,
+                             const int32_t *levels, int32_t batch);
+/* Room for `capacity` rows without reallocating the per-row buffers (capacity below the current room: nothing happens; it never
+ * shrinks).  The rows of the upper layers, about one per maxM rows, still grow by 1.5x. */
+int hnsw_index_reserve(hnsw_index_t *index, int64_t capacity);
+/* Counters of the last device build or append of this index (any pointer may be NULL): rounds run, additions a re-selection did
+ * not see, candidate-queue prunes, candidates dropped because a pruned queue was still full. */
 int hnsw_index_build_stats(const hnsw_index_t *index, int64_t *rounds, int64_t *unseen_additions, int64_t *queue_prunes,
                            int64_t *dropped_candidates);
 int hnsw_index_graph_size(const hnsw_index_t *index, int64_t *n_entries, int64_t *n_neighbours, int64_t *entry_point,

@@ -29,6 +29,7 @@
 //   select  per query: sort the <= CAP survivors by (score desc, position asc), convert to distances.
 // Positions are in id order (the builder sorts by id), so ties resolve by id ascending.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -568,9 +569,12 @@ __global__ void refine_kernel(float *__restrict__ tau, uint32_t *__restrict__ cn
   }
 }
 
-// per query: sort survivors by (score desc, position asc), emit the k nearest as distances
+// per query: sort survivors by (score desc, position asc), emit the k nearest as distances.  When appends left the positions
+// out of id order, `rank` / `rpos` (position -> rank in id order and back; else NULL) make that (score desc, id asc): the
+// order of an index built in one call over the same rows.
 __global__ __launch_bounds__(512) void select_kernel(const Survivor *__restrict__ surv, const uint32_t *__restrict__ done_cnt,
                                                      const float *__restrict__ qsumsq, const int64_t *__restrict__ ids,
+                                                     const uint32_t *__restrict__ rank, const uint32_t *__restrict__ rpos,
                                                      int metric, int k, float *__restrict__ out_dist,
                                                      int64_t *__restrict__ out_ids, int32_t *__restrict__ out_counts) {
   extern __shared__ unsigned long long keys[];
@@ -582,7 +586,7 @@ __global__ __launch_bounds__(512) void select_kernel(const Survivor *__restrict_
     unsigned long long key = 0;
     if (i < c) {
       Survivor s = surv[(size_t)q * CAP + i];
-      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - s.pos);
+      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - (rank ? rank[s.pos] : s.pos));
     }
     keys[i] = key;
   }
@@ -609,6 +613,7 @@ __global__ __launch_bounds__(512) void select_kernel(const Survivor *__restrict_
       unsigned long long key = keys[i];
       float sc = key2f((uint32_t)(key >> 32));
       uint32_t pos = 0xffffffffu - (uint32_t)key;
+      if (rank) pos = rpos[pos];
       id = ids ? ids[pos] : (int64_t)pos;
       if (metric == DANN_METRIC_L2) dist = sqrtf(fmaxf(0.0f, qsumsq[q] - 2.0f * sc));
       else dist = 1.0f - sc;
@@ -745,6 +750,12 @@ struct dann_index {
   Buf x32, xss32, tau_used;  // exact mode: fp32 rows [n][d] (Cosine: unit length), their squared norms, per-query thresholds
   bool has_ids = false, exact = false;
   float max_norm = 0.0f;     // exact mode: largest |x| of the stored rows
+  float max_ss = 0.0f;       // exact mode: largest |x|^2 (max_norm is its root, widened)
+  // appends (dann_index_append)
+  int64_t cap_pad = 0;       // rows the buffers hold (a multiple of the tile); 0 = n_pad
+  bool id_order = true;      // positions are in id order (a build sorts by id; an append keeps it while its ids come last)
+  int64_t max_id = 0;        // largest id stored (with ids)
+  Buf rank, rpos, rank_keys, rank_tmp;  // !id_order: position -> rank in (id, position) order, and back
   // per-search scratch (grown on demand, reused)
   Buf q_in, qf, qsumsq, tmax, tau, cnt, done_cnt, surv, status, flags, o_dist, o_ids, o_cnt;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -807,6 +818,50 @@ int launch_gemm_any(int S, bool emit, bool bias, const GemmArgs &a, hipStream_t 
   }
 }
 
+// ---- appends (dann_index_append) ----
+__global__ void iota_kernel(uint32_t *__restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (uint32_t)i;
+}
+// rpos = positions in (id, position) order -> rank[rpos[r]] = r
+__global__ void rank_scatter_kernel(const uint32_t *__restrict__ rpos, int64_t n, uint32_t *__restrict__ rank) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n) rank[rpos[r]] = (uint32_t)r;
+}
+
+// growth that keeps the first `keep` bytes (device to device); the old buffer goes only once the new one holds them
+hipError_t grow_keep(Buf &b, size_t keep, size_t want) {
+  if (b.p && want <= b.bytes) return hipSuccess;
+  void *p = nullptr;
+  hipError_t e = hipMalloc(&p, want ? want : 8);
+  if (e != hipSuccess) return e;
+  if (keep && b.p) {
+    e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return e;
+    }
+  }
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  b.bytes = want ? want : 8;
+  return hipSuccess;
+}
+
+// room for cap_pad rows (a multiple of the tile) in every per-row buffer
+int dense_grow(dann_index *ix, int64_t cap_pad) {
+  const size_t row_bytes = (size_t)ix->S * 16 * sizeof(_Float16);
+  DTRY(grow_keep(ix->xf, (size_t)ix->n_pad * row_bytes, (size_t)cap_pad * row_bytes));
+  DTRY(grow_keep(ix->bias, (size_t)ix->n_pad * sizeof(float), (size_t)cap_pad * sizeof(float)));
+  if (ix->has_ids) DTRY(grow_keep(ix->ids, (size_t)ix->n * sizeof(int64_t), (size_t)cap_pad * sizeof(int64_t)));
+  if (ix->exact) {
+    DTRY(grow_keep(ix->x32, (size_t)ix->n * ix->d * sizeof(float), (size_t)cap_pad * ix->d * sizeof(float)));
+    DTRY(grow_keep(ix->xss32, (size_t)ix->n * sizeof(float), (size_t)cap_pad * sizeof(float)));
+  }
+  ix->cap_pad = std::max(ix->cap_pad, cap_pad);
+  return DANN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -843,6 +898,7 @@ static int build_impl(int32_t device, int32_t metric, int64_t n, int32_t d, cons
     DTRY(ix->ids.reserve((size_t)n * sizeof(int64_t)));
     DTRY(hipMemcpy(ix->ids.p, sorted.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
     ix->has_ids = true;
+    ix->max_id = sorted[(size_t)n - 1];
   }
   const int64_t chunk = std::max<int64_t>(1, (int64_t)(256u << 20) / ((int64_t)d * 4));
   Buf stage;
@@ -878,6 +934,7 @@ static int build_impl(int32_t device, int32_t metric, int64_t n, int32_t d, cons
     float mx = 0.0f;
     for (float v : ss) mx = std::max(mx, v);
     ix->max_norm = std::sqrt(mx) * 1.0001f;
+    ix->max_ss = mx;
     ix->exact = true;
   }
   hipLaunchKernelGGL(bias_kernel, dim3((unsigned)((ix->n_pad + 255) / 256)), dim3(256), 0, 0, ix->bias.as<float>(), n,
@@ -1086,6 +1143,7 @@ static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int3
                            CAP * sizeof(unsigned long long)));
   hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
                      ix->done_cnt.as<uint32_t>(), ix->qsumsq.as<float>(), ix->has_ids ? ix->ids.as<int64_t>() : nullptr,
+                     ix->id_order ? nullptr : ix->rank.as<uint32_t>(), ix->id_order ? nullptr : ix->rpos.as<uint32_t>(),
                      ix->metric, k, ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
   DTRY(hipGetLastError());
   DTRY(hipEventRecord(ix->ev[3], st));
@@ -1098,6 +1156,112 @@ static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int3
   (void)hipEventElapsedTime(&ix->t_sel, ix->ev[2], ix->ev[3]);
   return DANN_OK;
 }
+
+int dann_index_append(dann_index_t *ix, int64_t n, const float *vectors, const int64_t *ids) try {
+  if (!ix) return fail(DANN_EINVAL, "null index");
+  if (n < 0) return fail(DANN_EINVAL, "n must not be negative");
+  if (n == 0) return DANN_OK;
+  if (!vectors) return fail(DANN_EINVAL, "null vectors");
+  if (ix->has_ids && !ids) return fail(DANN_EINVAL, "the index was built with ids: an append must give ids");
+  if (!ix->has_ids && ids) return fail(DANN_EINVAL, "the index was built without ids (its ids are positions): ids must be NULL");
+  const int64_t n_old = ix->n, total = n_old + n;
+  if (total >= (int64_t)0xffffff00u) return fail(DANN_EINVAL, "vector count out of range");
+  DTRY(hipSetDevice(ix->device));
+  const int d = ix->d;
+  // the new rows in id order, as a build orders them
+  std::vector<int64_t> order;
+  if (ids) {
+    order.resize((size_t)n);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return ids[x] < ids[y]; });
+  }
+  // room: whole tiles, amortised by 1.5x (exactly the capacity after dann_index_reserve); a failed growth changes nothing
+  const int64_t tile = (int64_t)W2 * ix->VB * 32;
+  const int64_t need_pad = (total + tile - 1) / tile * tile;
+  const int64_t have = std::max(ix->cap_pad, ix->n_pad);
+  // (a build sizes ids and the fp32 rows by n, not by whole tiles: the first append brings them to `have` rows)
+  if (int rc = dense_grow(ix, need_pad > have ? std::max(need_pad, (have + have / 2 + tile - 1) / tile * tile) : have)) return rc;
+  const size_t row_bytes = (size_t)ix->S * 16 * sizeof(_Float16);
+  // padding rows are zero in the fragments and -inf in the bias: the tiles the index grows into start zeroed
+  if (need_pad > ix->n_pad) DTRY(hipMemsetAsync((char *)ix->xf.p + (size_t)ix->n_pad * row_bytes, 0, (size_t)(need_pad - ix->n_pad) * row_bytes, 0));
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)(256u << 20) / ((int64_t)d * 4));
+  DTRY(ix->q_in.reserve((size_t)std::min(chunk, n) * d * sizeof(float)));  // (the search's query staging, between searches)
+  std::vector<float> gathered;
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t m = std::min(chunk, n - r0);
+    const float *src = vectors + r0 * d;
+    if (ids) {
+      gathered.resize((size_t)m * d);
+      for (int64_t i = 0; i < m; ++i)
+        std::memcpy(&gathered[(size_t)i * d], vectors + order[(size_t)(r0 + i)] * d, (size_t)d * sizeof(float));
+      src = gathered.data();
+    }
+    DTRY(hipMemcpy(ix->q_in.p, src, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, ix->q_in.as<float>(), m, d, ix->S,
+                       ix->metric == DANN_METRIC_COSINE ? 1 : 0, n_old + r0, ix->xf.as<_Float16>(), ix->bias.as<float>());
+    DTRY(hipGetLastError());
+    if (ix->exact) {
+      hipLaunchKernelGGL(store_rows_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, ix->q_in.as<float>(), m, d,
+                         ix->metric == DANN_METRIC_COSINE ? 1 : 0, n_old + r0, ix->x32.as<float>(), ix->xss32.as<float>());
+      DTRY(hipGetLastError());
+    }
+  }
+  // the bias of the new rows (and -inf on the padding after them): bias_kernel over [n_old, need_pad)
+  hipLaunchKernelGGL(bias_kernel, dim3((unsigned)((need_pad - n_old + 255) / 256)), dim3(256), 0, 0, ix->bias.as<float>() + n_old, n,
+                     need_pad - n_old, ix->metric);
+  DTRY(hipGetLastError());
+  if (ix->exact) {  // the largest norm over all rows, as a build of all of them computes it
+    std::vector<float> ss((size_t)n);
+    DTRY(hipMemcpy(ss.data(), ix->xss32.as<float>() + n_old, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    for (float v : ss) ix->max_ss = std::max(ix->max_ss, v);
+    ix->max_norm = std::sqrt(ix->max_ss) * 1.0001f;
+  }
+  if (ids) {
+    std::vector<int64_t> sorted((size_t)n);
+    for (int64_t i = 0; i < n; ++i) sorted[(size_t)i] = ids[order[(size_t)i]];
+    DTRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, sorted.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (sorted[0] < ix->max_id) ix->id_order = false;  // (equal ids stay in arrival order, as a build's stable sort keeps them)
+    ix->max_id = std::max(ix->max_id, sorted[(size_t)n - 1]);
+    if (!ix->id_order) {  // rank in (id, position) order: the tie order of a build over the same rows
+      size_t tb = 0;
+      DTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const uint32_t *)nullptr,
+                                              (uint32_t *)nullptr, (int)total, 0, 64, (hipStream_t)0));
+      DTRY(ix->rank_tmp.reserve(tb));
+      DTRY(ix->rank_keys.reserve((size_t)total * sizeof(int64_t)));
+      DTRY(ix->rank.reserve((size_t)total * sizeof(uint32_t)));
+      DTRY(ix->rpos.reserve((size_t)total * sizeof(uint32_t)));
+      hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, ix->rank.as<uint32_t>(), total);
+      DTRY(hipGetLastError());
+      DTRY(hipcub::DeviceRadixSort::SortPairs(ix->rank_tmp.p, tb, ix->ids.as<int64_t>(), ix->rank_keys.as<int64_t>(), ix->rank.as<uint32_t>(),
+                                              ix->rpos.as<uint32_t>(), (int)total, 0, 64, (hipStream_t)0));
+      hipLaunchKernelGGL(rank_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, ix->rpos.as<uint32_t>(), total,
+                         ix->rank.as<uint32_t>());
+      DTRY(hipGetLastError());
+    }
+  }
+  DTRY(hipDeviceSynchronize());
+  ix->n = total;
+  ix->n_pad = need_pad;
+  return DANN_OK;
+} ABI_CATCH
+
+int dann_index_reserve(dann_index_t *ix, int64_t capacity) try {
+  if (!ix) return fail(DANN_EINVAL, "null index");
+  if (capacity < 0 || capacity >= (int64_t)0xffffff00u) return fail(DANN_EINVAL, "capacity out of range");
+  const int64_t tile = (int64_t)W2 * ix->VB * 32;
+  const int64_t want = (capacity + tile - 1) / tile * tile;
+  if (want <= std::max(ix->cap_pad, ix->n_pad)) return DANN_OK;  // never shrinks
+  DTRY(hipSetDevice(ix->device));
+  return dense_grow(ix, want);
+} ABI_CATCH
+
+int dann_index_info(const dann_index_t *ix, int64_t *n, int32_t *d, int32_t *metric) try {
+  if (!ix) return fail(DANN_EINVAL, "null index");
+  if (n) *n = ix->n;
+  if (d) *d = ix->d;
+  if (metric) *metric = ix->metric;
+  return DANN_OK;
+} ABI_CATCH
 
 int dann_last_rounds(const dann_index_t *ix, int32_t *rounds) try {
   if (!ix || !rounds) return fail(DANN_EINVAL, "null argument");

@@ -564,6 +564,9 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
 // holds BUILD_CCAP entries -- when full, entries farther than the current bound (which can never be expanded: the walk
 // stops at the first such entry, :589-591) are dropped and the heap is rebuilt in array order; a re-selection sees the first
 // LINK_CAP entries of old list + additions.
+// Appends (hnsw_index_append) run the same two kernels on a live graph: the rounds continue the schedule from linked = n, and
+// the entry point / maxLevel are per round (BuildArgs.entry, max_level), since a new row above maxLevel takes over as the entry
+// point once its round is done.
 // ---------------------------------------------------------------------------------------------
 constexpr int BUILD_EF_MAX = 256;  // efConstruction
 constexpr int BUILD_CCAP = 1024;   // candidate-queue entries of a construction walk
@@ -921,6 +924,70 @@ __global__ void hnsw_rows_to_f32(const _Float16 *__restrict__ src, int64_t i0, i
   dst[e] = (float)src[(i0 + e / d) * dpad + e % d];
 }
 
+// ---- the keys of an append (hnsw_index_append): IllegalDuplicateInsertException on the device ----
+// The index keeps its keys sorted (`table`, nt entries); an append sorts its own keys (`b`, nb entries) and every key looks
+// itself up: a repeat of its predecessor in the batch, or a hit in the table, is a duplicate.  The first offending batch
+// index (in sorted order) is left in *bad (which starts at INT32_MAX).
+__global__ void hnsw_key_probe_kernel(const int64_t *__restrict__ table, int64_t nt, const int64_t *__restrict__ b, int64_t nb,
+                                      int32_t *__restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb) return;
+  const int64_t k = b[i];
+  bool dup = i > 0 && b[i - 1] == k;
+  if (!dup) {
+    int64_t lo = 0, hi = nt;  // lower_bound
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (table[mid] < k) lo = mid + 1;
+      else hi = mid;
+    }
+    dup = lo < nt && table[lo] == k;
+  }
+  if (dup) atomicMin(bad, (int32_t)i);
+}
+
+// Merge path: the sorted table and the sorted batch into one sorted table of na + nb keys.  Thread t writes outputs
+// [t * MERGE_ITEMS, (t + 1) * MERGE_ITEMS): a binary search along that diagonal finds how many of them come from `a`, then a
+// sequential merge of MERGE_ITEMS steps (ties: `a` first; an append that reaches this has no ties).
+constexpr int MERGE_ITEMS = 8;
+__global__ void hnsw_key_merge_kernel(const int64_t *__restrict__ a, int64_t na, const int64_t *__restrict__ b, int64_t nb,
+                                      int64_t *__restrict__ out) {
+  const int64_t total = na + nb;
+  const int64_t diag = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * MERGE_ITEMS;
+  if (diag >= total) return;
+  int64_t lo = diag > nb ? diag - nb : 0, hi = diag < na ? diag : na;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (a[mid] <= b[diag - 1 - mid]) lo = mid + 1;
+    else hi = mid;
+  }
+  int64_t i = lo, j = diag - lo;
+  for (int s = 0; s < MERGE_ITEMS && diag + s < total; ++s) {
+    const bool take_a = j >= nb || (i < na && a[i] <= b[j]);
+    out[diag + s] = take_a ? a[i++] : b[j++];
+  }
+}
+
+// Device buffer growth that keeps the first `keep` bytes (device to device) and frees the old buffer only once the new one
+// holds them: a failed growth leaves the buffer as it was.
+hipError_t grow_keep(Buf &b, size_t keep, size_t want) {
+  if (b.p && want <= b.bytes) return hipSuccess;
+  void *p = nullptr;
+  hipError_t e = hipMalloc(&p, want ? want : 8);
+  if (e != hipSuccess) return e;
+  if (keep && b.p) {
+    e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return e;
+    }
+  }
+  if (b.p) (void)hipFree(b.p);
+  b.p = p;
+  b.bytes = want ? want : 8;
+  return hipSuccess;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -944,7 +1011,20 @@ struct hnsw_index {
   int32_t last_spilled = 0;
   int64_t last_peak = 0, last_adm = 0;
   float last_ms = 0;
-  int64_t build_rounds = 0, build_truncated = 0, build_prunes = 0, build_dropped = 0;  // hnsw_index_build_insert_gpu
+  int64_t build_rounds = 0, build_truncated = 0, build_prunes = 0, build_dropped = 0;  // hnsw_index_build_insert_gpu / _append
+  int64_t search_vwords = 0;  // bitmap layout of the last search: a different one is a fresh layout (visited_dirty)
+  // ---- hnsw_index_append: room, host-mirror state, and construction scratch kept across calls ----
+  int64_t cap = 0;              // rows the per-row buffers (x, adj0, upper_slot, ids, levels) hold; 0 = n
+  int64_t upper_rows_cap = 0, upper_slots_cap = 0;
+  bool keyed = false;           // created with ids (has_ids may be false only because n was 0)
+  bool broken = false;          // a device error part-way through an append: every later call fails with HNSW_EDEVICE
+  mutable bool host_stale = false;  // level0 / upper / has0 / has_upper behind the device graph (refreshed by an export)
+  Buf levels;                   // [cap] levels of appended rows (read by the insert kernel by position)
+  Buf b_order, b_pair_off, b_keys, b_sorted, b_tmp, b_bstats, b_visited, b_vlog;
+  int64_t bv_items = 0, bv_vwords = 0;
+  bool bv_clean = false;        // b_visited is all zeros (what a walk with an undo log needs at its start)
+  Buf key_table, key_next, key_in, key_batch, key_tmp, key_bad;  // sorted keys of the index (built at the first append)
+  int64_t key_n = -1;           // entries of key_table; -1 = not built yet
   ~hnsw_index() {
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -1273,6 +1353,7 @@ int create_index(int32_t device, int32_t metric, int64_t n, int32_t d, const flo
     HTRY(hipMemcpy(ix->ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
     ix->has_ids = true;
   }
+  ix->keyed = ids != nullptr;
   if (host_rows) {  // the stored rows, as floats, for the host-side builder
     std::vector<_Float16> h((size_t)n * ix->dpad);
     if (n > 0) HTRY(hipMemcpy(h.data(), ix->x.p, h.size() * sizeof(_Float16), hipMemcpyDeviceToHost));
@@ -1323,6 +1404,16 @@ int hnsw_index_build(int32_t device, int32_t metric, int64_t n, int32_t d, const
     if (entry_level[e] < 0 || entry_level[e] > max_level || entry_item[e] < 0 || entry_item[e] >= n)
       return fail(HNSW_EINVAL, "graph entry out of range");
     tops[(size_t)entry_item[e]] = std::max(tops[(size_t)entry_item[e]], entry_level[e]);
+  }
+  // Rows also for every layer a node can be REACHED on without a key of its own there -- the entry point on layers up to
+  // maxLevel, a neighbour on its list's layer: empty rows, which searches read as the absent list they are, and which an
+  // append (whose walks read and whose back links write the rows of every node they reach) needs to exist.
+  if (entry_point >= 0) tops[(size_t)entry_point] = std::max(tops[(size_t)entry_point], max_level);
+  for (int64_t e = 0; e < n_entries && entry_neighbours; ++e) {
+    if (entry_offsets[e + 1] < entry_offsets[e] || entry_offsets[e + 1] - entry_offsets[e] > 2 * (int64_t)max_m) continue;  // (refused below)
+    for (int64_t j = entry_offsets[e]; j < entry_offsets[e + 1]; ++j)
+      if (entry_neighbours[j] >= 0 && entry_neighbours[j] < n)
+        tops[(size_t)entry_neighbours[j]] = std::max(tops[(size_t)entry_neighbours[j]], entry_level[e]);
   }
   HostGraph g;
   g.init(n, max_m, tops);
@@ -1566,6 +1657,7 @@ static int build_insert_gpu_impl(int32_t device, int32_t metric, int64_t n, int3
     HTRY(hipMemcpy(ix->ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
     ix->has_ids = true;
   }
+  ix->keyed = ids != nullptr;
   *out = ix.release();
   return HNSW_OK;
 }
@@ -1581,6 +1673,338 @@ int hnsw_index_build_insert_gpu_levels(int32_t device, int32_t metric, int64_t n
   return build_insert_gpu_impl(device, metric, n, d, vectors, ids, max_m, ef_construction, 0, levels, batch, out);
 } ABI_CATCH
 
+// ---- hnsw_index_append -------------------------------------------------------------------------------------------------
+// Rounds of the device builder continued on a live index: see include/hnsw_ann.h.  The host works out the new rows' levels,
+// their order and the round schedule (functions of the levels and n_old alone), grows the buffers device to device, and
+// enqueues kernels; what comes back per call is O(1): the first duplicate key, if any, and the round counters.
+static const char *const BROKEN = "an earlier append failed on the device part-way: the index is unusable";
+
+static int append_keys_check(hnsw_index *ix, int64_t n, const int64_t *ids) {
+  const int64_t n_old = ix->n;
+  size_t tmp_bytes = 0;
+  const int64_t most = std::max<int64_t>(std::max<int64_t>(n_old, n), 1);
+  HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, (const int64_t *)nullptr, (int64_t *)nullptr, (int)most, 0, 64, (hipStream_t)0));
+  HTRY(ix->key_tmp.reserve(tmp_bytes));
+  if (ix->key_n < 0) {  // the sorted table of the keys already in the index, once
+    HTRY(ix->key_table.reserve((size_t)std::max<int64_t>(n_old, 1) * 8));
+    if (n_old > 0) {
+      size_t tb = tmp_bytes;
+      HTRY(hipcub::DeviceRadixSort::SortKeys(ix->key_tmp.p, tb, ix->ids.as<int64_t>(), ix->key_table.as<int64_t>(), (int)n_old, 0, 64, (hipStream_t)0));
+    }
+    ix->key_n = n_old;
+  }
+  HTRY(ix->key_in.reserve((size_t)n * 8));
+  HTRY(ix->key_batch.reserve((size_t)n * 8));
+  HTRY(ix->key_bad.reserve(4));
+  HTRY(hipMemcpy(ix->key_in.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  size_t tb = tmp_bytes;
+  HTRY(hipcub::DeviceRadixSort::SortKeys(ix->key_tmp.p, tb, ix->key_in.as<int64_t>(), ix->key_batch.as<int64_t>(), (int)n, 0, 64, (hipStream_t)0));
+  HTRY(hipMemsetAsync(ix->key_bad.p, 0x7f, 4, 0));
+  hipLaunchKernelGGL(hnsw_key_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ix->key_table.as<int64_t>(), ix->key_n,
+                     ix->key_batch.as<int64_t>(), n, ix->key_bad.as<int32_t>());
+  HTRY(hipGetLastError());
+  int32_t bad = 0;
+  HTRY(hipMemcpy(&bad, ix->key_bad.p, 4, hipMemcpyDeviceToHost));
+  if (bad >= 0 && bad < n) {
+    int64_t k[2] = {0, 0};
+    const int64_t from = bad > 0 ? bad - 1 : bad;
+    HTRY(hipMemcpy(k, ix->key_batch.as<int64_t>() + from, (size_t)(bad - from + 1) * 8, hipMemcpyDeviceToHost));
+    const int64_t key = k[bad - from];
+    if (bad > 0 && k[0] == key) return fail(HNSW_EINVAL, "duplicate key " + std::to_string(key) + ": it appears twice in the appended rows");
+    return fail(HNSW_EINVAL, "duplicate key " + std::to_string(key) + ": it is already in the index");
+  }
+  return HNSW_OK;
+}
+
+// the host copy of the graph after appends: every list from the device; a key exists where the host recorded one (loaded,
+// or wired by a build or an append) or where a list is not empty (a back link made it)
+static int refresh_host(const hnsw_index *cix) {
+  if (!cix->host_stale) return HNSW_OK;
+  hnsw_index *ix = const_cast<hnsw_index *>(cix);
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
+  HTRY(hipSetDevice(ix->device));
+  const int64_t n = ix->n;
+  std::vector<uint32_t> adj0((size_t)n * (ix->m0 + 1));
+  if (n > 0) HTRY(hipMemcpy(adj0.data(), ix->adj0.p, adj0.size() * 4, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t *row = &adj0[(size_t)i * (ix->m0 + 1)];
+    ix->level0[(size_t)i].assign(row + 1, row + 1 + row[0]);
+    ix->has0[(size_t)i] |= row[0] > 0 ? 1 : 0;
+  }
+  const int64_t urows = ix->upper_base_h.back();
+  std::vector<uint32_t> uadj((size_t)urows * (ix->m + 1));
+  if (urows > 0) HTRY(hipMemcpy(uadj.data(), ix->upper_adj.p, uadj.size() * 4, hipMemcpyDeviceToHost));
+  for (size_t s = 0; s + 1 < ix->upper_base_h.size(); ++s)
+    for (int l = 1; l <= ix->upper_base_h[s + 1] - ix->upper_base_h[s]; ++l) {
+      const uint32_t *row = uadj.data() + (size_t)(ix->upper_base_h[s] + l - 1) * (ix->m + 1);
+      ix->upper[(size_t)l - 1][s].assign(row + 1, row + 1 + row[0]);
+      ix->has_upper[s][(size_t)l - 1] |= row[0] > 0 ? 1 : 0;
+    }
+  ix->host_stale = false;
+  return HNSW_OK;
+}
+
+static int append_impl(hnsw_index *ix, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction, uint64_t seed,
+                       const int32_t *given_levels, int32_t batch) {
+  // ---- everything that can be refused is refused before anything changes ----
+  if (!ix) return fail(HNSW_EINVAL, "NULL index");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
+  if (n < 0) return fail(HNSW_EINVAL, "n must not be negative");
+  if (ef_construction < 1 || ef_construction > BUILD_EF_MAX) return fail(HNSW_EINVAL, "ef_construction must be in 1..256");
+  if (batch < 0 || batch > (1 << 20)) return fail(HNSW_EINVAL, "batch must be in 0..2^20");
+  if (batch == 0) batch = 4096;
+  if (n == 0) return HNSW_OK;
+  if (!vectors) return fail(HNSW_EINVAL, "NULL vectors");
+  if (ix->keyed && !ids) return fail(HNSW_EINVAL, "the index was created with ids: an append must give ids");
+  if (!ix->keyed && ids) return fail(HNSW_EINVAL, "the index was created without ids (its keys are positions): ids must be NULL");
+  const int64_t n_old = ix->n;
+  if (n_old + n >= (int64_t)0x7fffffff) return fail(HNSW_EINVAL, "the index would reach 2^31 - 1 rows");
+  std::vector<int32_t> lv((size_t)n);
+  const double level_mult = 1.0 / std::log(1.0 * ix->m);  // HnswIndex.java:118
+  for (int64_t i = 0; i < n; ++i) {
+    if (given_levels) {
+      if (given_levels[i] < 0 || given_levels[i] > 60) return fail(HNSW_EINVAL, "a level is outside 0..60");
+      lv[(size_t)i] = given_levels[i];
+      continue;
+    }
+    const uint64_t h = sann::mix64(seed ^ ((uint64_t)(n_old + i) * 0x9E3779B97F4A7C15ull));  // the builder's draw, global position
+    const double u = ((double)(h >> 11) + 1.0) * (1.0 / 9007199254740992.0);
+    lv[(size_t)i] = std::min(60, (int)(-std::log(u) * level_mult));
+  }
+  HTRY(hipSetDevice(ix->device));
+  if (ix->keyed) {
+    const int rc = append_keys_check(ix, n, ids);
+    if (rc) return rc;
+  }
+  // ---- order, rounds, entry point per round (host: functions of the levels and n_old) ----
+  std::vector<uint32_t> order((size_t)n);
+  for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (uint32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return lv[x] > lv[y]; });
+  struct Round {
+    int64_t at, count, entry;
+    int max_level;
+  };
+  std::vector<Round> rounds;
+  std::vector<int64_t> pair_off((size_t)n + 1, 0);
+  std::vector<int32_t> wired_top((size_t)n, -1);  // layers each new row is wired on (-1: it became the entry of an empty graph)
+  int64_t entry = ix->entry, at = 0, linked = n_old, max_keys = 0, max_items = 0;
+  int max_level = ix->max_level;
+  if (entry < 0) {  // an empty graph: the first row in order is the entry point, as in a build
+    entry = n_old + order[0];
+    max_level = lv[order[0]];
+    at = 1;
+    linked = n_old + 1;
+  }
+  while (at < n) {
+    const int64_t m = std::min<int64_t>(n - at, std::min<int64_t>(batch, std::max<int64_t>(1, linked / 8)));
+    rounds.push_back({at, m, entry, max_level});
+    int64_t up = -1;
+    for (int64_t e = at; e < at + m; ++e) {
+      const uint32_t r = order[(size_t)e];
+      wired_top[r] = std::min(lv[r], max_level);
+      pair_off[(size_t)e + 1] = pair_off[(size_t)e] + (int64_t)(wired_top[r] + 1) * ix->m;
+      if (up < 0 && lv[r] > max_level) up = r;  // HnswIndex.java:193-198, the round as the unit of interleaving
+    }
+    max_keys = std::max(max_keys, pair_off[(size_t)(at + m)] - pair_off[(size_t)at]);
+    max_items = std::max(max_items, m);
+    if (up >= 0) {
+      entry = n_old + up;
+      max_level = lv[(size_t)up];
+    }
+    at += m;
+    linked += m;
+  }
+  if (max_keys >= (int64_t)1 << 31) return fail(HNSW_EINVAL, "batch * max_m too large");
+  // ---- new upper slots (rows at levels >= 1) at the end ----
+  const int64_t old_slots = (int64_t)ix->upper_base_h.size() - 1, old_rows = ix->upper_base_h.back();
+  std::vector<int32_t> new_slot((size_t)n, -1), new_base;
+  for (int64_t i = 0; i < n; ++i)
+    if (lv[(size_t)i] > 0) {
+      new_slot[(size_t)i] = (int32_t)(old_slots + (int64_t)new_base.size());
+      new_base.push_back((new_base.empty() ? (int32_t)old_rows : new_base.back()) + lv[(size_t)i]);
+    }
+  const int64_t n_slots = old_slots + (int64_t)new_base.size(), n_rows = new_base.empty() ? old_rows : new_base.back();
+  // ---- room: amortised (>= 1.5x), device to device; a failed growth leaves the index as it was ----
+  const int64_t need = n_old + n;
+  int64_t cap = std::max(ix->cap, n_old);
+  if (need > cap) cap = std::max(need, cap + cap / 2);
+  HTRY(grow_keep(ix->x, (size_t)n_old * ix->dpad * sizeof(_Float16), (size_t)cap * ix->dpad * sizeof(_Float16)));
+  HTRY(grow_keep(ix->adj0, (size_t)n_old * (ix->m0 + 1) * 4, (size_t)cap * (ix->m0 + 1) * 4));
+  HTRY(grow_keep(ix->upper_slot, (size_t)n_old * 4, (size_t)cap * 4));
+  HTRY(grow_keep(ix->levels, 0, (size_t)cap * 4));
+  if (ix->keyed) HTRY(grow_keep(ix->ids, (size_t)n_old * 8, (size_t)cap * 8));
+  ix->cap = cap;
+  int64_t slots_cap = std::max(ix->upper_slots_cap, old_slots + 1), rows_cap = std::max(ix->upper_rows_cap, std::max<int64_t>(old_rows, 1));
+  if (n_slots + 1 > slots_cap) slots_cap = std::max(n_slots + 1, slots_cap + slots_cap / 2);
+  if (n_rows > rows_cap) rows_cap = std::max(n_rows, rows_cap + rows_cap / 2);
+  HTRY(grow_keep(ix->upper_base, (size_t)(old_slots + 1) * 4, (size_t)slots_cap * 4));
+  HTRY(grow_keep(ix->upper_adj, (size_t)old_rows * (ix->m + 1) * 4, (size_t)rows_cap * (ix->m + 1) * 4));
+  ix->upper_slots_cap = slots_cap;
+  ix->upper_rows_cap = rows_cap;
+  // construction scratch (kept on the handle)
+  const int64_t vwords = ((cap + 31) / 32 + 255) / 256 * 256;
+  const bool use_vlog = vwords >= VLOG_MIN_VWORDS || getenv("HNSW_DEBUG_VLOG") != nullptr;  // (as in the builder)
+  size_t tmp_bytes = 0;
+  HTRY(ix->b_order.reserve((size_t)n * 4));
+  HTRY(ix->b_pair_off.reserve(((size_t)n + 1) * 8));
+  HTRY(ix->b_keys.reserve((size_t)std::max<int64_t>(max_keys, 1) * 8));
+  HTRY(ix->b_sorted.reserve((size_t)std::max<int64_t>(max_keys, 1) * 8));
+  HTRY(ix->b_bstats.reserve(4 * 8));
+  HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)std::max<int64_t>(max_keys, 1), 0, 64, (hipStream_t)0));
+  HTRY(ix->b_tmp.reserve(tmp_bytes));
+  if (max_items > 0 && (vwords != ix->bv_vwords || max_items > ix->bv_items)) {  // a new bitmap layout
+    const int64_t items = std::max(max_items, vwords == ix->bv_vwords ? std::min<int64_t>(2 * ix->bv_items, batch) : 0);
+    ix->bv_items = ix->bv_vwords = 0;
+    ix->bv_clean = false;
+    HTRY(ix->b_visited.reserve((size_t)items * vwords * 4));
+    ix->bv_items = items;
+    ix->bv_vwords = vwords;
+  }
+  if (max_items > 0 && use_vlog) HTRY(ix->b_vlog.reserve((size_t)ix->bv_items * VLOG_CAP * 4));
+  if (ix->keyed) HTRY(ix->key_next.reserve((size_t)cap * 8));
+
+  // ---- from here on the index changes: a device error leaves it broken ----
+  ix->broken = true;
+  {
+    const int64_t chunk = std::max<int64_t>(1, (int64_t)(128u << 20) / ((int64_t)ix->d * 4));
+    HTRY(ix->q_in.reserve((size_t)std::min(chunk, n) * ix->d * 4));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {  // hnsw_prep_rows, as at build time
+      const int64_t m = std::min(chunk, n - r0);
+      HTRY(hipMemcpy(ix->q_in.p, vectors + r0 * ix->d, (size_t)m * ix->d * 4, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(hnsw_prep_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, ix->q_in.as<float>(), m, ix->d, ix->dpad,
+                         ix->metric == HNSW_METRIC_COSINE ? 1 : 0, ix->x.as<_Float16>() + (n_old + r0) * ix->dpad);
+      HTRY(hipGetLastError());
+    }
+  }
+  if (ix->keyed) HTRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ix->key_in.p, (size_t)n * 8, hipMemcpyDeviceToDevice));
+  HTRY(hipMemcpy(ix->upper_slot.as<int32_t>() + n_old, new_slot.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  if (!new_base.empty())
+    HTRY(hipMemcpy(ix->upper_base.as<int32_t>() + old_slots + 1, new_base.data(), new_base.size() * 4, hipMemcpyHostToDevice));
+  HTRY(hipMemsetAsync(ix->adj0.as<uint32_t>() + (size_t)n_old * (ix->m0 + 1), 0, (size_t)n * (ix->m0 + 1) * 4, 0));
+  if (n_rows > old_rows)
+    HTRY(hipMemsetAsync(ix->upper_adj.as<uint32_t>() + (size_t)old_rows * (ix->m + 1), 0, (size_t)(n_rows - old_rows) * (ix->m + 1) * 4, 0));
+  HTRY(hipMemcpy(ix->levels.as<int32_t>() + n_old, lv.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  std::vector<uint32_t> gorder((size_t)n);
+  for (int64_t e = 0; e < n; ++e) gorder[(size_t)e] = (uint32_t)(n_old + order[(size_t)e]);
+  HTRY(hipMemcpy(ix->b_order.p, gorder.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  HTRY(hipMemcpy(ix->b_pair_off.p, pair_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+  HTRY(hipMemsetAsync(ix->b_bstats.p, 0, 4 * 8, 0));
+  if (max_items > 0) {
+    if (use_vlog && !ix->bv_clean) HTRY(hipMemsetAsync(ix->b_visited.p, 0, (size_t)ix->bv_items * vwords * 4, 0));  // once per layout
+    ix->bv_clean = use_vlog;  // (walks with the log leave their bitmaps clean; walks without it leave them dirty)
+    BuildArgs a;
+    a.x = ix->x.as<_Float16>();
+    a.adj0 = ix->adj0.as<uint32_t>();
+    a.upper_slot = ix->upper_slot.as<int32_t>();
+    a.upper_base = ix->upper_base.as<int32_t>();
+    a.upper_adj = ix->upper_adj.as<uint32_t>();
+    a.order = ix->b_order.as<uint32_t>();
+    a.levels = ix->levels.as<int32_t>();
+    a.pair_off = ix->b_pair_off.as<int64_t>();
+    a.visited = ix->b_visited.as<uint32_t>();
+    a.vlog = use_vlog ? ix->b_vlog.as<uint32_t>() : nullptr;
+    a.bstats = ix->b_bstats.as<unsigned long long>();
+    a.vwords = vwords;
+    a.dpad = ix->dpad;
+    a.metric = ix->metric;
+    a.m = ix->m;
+    a.m0 = ix->m0;
+    a.efc = ef_construction;
+    a.ccap = BUILD_CCAP;
+    if (const char *e = std::getenv("HNSW_BUILD_CCAP")) a.ccap = std::max(2, std::min(BUILD_CCAP, std::atoi(e)));
+    const int chunks = ix->dpad / 64;
+    for (const Round &r : rounds) {
+      a.entry = (uint32_t)r.entry;  // per round: a row above maxLevel moves the entry point for the rounds after its own
+      a.max_level = r.max_level;
+      a.at = (uint32_t)r.at;
+      a.count = (uint32_t)r.count;
+      a.n_keys = (uint32_t)(pair_off[(size_t)(r.at + r.count)] - pair_off[(size_t)r.at]);
+      BuildArgs a_ins = a, a_link = a;
+      a_ins.keys = ix->b_keys.as<uint64_t>();
+      a_link.keys = ix->b_sorted.as<uint64_t>();
+      launch_build_any(chunks, a_ins, a_link, 0, 0);
+      size_t tb = tmp_bytes;
+      HTRY(hipcub::DeviceRadixSort::SortKeys(ix->b_tmp.p, tb, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)a.n_keys, 0, 64, (hipStream_t)0));
+      launch_build_any(chunks, a_ins, a_link, 0, 1);
+      HTRY(hipGetLastError());
+    }
+  }
+  if (ix->keyed) {  // the new keys into the sorted table (merge path), then the tables swap
+    const int64_t total = ix->key_n + n, threads = (total + MERGE_ITEMS - 1) / MERGE_ITEMS;
+    hipLaunchKernelGGL(hnsw_key_merge_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, ix->key_table.as<int64_t>(), ix->key_n,
+                       ix->key_batch.as<int64_t>(), n, ix->key_next.as<int64_t>());
+    HTRY(hipGetLastError());
+  }
+  HTRY(hipDeviceSynchronize());
+  unsigned long long bs[4] = {0, 0, 0, 0};
+  HTRY(hipMemcpy(bs, ix->b_bstats.p, sizeof(bs), hipMemcpyDeviceToHost));
+  ix->broken = false;
+  if (ix->keyed) {
+    std::swap(ix->key_table.p, ix->key_next.p);
+    std::swap(ix->key_table.bytes, ix->key_next.bytes);
+    ix->key_n += n;
+  }
+  // ---- the host side: O(n) of appended rows; the lists themselves are read back only when exported ----
+  ix->build_truncated = (int64_t)bs[0];
+  ix->build_prunes = (int64_t)bs[1];
+  ix->build_dropped = (int64_t)bs[2];
+  ix->build_rounds = (int64_t)rounds.size();
+  ix->n = n_old + n;
+  ix->entry = entry;
+  ix->max_level = std::max(max_level, 0);
+  ix->has_ids = ix->keyed;
+  ix->upper_slot_h.resize((size_t)n_old);
+  ix->upper_slot_h.insert(ix->upper_slot_h.end(), new_slot.begin(), new_slot.end());
+  ix->upper_base_h.insert(ix->upper_base_h.end(), new_base.begin(), new_base.end());
+  ix->level0.resize((size_t)(n_old + n));
+  ix->has0.resize((size_t)n_old);
+  int top_all = (int)ix->upper.size();
+  for (int64_t i = 0; i < n; ++i) {
+    ix->has0.push_back(wired_top[(size_t)i] >= 0 ? 1 : 0);
+    if (lv[(size_t)i] > 0) {
+      std::vector<uint8_t> h((size_t)lv[(size_t)i], 0);
+      for (int l = 1; l <= lv[(size_t)i]; ++l) h[(size_t)l - 1] = l <= wired_top[(size_t)i] ? 1 : 0;
+      ix->has_upper.push_back(std::move(h));
+      top_all = std::max(top_all, lv[(size_t)i]);
+    }
+  }
+  ix->upper.resize((size_t)top_all);
+  for (auto &layer : ix->upper) layer.resize((size_t)n_slots);
+  ix->host_stale = true;
+  return HNSW_OK;
+}
+
+int hnsw_index_append(hnsw_index_t *ix, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction, uint64_t seed,
+                      int32_t batch) try {
+  return append_impl(ix, n, vectors, ids, ef_construction, seed, nullptr, batch);
+} ABI_CATCH
+
+int hnsw_index_append_levels(hnsw_index_t *ix, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction,
+                             const int32_t *levels, int32_t batch) try {
+  if (!levels && n > 0) return fail(HNSW_EINVAL, "levels is NULL");
+  return append_impl(ix, n, vectors, ids, ef_construction, 0, levels, batch);
+} ABI_CATCH
+
+int hnsw_index_reserve(hnsw_index_t *ix, int64_t capacity) try {
+  if (!ix) return fail(HNSW_EINVAL, "NULL index");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
+  if (capacity < 0 || capacity >= (int64_t)0x7fffffff) return fail(HNSW_EINVAL, "capacity out of range");
+  const int64_t n = ix->n;
+  if (capacity <= std::max(ix->cap, n)) return HNSW_OK;  // never shrinks
+  HTRY(hipSetDevice(ix->device));
+  HTRY(grow_keep(ix->x, (size_t)n * ix->dpad * sizeof(_Float16), (size_t)capacity * ix->dpad * sizeof(_Float16)));
+  HTRY(grow_keep(ix->adj0, (size_t)n * (ix->m0 + 1) * 4, (size_t)capacity * (ix->m0 + 1) * 4));
+  HTRY(grow_keep(ix->upper_slot, (size_t)n * 4, (size_t)capacity * 4));
+  HTRY(grow_keep(ix->levels, 0, (size_t)capacity * 4));
+  if (ix->keyed) {
+    HTRY(grow_keep(ix->ids, (size_t)n * 8, (size_t)capacity * 8));
+    if (ix->key_n >= 0) HTRY(grow_keep(ix->key_table, (size_t)ix->key_n * 8, (size_t)capacity * 8));
+    HTRY(ix->key_next.reserve((size_t)capacity * 8));
+  }
+  ix->cap = capacity;
+  return HNSW_OK;
+} ABI_CATCH
+
 int hnsw_index_build_stats(const hnsw_index_t *ix, int64_t *rounds, int64_t *unseen_additions, int64_t *queue_prunes, int64_t *dropped_candidates) try {
   if (!ix) return fail(HNSW_EINVAL, "NULL index");
   if (rounds) *rounds = ix->build_rounds;
@@ -1593,6 +2017,7 @@ int hnsw_index_build_stats(const hnsw_index_t *ix, int64_t *rounds, int64_t *uns
 int hnsw_index_graph_size(const hnsw_index_t *ix, int64_t *n_entries, int64_t *n_neighbours, int64_t *entry_point,
                           int32_t *max_level) try {
   if (!ix) return fail(HNSW_EINVAL, "NULL index");
+  if (int rc = refresh_host(ix)) return rc;
   int64_t ne = 0, nn = 0;
   for (int64_t i = 0; i < ix->n; ++i)
     if (ix->has0[(size_t)i]) {
@@ -1615,6 +2040,7 @@ int hnsw_index_graph_size(const hnsw_index_t *ix, int64_t *n_entries, int64_t *n
 int hnsw_index_graph(const hnsw_index_t *ix, int32_t *entry_level, int64_t *entry_item, int64_t *entry_offsets,
                      int64_t *entry_neighbours) try {
   if (!ix || !entry_level || !entry_item || !entry_offsets) return fail(HNSW_EINVAL, "NULL argument");
+  if (int rc = refresh_host(ix)) return rc;
   int64_t e = 0, pos = 0;
   entry_offsets[0] = 0;
   auto emit = [&](int level, int64_t item, const std::vector<uint32_t> &list) {
@@ -1636,6 +2062,7 @@ int hnsw_index_graph(const hnsw_index_t *ix, int32_t *entry_level, int64_t *entr
 
 int hnsw_index_get_vectors(const hnsw_index_t *ix, int64_t i0, int64_t n, float *out) try {
   if (!ix || !out || i0 < 0 || n < 0 || i0 + n > ix->n) return fail(HNSW_EINVAL, "range outside the index");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
   if (n == 0) return HNSW_OK;
   HTRY(hipSetDevice(ix->device));
   // in slabs: a launch stays far below 2^32 work-items (50M x 256 elements in ONE launch is 1.28e10 -- the grid wrapped and
@@ -1664,6 +2091,7 @@ int hnsw_index_info(const hnsw_index_t *ix, int64_t *n, int32_t *d, int32_t *met
 
 int hnsw_index_get_ids(const hnsw_index_t *ix, int64_t *out) try {
   if (!ix || (!out && ix->n > 0)) return fail(HNSW_EINVAL, "NULL argument");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
   if (ix->n == 0) return HNSW_OK;
   if (!ix->has_ids) {
     for (int64_t i = 0; i < ix->n; ++i) out[i] = i;
@@ -1686,6 +2114,7 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
   if (k < 1 || ef < 1) return fail(HNSW_EINVAL, "k and ef must be positive");
   const int beam = std::max(ef, k);  // HnswIndex.java:545
   if (beam > MAX_EF) return fail(HNSW_ELIMIT, "max(ef, k) above 1024");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
   ix->last_dist = ix->last_exp = 0;
   ix->last_spilled = 0;
   ix->last_ms = 0;
@@ -1705,7 +2134,8 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
   {
     const void *before = ix->visited.p;
     HTRY(ix->visited.reserve((size_t)per_launch * vwords * 4));
-    if (ix->visited.p != before) ix->visited_dirty = true;
+    if (ix->visited.p != before || vwords != ix->search_vwords) ix->visited_dirty = true;  // a new buffer or a new layout (appends grow n)
+    ix->search_vwords = vwords;
   }
   const bool use_vlog = vwords >= VLOG_MIN_VWORDS || getenv("HNSW_DEBUG_VLOG") != nullptr;  // (the variable: tests force the log on small graphs)
   HTRY(ix->o_dist.reserve((size_t)nq * k * 4));

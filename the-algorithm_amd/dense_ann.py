@@ -33,6 +33,9 @@ PROTOS = {
     "dann_index_build": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "dann_index_build_exact": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "dann_index_build_synthetic": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "dann_index_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "dann_index_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
+    "dann_index_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "dann_index_get_vectors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "dann_index_destroy": (C.c_int, [C.c_void_p]),
     "dann_search": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -64,8 +67,8 @@ def _check(lib, rc: int) -> None:
 
 
 class BruteForceIndex:
-    """Exhaustive index resident in HBM.  Unlike the reference's appendable in-memory queue
-    (BruteForceIndex.scala:48-64) it is built in one call: the device layout is immutable."""
+    """Exhaustive index resident in HBM, appendable like the reference's in-memory queue (BruteForceIndex.scala:40-64):
+    append() adds rows on the device, and a search answers as it would on one build over all rows so far."""
 
     def __init__(self, handle, metric: DistanceMetric, n: int, d: int):
         self._h, self.metric, self.n, self.d = handle, DistanceMetric(metric), n, d
@@ -96,8 +99,28 @@ class BruteForceIndex:
         _check(lib, lib.dann_index_build_synthetic(device, int(metric), n, d, seed, C.byref(h)))
         return cls(h, metric, n, d)
 
+    def append(self, vectors: np.ndarray, ids: Optional[Sequence[int]] = None) -> None:
+        """BruteForceIndex.append for every row (dann_index_append).  ids: required when the index was built with ids, else
+        None (ids = positions).  One caller at a time."""
+        lib = _lib()
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.d:
+            raise ValueError(f"vectors must be [n, {self.d}], got shape {v.shape}")
+        idp = None
+        if ids is not None:
+            idp = np.ascontiguousarray(ids, np.int64)
+            if idp.shape != (v.shape[0],):
+                raise ValueError("one id per vector")
+        _check(lib, lib.dann_index_append(self._h, v.shape[0], v.ctypes.data, idp.ctypes.data if idp is not None else None))
+        self.n += v.shape[0]
+
+    def reserve(self, capacity: int) -> None:
+        """Room for `capacity` rows without reallocating (dann_index_reserve); never shrinks."""
+        _check(_lib(), _lib().dann_index_reserve(self._h, int(capacity)))
+
     def stored_vectors(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
-        """The vectors as stored (fp16-rounded; unit length for Cosine), in position (= id) order."""
+        """The vectors as stored (fp16-rounded; unit length for Cosine), in position order (id order for a build and for
+        appends whose ids come after the stored ones)."""
         n = self.n - i0 if n is None else n
         out = np.empty((n, self.d), np.float32)
         lib = _lib()

@@ -29,6 +29,9 @@ PROTOS = {
                                               C.c_uint64, C.c_int32, C.POINTER(C.c_void_p)]),
     "hnsw_index_build_insert_gpu_levels": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                      C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "hnsw_index_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32]),
+    "hnsw_index_append_levels": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "hnsw_index_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
     "hnsw_index_build_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hnsw_index_graph_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "hnsw_index_graph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -73,7 +76,7 @@ class HnswParams:
 
 
 class Hnsw:
-    """Device-resident HNSW index (graph + vectors)."""
+    """Device-resident HNSW index (graph + vectors), appendable like the reference's (Hnsw.append, Hnsw.scala:86-114)."""
 
     def __init__(self, handle, metric, n, d, max_m):
         self._h, self.metric, self.n, self.d, self.max_m = handle, DistanceMetric(metric), n, d, max_m
@@ -124,6 +127,40 @@ class Hnsw:
         _check(lib, lib.hnsw_index_build(device, int(metric), v.shape[0], v.shape[1] if v.ndim == 2 else 1, _p(v), _p(i), max_m,
                                          int(entry), int(max_level), len(lv), _p(lv), _p(it), _p(off), _p(nb), C.byref(h)))
         return cls(h, metric, v.shape[0], v.shape[1], max_m)
+
+    def append(self, vectors: np.ndarray, ids: Optional[Sequence[int]] = None, *, ef_construction: int = 200, seed: int = 1,
+               levels: Optional[Sequence[int]] = None, batch: int = 0) -> None:
+        """Hnsw.append for every row of `vectors` (hnsw_index_append): new positions n .. n + len - 1, inserted on the device
+        with the device builder's rounds.  ids: required when the index was created with ids, else None (keys = positions).
+        A key already in the index, or repeated among `ids`, raises HnswError naming it and leaves the index unchanged.
+        levels: every new row's level, instead of the seeded draw at its global position.  One caller at a time."""
+        lib = _lib()
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.d:
+            raise ValueError(f"vectors must be [n][{self.d}], got shape {v.shape}")
+        i = None if ids is None else np.ascontiguousarray(ids, np.int64)
+        if i is not None and i.shape != (v.shape[0],):
+            raise ValueError("ids must hold one key per vector")
+        if levels is not None:
+            lv = np.ascontiguousarray(levels, np.int32)
+            if lv.shape != (v.shape[0],):
+                raise ValueError("levels must hold one level per vector")
+            _check(lib, lib.hnsw_index_append_levels(self._h, v.shape[0], _p(v), _p(i), ef_construction, _p(lv), batch))
+        else:
+            _check(lib, lib.hnsw_index_append(self._h, v.shape[0], _p(v), _p(i), ef_construction, seed, batch))
+        n = C.c_int64()
+        _check(lib, lib.hnsw_index_info(self._h, C.byref(n), None, None, None))
+        self.n = n.value
+
+    def reserve(self, capacity: int) -> None:
+        """Room for `capacity` rows without reallocating (hnsw_index_reserve); never shrinks."""
+        _check(_lib(), _lib().hnsw_index_reserve(self._h, int(capacity)))
+
+    def ids(self) -> np.ndarray:
+        """The keys searches return, by position (hnsw_index_get_ids)."""
+        out = np.zeros(max(self.n, 1), np.int64)
+        _check(_lib(), _lib().hnsw_index_get_ids(self._h, _p(out)))
+        return out[:self.n]
 
     def graph(self):
         lib = _lib()

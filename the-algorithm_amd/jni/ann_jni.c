@@ -52,6 +52,27 @@ JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_denseIndexDestroy(JNIEnv 
   (void)cls;
   dann_index_destroy((dann_index_t *)(intptr_t)index);
 }
+/* void denseIndexAppend(long index, long n, int d, ByteBuffer vectors /+ float[n][d] +/, ByteBuffer ids /+ long[n] or null +/)
+ * BruteForceIndex.append for n rows (dann_index_append); one writer at a time per index */
+JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_denseIndexAppend(JNIEnv *env, jclass cls, jlong index, jlong n, jint d, jobject vectors,
+                                                                        jobject ids) {
+  (void)cls;
+  if (n < 0 || d < 1 || (n > 0 && (!vectors || CAP(vectors) / 4 / d < n)) || (ids && CAP(ids) / 8 < n)) {
+    throw_runtime(env, "vectors must hold n x d floats (and ids n longs)");
+    return;
+  }
+  if (!index) {
+    throw_runtime(env, "null index");
+    return;
+  }
+  int32_t dim = 0;
+  if (dann_index_info((const dann_index_t *)(intptr_t)index, NULL, &dim, NULL) != DANN_OK || dim != d) {
+    throw_runtime(env, "d is not the index's dimension");
+    return;
+  }
+  if (dann_index_append((dann_index_t *)(intptr_t)index, n, (const float *)BUF(vectors), (const int64_t *)BUF(ids)) != DANN_OK)
+    throw_runtime(env, dann_last_error());
+}
 /* void denseSearch(long index, int nq, int d, ByteBuffer x /+ float[nq][d] +/, int k, ByteBuffer distances /+ float[nq][k] +/,
  *                  ByteBuffer labels /+ long[nq][k] +/, ByteBuffer counts /+ int[nq] +/) */
 JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_denseSearch(JNIEnv *env, jclass cls, jlong index, jint nq, jint d, jobject x, jint k,
@@ -118,6 +139,31 @@ JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_hnswIndexDestroy(JNIEnv *
   (void)env;
   (void)cls;
   hnsw_index_destroy((hnsw_index_t *)(intptr_t)index);
+}
+/* void hnswIndexAppend(long index, long n, int d, ByteBuffer vectors /+ float[n][d] +/, ByteBuffer ids /+ long[n] or null +/,
+ *                      int efConstruction, long seed)
+ * Hnsw.append / HnswIndex.insert for n rows on the device (hnsw_index_append, 4096 rows per round at most); a duplicate key is
+ * the RuntimeException in place of IllegalDuplicateInsertException.  One writer at a time per index (Hnsw.append takes
+ * readWriteFuturePool.write) */
+JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_hnswIndexAppend(JNIEnv *env, jclass cls, jlong index, jlong n, jint d, jobject vectors,
+                                                                       jobject ids, jint efConstruction, jlong seed) {
+  (void)cls;
+  if (n < 0 || d < 1 || (n > 0 && (!vectors || CAP(vectors) / 4 / d < n)) || (ids && CAP(ids) / 8 < n)) {
+    throw_runtime(env, "vectors must hold n x d floats (and ids n longs)");
+    return;
+  }
+  if (!index) {
+    throw_runtime(env, "null index");
+    return;
+  }
+  int32_t dim = 0;
+  if (hnsw_index_info((const hnsw_index_t *)(intptr_t)index, NULL, &dim, NULL, NULL) != HNSW_OK || dim != d) {
+    throw_runtime(env, "d is not the index's dimension");
+    return;
+  }
+  if (hnsw_index_append((hnsw_index_t *)(intptr_t)index, n, (const float *)BUF(vectors), (const int64_t *)BUF(ids), efConstruction,
+                        (uint64_t)seed, 0) != HNSW_OK)
+    throw_runtime(env, hnsw_last_error());
 }
 /* void hnswSearch(long index, int nq, int d, ByteBuffer x, int k, int ef, ByteBuffer distances, ByteBuffer labels, ByteBuffer counts)
  * = Hnsw.queryWithDistance for nq queries (HnswParams.ef; Hnsw.scala:125-147) */

@@ -21,6 +21,9 @@ public final class AnnJni {
 
   public static native void denseIndexDestroy(long index);
 
+  /** BruteForceIndex.append: vectors float[n][d] (d = the index's); ids long[n], or null when the index was built without. One writer at a time. */
+  public static native void denseIndexAppend(long index, long n, int d, ByteBuffer vectors, ByteBuffer ids);
+
   /** x: float[nq][d]; distances: float[nq][k]; labels: long[nq][k]; counts: int[nq]. */
   public static native void denseSearch(long index, int nq, int d, ByteBuffer x, int k, ByteBuffer distances, ByteBuffer labels,
                                         ByteBuffer counts);
@@ -34,6 +37,12 @@ public final class AnnJni {
                                                    String directory);
 
   public static native void hnswIndexDestroy(long index);
+
+  /**
+   * Hnsw.append / HnswIndex.insert for n rows, on the device: vectors float[n][d] (d = the index's); ids long[n], or null when the
+   * index was created without. A duplicate key throws. One writer at a time (Hnsw.append holds readWriteFuturePool.write).
+   */
+  public static native void hnswIndexAppend(long index, long n, int d, ByteBuffer vectors, ByteBuffer ids, int efConstruction, long seed);
 
   /**
    * ComposedQueryable.queryWithDistance (ShardApi.scala:71-87) over the batched answers of one index per GPU: ids long[nShards][nq][kIn],
