@@ -121,6 +121,55 @@ int hnsw_index_append(hnsw_index_t *index, int64_t n, const float *vectors, cons
                       uint64_t seed, int32_t batch);
 int hnsw_index_append_levels(hnsw_index_t *index, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction,
                              const int32_t *levels, int32_t batch);
+/* Hnsw.update (Hnsw.scala:161-181, SerializableHnsw.scala:191-195; trait Updatable, Api.scala:147-150) for n rows, on the device:
+ * the embedding of a key already in the index is overwritten and the key re-inserted (HnswIndex.reInsert, HnswIndex.java:220-329);
+ * a key not in the index is inserted.
+ *   keys     ids is required.  On an index created with ids they are keys: present keys are updated, then the absent ones are
+ *            appended in request order by hnsw_index_append (same ef_construction, seed and batch; levels drawn at their global
+ *            positions), so update(P ++ A) is update(P) then append(A); *out_appended (may be NULL) is their number.  On an index
+ *            created without ids they are positions, each < n: there is no upsert.  The key -> position table lives on the device
+ *            (built at the first update, rebuilt after an append)
+ *   rows     prepared as at build time (fp16, normalised for Cosine, Hnsw.scala:149-155)
+ *   rounds   the present rows in request order, `batch` per round (0 = 4096); each round, in this order:
+ *     1 vectors  the round's rows are written
+ *     2 relink   (:251-324) for each item u and each layer l = 0 .. top(u) with N_l(u) non-empty, where top(u) is the highest layer
+ *                <= maxLevel holding HnswNode(l, u) (:244-250; the existence the export shows: a key loaded or wired, or a non-empty
+ *                list).  setCand = u, then each e of N_l(u) in list order followed by N_l(e) in list order, first occurrence kept
+ *                (the reference's HashSet order is unspecified: insertion order is this library's choice).  For every v of N_l(u)
+ *                other than u (updateNeighborProbability = 1, :125,271) a proposal for v's list: setCand \ {v} offered in that
+ *                order to a max queue of min(efC, |set|) entries with the replacement rule of :292-309, then
+ *                selectNearestNeighboursByHeuristic with maxM0 on layer 0 and maxM above (:311-314).  All proposals read the graph
+ *                as the round found it; of several proposals for one (l, v) the latest item in request order wins (a later
+ *                reInsert overwrites an earlier one), the others are counted as superseded.  setCand is enumerated without a cap
+ *                (at most 1 + 2maxM + 4maxM^2 entries)
+ *     3 wire     (:328, wireConnectionForAllLayers(..., isUpdate = true)) the builder's phase A with the item's level = top(u) and
+ *                the index's entry point and maxLevel, which an update never changes.  The walk puts u in the candidate queue but
+ *                not the result queue (:607-609); when u is the entry point the walk starts at u and the heuristic drops it
+ *                (:488-491, :505-507).  The items' new lists (maxM entries on every layer, :392) are committed after every walk of
+ *                the round has ended.  A layer whose heuristic keeps nobody keeps u's old list and the walk continues from u (the
+ *                reference throws at neighbours.get(0), :439): counted as lists_kept
+ *     4 links    the builder's phase B over the round's items; an addition of u to a list that already holds u -- judged on the
+ *                graph after the commits of steps 2 and 3 -- is dropped and counted (:405-412)
+ *            A row without HnswNode(0, u), or any row of an index whose graph is empty, has its vector written and nothing else
+ *            (the reference's checkState fails there, :231-240).
+ * With batch = 1 this is the reference's single-writer sequence of reInsert calls, up to the builder's candidate-queue bound
+ * (BUILD_CCAP, see hnsw_index_build_insert_gpu) and, in a full re-selection of step 4, ties in distance broken by position
+ * instead of heap order.  tests/hnsw_update_ref.c restates both the rounds and the unbatched reInsert.
+ * Refused with HNSW_EINVAL before anything changes: a key repeated in the call, a position out of range, ef_construction outside
+ * 1..256, batch outside 0..2^20, NULL vectors or ids, n_old + (absent keys) >= 2^31 - 1, more than 2^27 relink proposal slots in
+ * one round (batch * layers * 2maxM; not reachable with batch <= 2^20 at usual level counts).  A device error part-way leaves the
+ * index unusable (as an append does).  If the append of the absent keys fails after the rounds (device memory for its growth,
+ * a device error), the present keys stay updated, the absent ones are not added, and the message says so; the index is then as
+ * after update(P) (or unusable, for a device error part-way through the append).
+ * The host copy of the graph is refreshed by the next export.  One call at a time per index, as for appends and searches. */
+int hnsw_index_update(hnsw_index_t *index, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction,
+                      uint64_t seed, int32_t batch, int64_t *out_appended);
+/* Counters of the last hnsw_index_update (any pointer may be NULL): rounds, relink proposals, proposals superseded by a later item
+ * of their round, back-link additions dropped because the list held the item already, distance evaluations of steps 2-4, and
+ * layers whose own list was kept because the heuristic returned nobody.  The append of absent keys reports to
+ * hnsw_index_build_stats. */
+int hnsw_index_update_stats(const hnsw_index_t *index, int64_t *rounds, int64_t *relinks, int64_t *relinks_superseded,
+                            int64_t *additions_already_present, int64_t *distance_evals, int64_t *lists_kept);
 /* Room for `capacity` rows without reallocating the per-row buffers (capacity below the current room: nothing happens; it never
  * shrinks).  The rows of the upper layers, about one per maxM rows, still grow by 1.5x. */
 int hnsw_index_reserve(hnsw_index_t *index, int64_t capacity);

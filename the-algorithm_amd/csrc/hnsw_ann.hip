@@ -590,6 +590,14 @@ struct BuildArgs {
   int32_t ccap;                // candidate-queue entries a walk may hold: BUILD_CCAP (smaller only for tests)
   uint32_t entry, at, count;   // the round = order[at .. at + count)
   uint32_t n_keys;
+  // hnsw_index_update only (order = the positions of the updated rows, in request order)
+  int32_t *utop;               // [order index] top(u) as the round's relink found it; -1 = no HnswNode(0, u)
+  const uint64_t *fmask;       // [order index] layers on which the host holds the key HnswNode(level, u)
+  const int64_t *prop_off;     // [order index + 1] first relink-proposal slot of an item ((storage layers) * m0 slots each)
+  uint32_t *props;             // [round slot][m0 + 1] relink proposals
+  uint64_t *pkeys;             // [round slot] (layer << 58 | v << 27 | slot), ~0 = unused
+  uint32_t *own;               // [key slot / m][m + 1] the items' own new lists, committed after the round's walks
+  uint32_t n_pkeys;
 };
 
 __device__ __forceinline__ uint32_t *layer_row(const BuildArgs &a, int level, uint32_t node) {
@@ -624,8 +632,10 @@ __device__ __forceinline__ float group_row_distance(const BuildArgs &a, uint32_t
 }
 
 // `kept` (nk entries) vs candidate c at distance dc from the base: is some kept node closer to c than the base is (:508-519)
+// (evals: distances computed, added when not NULL)
 template <int CH>
-__device__ __forceinline__ bool heuristic_drops(const BuildArgs &a, const uint32_t *kept, int nk, uint32_t c, float dc, int lane) {
+__device__ __forceinline__ bool heuristic_drops(const BuildArgs &a, const uint32_t *kept, int nk, uint32_t c, float dc, int lane,
+                                                unsigned long long *evals = nullptr) {
   const int g = lane >> 3, j = lane & 7;
   bool drop = false;
   for (int k0 = 0; k0 < nk && !drop; k0 += 8) {
@@ -633,11 +643,16 @@ __device__ __forceinline__ bool heuristic_drops(const BuildArgs &a, const uint32
     bool closer = false;
     if (k < nk) closer = group_row_distance<CH>(a, kept[k], c, j) < dc;
     drop = __ballot(closer) != 0ull;
+    if (evals) *evals += (unsigned long long)min(8, nk - k0);
   }
   return drop;
 }
 
-template <int CH>
+// UPD: the wiring of hnsw_index_update (wireConnectionForAllLayers(..., isUpdate = true), HnswIndex.java:328): the item's level
+// is top(u); the walk offers u to the candidate queue but not to the result queue (:607-609); the heuristic drops u, which is
+// among the candidates when the walk starts at it (:488-491, :505-507); the item's own lists go to a.own, and a layer whose
+// heuristic keeps nobody keeps its old list and continues from u (the reference throws at neighbours.get(0), :439)
+template <int CH, bool UPD>
 __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
   __shared__ HEntry wq[BUILD_EF_MAX + 1];
   __shared__ HEntry cq[BUILD_CCAP];
@@ -647,10 +662,11 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
   const int lane = threadIdx.x;
   const uint32_t t = blockIdx.x;
   const uint32_t item = a.order[a.at + t];
-  const int item_level = a.levels[item];
+  const int item_level = UPD ? a.utop[a.at + t] : a.levels[item];
+  if (UPD && item_level < 0) return;  // not in the graph: the row alone changes
   uint32_t *vis = a.visited + (size_t)t * a.vwords;
   uint32_t *vlog = a.vlog ? a.vlog + (size_t)t * VLOG_CAP : nullptr;  // (uniform)
-  unsigned long long n_prune = 0, n_dropped = 0;
+  unsigned long long n_prune = 0, n_dropped = 0, n_evals = 0, n_empty = 0;
 
   float qv[CH][8];  // the item's own stored row is the query (distFnIndex, item to item)
   {
@@ -670,6 +686,7 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
     __syncthreads();
     wave_distances<CH>(a, qv, ul, ud, 1, lane);
     __syncthreads();
+    if (UPD) n_evals += 1;
     float cur_dist = ud[0];
     for (int level = a.max_level; level > item_level; --level) {
       bool changed = true;
@@ -682,6 +699,7 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
         if (cnt > 0) {
           wave_distances<CH>(a, qv, ul, ud, cnt, lane);
           __syncthreads();
+          if (UPD) n_evals += (unsigned long long)cnt;
           for (int i = 0; i < cnt; ++i) {
             const float d = ud[i];
             if (d < cur_dist) {
@@ -709,6 +727,7 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
     __syncthreads();
     wave_distances<CH>(a, qv, ul, ud, 1, lane);
     __syncthreads();
+    if (UPD) n_evals += 1;
     int cn = 0, wn = 0;
     {
       const HEntry e0{ud[0], cur};
@@ -747,6 +766,7 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
       if (nu > 0) {
         wave_distances<CH>(a, qv, ul, ud, nu, lane);
         __syncthreads();
+        if (UPD) n_evals += (unsigned long long)nu;
         for (int i = 0; i < nu; ++i) {
           const HEntry e{ud[i], ul[i]};
           if (wn < ef || e.dist < wq[0].dist) {
@@ -761,6 +781,7 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
             }
             if (cn < a.ccap) pq_add<true>(cq, cn, e);
             else n_dropped += 1;
+            if (UPD && e.node == item) continue;  // (:607-609)
             pq_add<false>(wq, wn, e);
             if (wn > ef) (void)pq_poll<false>(wq, wn);
             lower = wq[0].dist;
@@ -773,8 +794,15 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
     // ---- selectNearestNeighboursByHeuristic(candidates, maxM) (:479-526); the item itself is never among them ----
     int nk = 0;
     if (wn <= a.m) {  // (:488-491) toListWithItem: the queue's ARRAY order
-      if (lane < wn) kept[lane] = wq[lane].node;
-      nk = wn;
+      if (!UPD) {
+        if (lane < wn) kept[lane] = wq[lane].node;
+        nk = wn;
+      } else {  // list.remove(baseElement): the item occurs at most once
+        const bool keep = lane < wn && wq[lane].node != item;
+        const unsigned long long mk = __ballot(keep);
+        if (keep) kept[__popcll(mk & ((1ull << lane) - 1))] = wq[lane].node;
+        nk = __popcll(mk);
+      }
       __syncthreads();
     } else {
       cn = 0;  // candidates.reverse() (:495): re-offered in array order under the reversed comparator
@@ -782,7 +810,8 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
       __syncthreads();
       while (cn > 0 && nk < a.m) {
         const HEntry c = pq_poll<true>(cq, cn);
-        if (!heuristic_drops<CH>(a, kept, nk, c.node, c.dist, lane)) {
+        if (UPD && c.node == item) continue;  // (:505-507)
+        if (!heuristic_drops<CH>(a, kept, nk, c.node, c.dist, lane, UPD ? &n_evals : nullptr)) {
           if (lane == 0) kept[nk] = c.node;
           nk++;
           __syncthreads();
@@ -790,22 +819,29 @@ __global__ __launch_bounds__(64) void hnsw_build_insert_kernel(BuildArgs a) {
       }
     }
     // ---- setConnectionList(item, level, neighbours) (:393); the back links become keys ----
-    uint32_t *row = layer_row(a, level, item);
+    uint32_t *row = UPD ? a.own + (size_t)((keys - a.keys) / a.m + (top - level)) * (a.m + 1) : layer_row(a, level, item);
     if (lane < nk) row[1 + lane] = kept[lane];
-    if (lane == 0) row[0] = (uint32_t)nk;
+    if (lane == 0) row[0] = UPD && nk == 0 ? ~0u : (uint32_t)nk;  // (UPD, nobody kept: the old list stays)
     uint64_t *kslot = keys + (size_t)(top - level) * a.m;
     if (lane < a.m)
       kslot[lane] = lane < nk ? ((uint64_t)level << 56) | ((uint64_t)kept[lane] << 24) | (uint64_t)t : ~0ull;
-    cur = kept[0];  // neighbours.get(0) (:439)
+    if (UPD && nk == 0) n_empty += 1;
+    cur = UPD && nk == 0 ? item : kept[0];  // neighbours.get(0) (:439)
     __syncthreads();
   }
   if (lane == 0 && (n_prune | n_dropped)) {
     atomicAdd(&a.bstats[1], n_prune);
     atomicAdd(&a.bstats[2], n_dropped);
   }
+  if (UPD && lane == 0) {
+    atomicAdd(&a.bstats[3], n_empty);
+    atomicAdd(&a.bstats[7], n_evals);
+  }
 }
 
-template <int CH>
+// UPD: the back links of hnsw_index_update (mutuallyConnectNewElement(..., isUpdate = true)): an addition of an item the list
+// already holds is dropped and counted (:405-412); the rest is the builder's phase B
+template <int CH, bool UPD>
 __global__ __launch_bounds__(64) void hnsw_build_backlink_kernel(BuildArgs a) {
   __shared__ uint32_t t_id[LINK_CAP];
   __shared__ float t_d[LINK_CAP];
@@ -835,8 +871,36 @@ __global__ __launch_bounds__(64) void hnsw_build_backlink_kernel(BuildArgs a) {
   const int M = level == 0 ? a.m0 : a.m;
   uint32_t *row = layer_row(a, level, base);
   const int old_n = (int)row[0];
+  if (UPD) {  // old list, then the additions it does not hold yet, into t_id (as far as LINK_CAP)
+    for (int i = lane; i < old_n; i += 64) t_id[i] = row[1 + i];
+    __syncthreads();
+    int kn = 0;
+    for (int b0 = 0; b0 < add_n; b0 += 64) {
+      const int i = b0 + lane;
+      uint32_t it = 0;
+      bool keep = false;
+      if (i < add_n) {
+        it = a.order[a.at + (uint32_t)(a.keys[i0 + i] & 0xffffffull)];
+        keep = true;
+        for (int e = 0; e < old_n; ++e)
+          if (t_id[e] == it) {
+            keep = false;
+            break;
+          }
+      }
+      const unsigned long long mk = __ballot(keep);
+      const int at = old_n + kn + __popcll(mk & ((1ull << lane) - 1));
+      if (keep && at < LINK_CAP) t_id[at] = it;
+      kn += __popcll(mk);
+    }
+    __syncthreads();
+    if (lane == 0 && kn < add_n) atomicAdd(&a.bstats[6], (unsigned long long)(add_n - kn));
+    add_n = kn;
+    if (add_n == 0) return;
+  }
   if (old_n + add_n <= M) {  // room: append, in order-index order (:414-417)
-    for (int i = lane; i < add_n; i += 64) row[1 + old_n + i] = a.order[a.at + (uint32_t)(a.keys[i0 + i] & 0xffffffull)];
+    for (int i = lane; i < add_n; i += 64)
+      row[1 + old_n + i] = UPD ? t_id[old_n + i] : a.order[a.at + (uint32_t)(a.keys[i0 + i] & 0xffffffull)];
     __syncthreads();
     if (lane == 0) row[0] = (uint32_t)(old_n + add_n);
     return;
@@ -846,8 +910,10 @@ __global__ __launch_bounds__(64) void hnsw_build_backlink_kernel(BuildArgs a) {
     if (lane == 0) atomicAdd(&a.bstats[0], (unsigned long long)(n - LINK_CAP));
     n = LINK_CAP;
   }
-  for (int i = lane; i < n; i += 64) t_id[i] = i < old_n ? row[1 + i] : a.order[a.at + (uint32_t)(a.keys[i0 + (i - old_n)] & 0xffffffull)];
+  if (!UPD)
+    for (int i = lane; i < n; i += 64) t_id[i] = i < old_n ? row[1 + i] : a.order[a.at + (uint32_t)(a.keys[i0 + (i - old_n)] & 0xffffffull)];
   __syncthreads();
+  unsigned long long n_evals = (unsigned long long)n;
   for (int r0 = 0; r0 < n; r0 += 8) {  // distances to the base, eight candidates per round
     const int i = r0 + g;
     float d = 0.0f;
@@ -870,7 +936,7 @@ __global__ __launch_bounds__(64) void hnsw_build_backlink_kernel(BuildArgs a) {
   for (int i = 0; i < n && nk < M; ++i) {
     const uint32_t c = c_id[i];
     if (c == base) continue;
-    if (!heuristic_drops<CH>(a, kept, nk, c, c_d[i], lane)) {
+    if (!heuristic_drops<CH>(a, kept, nk, c, c_d[i], lane, UPD ? &n_evals : nullptr)) {
       if (lane == 0) kept[nk] = c;
       nk++;
       __syncthreads();
@@ -879,12 +945,255 @@ __global__ __launch_bounds__(64) void hnsw_build_backlink_kernel(BuildArgs a) {
   __syncthreads();
   for (int i = lane; i < nk; i += 64) row[1 + i] = kept[i];
   if (lane == 0) row[0] = (uint32_t)nk;
+  if (UPD && lane == 0) atomicAdd(&a.bstats[7], n_evals);
+}
+
+// ---- hnsw_index_update: HnswIndex.reInsert (HnswIndex.java:226-329) in rounds (include/hnsw_ann.h) ----
+// Per round: the rows (hnsw_update_rows_kernel), the relink proposals against the graph as the round found it
+// (hnsw_update_relink_kernel), the latest proposal per (layer, v) committed (hnsw_update_relink_commit_kernel), the wiring
+// walks (hnsw_build_insert_kernel<UPD>) with the items' own lists committed after all of them (hnsw_update_own_commit_kernel),
+// and the back links (hnsw_build_backlink_kernel<UPD>).
+constexpr int SETCAND_MAX = 1 + 2 * MAX_M + 4 * MAX_M * MAX_M;  // u, N_l(u), and N_l(e) for every e: 4161 at maxM = 32
+
+// One wave per round item u.  top(u) (:244-250), then per layer 0..top(u) with a non-empty N_l(u) (:259-262): setCand in
+// insertion order -- u, then each e of N_l(u) followed by N_l(e), first occurrence kept (a HashSet in the reference) -- and for
+// every v of N_l(u) other than u (updateNeighborProbability = 1, :271) the proposal for v's list: setCand \ {v} offered in
+// enumeration order to a max queue of min(efC, |set|) entries (:281-309), then selectNearestNeighboursByHeuristic with maxM0 on
+// layer 0, maxM above (:311-314).  The walk's visited bitmap of the slot is the set's membership test; it is clean again after
+// every layer.
+template <int CH>
+__global__ __launch_bounds__(64) void hnsw_update_relink_kernel(BuildArgs a) {
+  __shared__ uint32_t sc[SETCAND_MAX];
+  __shared__ float sd[SETCAND_MAX];
+  __shared__ HEntry wq[BUILD_EF_MAX + 1];
+  __shared__ HEntry mq[BUILD_EF_MAX + 1];
+  __shared__ uint32_t nl[2 * MAX_M];
+  __shared__ uint32_t kept[2 * MAX_M];
+  const int lane = threadIdx.x, g = lane >> 3, j = lane & 7;
+  const uint32_t t = blockIdx.x;
+  const uint32_t item = a.order[a.at + t];
+  uint32_t *vis = a.visited + (size_t)t * a.vwords;
+  if (!a.vlog) {  // (without the undo log, bitmaps are left dirty by the walks: wipe; with it they are clean)
+    for (int64_t w = (int64_t)lane * 4; w < a.vwords; w += 256) *(uint4 *)(vis + w) = make_uint4(0u, 0u, 0u, 0u);
+    __threadfence_block();
+  }
+  // ---- top(u): the highest layer <= maxLevel on which HnswNode(layer, u) exists -- a key the host holds, or a non-empty
+  //      row -- and -1 when HnswNode(0, u) does not (the reference's checkState, :239-240) ----
+  const uint64_t fm = a.fmask[a.at + t];
+  const int32_t slot = a.upper_slot[item];
+  const int stor = slot < 0 ? 0 : a.upper_base[slot + 1] - a.upper_base[slot];
+  int top = -1;
+  if ((fm & 1ull) || a.adj0[(size_t)item * (a.m0 + 1)] > 0) {
+    top = 0;
+    for (int l = 1; l <= min(stor, a.max_level); ++l)
+      if (((fm >> l) & 1ull) || layer_row(a, l, item)[0] > 0) top = l;
+  }
+  if (lane == 0) a.utop[a.at + t] = top;
+  unsigned long long n_relinks = 0, n_evals = 0;
+  const int64_t pbase = a.prop_off[a.at + t] - a.prop_off[a.at];
+  for (int level = 0; level <= top; ++level) {
+    const uint32_t *row = layer_row(a, level, item);
+    const int cnt = (int)row[0];
+    if (cnt == 0) continue;
+    if (lane < cnt) nl[lane] = row[1 + lane];
+    if (lane == 0) {
+      sc[0] = item;
+      atomicOr(&vis[item >> 5], 1u << (item & 31));
+    }
+    int S = 1;
+    __syncthreads();
+    for (int e = 0; e < cnt; ++e) {
+      const uint32_t el = nl[e];
+      bool fresh = false;
+      if (lane == 0) {
+        const uint32_t bit = 1u << (el & 31);
+        fresh = (atomicOr(&vis[el >> 5], bit) & bit) == 0;
+        if (fresh) sc[S] = el;
+      }
+      S += __ballot(fresh) ? 1 : 0;
+      const uint32_t *r2 = layer_row(a, level, el);
+      const int c2 = (int)r2[0];
+      uint32_t nn = 0;
+      bool part = lane < c2;
+      if (part) nn = r2[1 + lane];
+      for (int k = 0; k < 64; ++k) {  // of an id repeated within the list, the first occurrence alone takes part
+        const uint32_t o = __shfl(nn, k, 64);
+        if (k < lane && k < c2 && o == nn) part = false;
+      }
+      fresh = false;
+      if (part) {
+        const uint32_t bit = 1u << (nn & 31);
+        fresh = (atomicOr(&vis[nn >> 5], bit) & bit) == 0;
+      }
+      const unsigned long long mk = __ballot(fresh);
+      if (fresh) sc[S + __popcll(mk & ((1ull << lane) - 1))] = nn;
+      S += __popcll(mk);
+      __syncthreads();
+    }
+    const int M = level == 0 ? a.m0 : a.m;
+    for (int jv = 0; jv < cnt; ++jv) {
+      const uint32_t v = nl[jv];
+      if (v == item) continue;  // setNeigh.remove(item) (:279)
+      for (int r0 = 0; r0 < S; r0 += 8) {  // distFnIndex.distance(neigh, cand), eight candidates per round
+        const int i = r0 + g;
+        float d = 0.0f;
+        if (i < S) d = group_row_distance<CH>(a, v, sc[i], j);
+        if (i < S && j == 0) sd[i] = d;
+      }
+      __syncthreads();
+      n_evals += (unsigned long long)S;
+      const int keep = min(a.efc, S - 1);  // |setCopy| = |setCand| - 1: v is in the set
+      int wn = 0;
+      for (int i = 0; i < S; ++i) {
+        const uint32_t c = sc[i];
+        if (c == v) continue;
+        const HEntry e{sd[i], c};
+        if (wn < keep) {
+          pq_add<false>(wq, wn, e);
+        } else if (e.dist < wq[0].dist) {
+          (void)pq_poll<false>(wq, wn);
+          pq_add<false>(wq, wn, e);
+        }
+      }
+      __syncthreads();
+      int nk = 0;
+      if (wn <= M) {  // toListWithItem (array order); v, the base, is not among them
+        if (lane < wn) kept[lane] = wq[lane].node;
+        nk = wn;
+      } else {
+        int cn = 0;
+        for (int i = 0; i < wn; ++i) pq_add<true>(mq, cn, wq[i]);
+        __syncthreads();
+        while (cn > 0 && nk < M) {
+          const HEntry c = pq_poll<true>(mq, cn);
+          if (!heuristic_drops<CH>(a, kept, nk, c.node, c.dist, lane, &n_evals)) {
+            if (lane == 0) kept[nk] = c.node;
+            nk++;
+            __syncthreads();
+          }
+        }
+      }
+      __syncthreads();
+      const int64_t ps = pbase + (int64_t)level * a.m0 + jv;
+      uint32_t *prow = a.props + (size_t)ps * (a.m0 + 1);
+      if (lane < nk) prow[1 + lane] = kept[lane];
+      if (lane == 0) {
+        prow[0] = (uint32_t)nk;
+        a.pkeys[ps] = ((uint64_t)level << 58) | ((uint64_t)v << 27) | (uint64_t)ps;
+      }
+      n_relinks += 1;
+      __syncthreads();
+    }
+    __threadfence_block();
+    for (int i = lane; i < S; i += 64) vis[sc[i] >> 5] = 0u;  // the bitmap clean again
+    __threadfence_block();
+    __syncthreads();
+  }
+  if (lane == 0) {
+    atomicAdd(&a.bstats[4], n_relinks);
+    atomicAdd(&a.bstats[7], n_evals);
+  }
+}
+
+// pkeys sorted: the last proposal of every (layer, v) run -- the latest item in request order -- is v's new list; the others are
+// superseded (a later reInsert overwrites an earlier one's setConnectionList)
+__global__ void hnsw_update_relink_commit_kernel(BuildArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)a.n_pkeys) return;
+  const uint64_t key = a.pkeys[i];
+  if (key == ~0ull) return;
+  const uint64_t run = key >> 27;
+  if (i + 1 < (int64_t)a.n_pkeys && (a.pkeys[i + 1] >> 27) == run) {
+    atomicAdd(&a.bstats[5], 1ull);
+    return;
+  }
+  const int level = (int)(key >> 58);
+  const uint32_t v = (uint32_t)(run & 0x7fffffffull);
+  const uint32_t *p = a.props + (size_t)(key & ((1ull << 27) - 1)) * (a.m0 + 1);
+  uint32_t *row = layer_row(a, level, v);
+  const uint32_t c = p[0];
+  for (uint32_t k = 0; k < c; ++k) row[1 + k] = p[1 + k];
+  row[0] = c;
+}
+
+// the items' own lists of the round, once every walk has ended (a layer whose heuristic kept nobody keeps its list)
+__global__ __launch_bounds__(64) void hnsw_update_own_commit_kernel(BuildArgs a) {
+  const uint32_t t = blockIdx.x;
+  const int lane = threadIdx.x;
+  const uint32_t item = a.order[a.at + t];
+  const int top = a.utop[a.at + t];
+  const int64_t kb = (a.pair_off[a.at + t] - a.pair_off[a.at]) / a.m;
+  for (int level = 0; level <= top; ++level) {
+    const uint32_t *o = a.own + (size_t)(kb + (top - level)) * (a.m + 1);
+    const uint32_t c = o[0];
+    if (c == ~0u) continue;
+    uint32_t *row = layer_row(a, level, item);
+    if ((uint32_t)lane < c) row[1 + lane] = o[1 + lane];
+    if (lane == 0) row[0] = c;
+  }
+}
+
+// the round's rows, prepared as at build time (hnsw_prep_rows), into their positions
+__global__ void hnsw_update_rows_kernel(const float *__restrict__ src, int64_t n, const uint32_t *__restrict__ pos, int d, int dpad,
+                                        int normalise, _Float16 *__restrict__ dst) {
+  int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const float *x = src + row * d;
+  float norm = 1.0f;
+  if (normalise) {
+    double ss = 0;
+    for (int k = lane; k < d; k += 64) ss += (double)x[k] * (double)x[k];
+    for (int o = 32; o; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    norm = (float)sqrt(ss);
+    if (!(norm > 0.0f)) norm = 1.0f;
+  }
+  _Float16 *y = dst + (int64_t)pos[row] * dpad;
+  for (int k = lane; k < dpad; k += 64) y[k] = (_Float16)(k < d ? x[k] / norm : 0.0f);
+}
+
+// key -> position of a keyed index: the (key, position) table sorted by key, one binary search per requested key (-1: absent)
+__global__ void hnsw_key_lookup_kernel(const int64_t *__restrict__ keys, const int64_t *__restrict__ pos, int64_t nt,
+                                       const int64_t *__restrict__ q, int64_t nq, int64_t *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  const int64_t k = q[i];
+  int64_t lo = 0, hi = nt;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  out[i] = lo < nt && keys[lo] == k ? pos[lo] : -1;
+}
+__global__ void hnsw_iota_kernel(int64_t *__restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = i;
+}
+
+template <int CH>
+void launch_update_round(const BuildArgs &a, hipStream_t st, int which, unsigned grid) {
+  if (which == 0) hipLaunchKernelGGL((hnsw_update_relink_kernel<CH>), dim3(grid), dim3(64), 0, st, a);
+  else if (which == 1) hipLaunchKernelGGL((hnsw_build_insert_kernel<CH, true>), dim3(grid), dim3(64), 0, st, a);
+  else hipLaunchKernelGGL((hnsw_build_backlink_kernel<CH, true>), dim3(grid), dim3(64), 0, st, a);
+}
+void launch_update_any(int chunks, const BuildArgs &a, hipStream_t st, int which, unsigned grid) {
+  switch (chunks) {
+    case 1: return launch_update_round<1>(a, st, which, grid);
+    case 2: return launch_update_round<2>(a, st, which, grid);
+    case 3: return launch_update_round<3>(a, st, which, grid);
+    case 4: return launch_update_round<4>(a, st, which, grid);
+    case 5: return launch_update_round<5>(a, st, which, grid);
+    case 6: return launch_update_round<6>(a, st, which, grid);
+    case 7: return launch_update_round<7>(a, st, which, grid);
+    default: return launch_update_round<8>(a, st, which, grid);
+  }
 }
 
 template <int CH>
 void launch_build_round(const BuildArgs &a_ins, const BuildArgs &a_link, hipStream_t st, int which) {
-  if (which == 0) hipLaunchKernelGGL((hnsw_build_insert_kernel<CH>), dim3(a_ins.count), dim3(64), 0, st, a_ins);
-  else hipLaunchKernelGGL((hnsw_build_backlink_kernel<CH>), dim3(a_link.n_keys), dim3(64), 0, st, a_link);
+  if (which == 0) hipLaunchKernelGGL((hnsw_build_insert_kernel<CH, false>), dim3(a_ins.count), dim3(64), 0, st, a_ins);
+  else hipLaunchKernelGGL((hnsw_build_backlink_kernel<CH, false>), dim3(a_link.n_keys), dim3(64), 0, st, a_link);
 }
 void launch_build_any(int chunks, const BuildArgs &a_ins, const BuildArgs &a_link, hipStream_t st, int which) {
   switch (chunks) {
@@ -1025,6 +1334,11 @@ struct hnsw_index {
   bool bv_clean = false;        // b_visited is all zeros (what a walk with an undo log needs at its start)
   Buf key_table, key_next, key_in, key_batch, key_tmp, key_bad;  // sorted keys of the index (built at the first append)
   int64_t key_n = -1;           // entries of key_table; -1 = not built yet
+  // ---- hnsw_index_update ----
+  Buf kp_keys, kp_pos, kp_q, kp_out;  // (key, position) sorted by key, built when an update finds n != kp_n
+  int64_t kp_n = -1;
+  Buf u_pos, u_fmask, u_top, u_pair_off, u_prop_off, u_props, u_pkeys, u_psorted, u_own, u_rows;
+  int64_t upd_rounds = 0, upd_relinks = 0, upd_superseded = 0, upd_present = 0, upd_evals = 0, upd_empty = 0;  // the last update
   ~hnsw_index() {
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -1983,6 +2297,266 @@ int hnsw_index_append_levels(hnsw_index_t *ix, int64_t n, const float *vectors, 
                              const int32_t *levels, int32_t batch) try {
   if (!levels && n > 0) return fail(HNSW_EINVAL, "levels is NULL");
   return append_impl(ix, n, vectors, ids, ef_construction, 0, levels, batch);
+} ABI_CATCH
+
+// ---- hnsw_index_update -------------------------------------------------------------------------------------------------
+// Hnsw.update (Hnsw.scala:161-181): keys already in the index are re-inserted (HnswIndex.reInsert, :226-329) in rounds on the
+// device, absent ones appended afterwards by append_impl.  See include/hnsw_ann.h for the semantics.
+
+// positions of the requested keys of a keyed index (-1: absent), by the device's (key, position) table
+static int update_positions(hnsw_index *ix, int64_t n, const int64_t *ids, std::vector<int64_t> &pos) {
+  const int64_t n_old = ix->n;
+  pos.assign((size_t)n, -1);
+  if (n_old == 0 || !ix->has_ids) return HNSW_OK;
+  if (ix->kp_n != n_old) {  // (re)built after the first update and after an append
+    ix->kp_n = -1;
+    size_t tb = 0;
+    HTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const int64_t *)nullptr,
+                                            (int64_t *)nullptr, (int)n_old, 0, 64, (hipStream_t)0));
+    Buf tmp, iota;  // (the sort's scratch and the positions it permutes live only for the sort)
+    HTRY(tmp.reserve(tb));
+    HTRY(iota.reserve((size_t)n_old * 8));
+    HTRY(ix->kp_keys.reserve((size_t)n_old * 8));
+    HTRY(ix->kp_pos.reserve((size_t)n_old * 8));
+    hipLaunchKernelGGL(hnsw_iota_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, 0, iota.as<int64_t>(), n_old);
+    HTRY(hipGetLastError());
+    HTRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, ix->ids.as<int64_t>(), ix->kp_keys.as<int64_t>(), iota.as<int64_t>(),
+                                            ix->kp_pos.as<int64_t>(), (int)n_old, 0, 64, (hipStream_t)0));
+    HTRY(hipDeviceSynchronize());  // (before tmp and iota are freed)
+    ix->kp_n = n_old;
+  }
+  HTRY(ix->kp_q.reserve((size_t)n * 8));
+  HTRY(ix->kp_out.reserve((size_t)n * 8));
+  HTRY(hipMemcpy(ix->kp_q.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(hnsw_key_lookup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ix->kp_keys.as<int64_t>(),
+                     ix->kp_pos.as<int64_t>(), n_old, ix->kp_q.as<int64_t>(), n, ix->kp_out.as<int64_t>());
+  HTRY(hipGetLastError());
+  HTRY(hipMemcpy(pos.data(), ix->kp_out.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return HNSW_OK;
+}
+
+// the rounds over the present rows: their positions in request order and their rows as given (fp32 [np][d], prepared on the device)
+static int update_rounds(hnsw_index *ix, const std::vector<uint32_t> &P, const std::vector<float> &rows, int32_t efc, int32_t batch) {
+  const int64_t np = (int64_t)P.size(), B = batch == 0 ? 4096 : batch;  // (tools/hnsw_update_probe.py: 4096 beats 1024 and 256)
+  const bool graph_on = ix->entry >= 0;  // (an empty graph: HnswIndex.reInsert's checkState(entryPoint.isPresent); rows alone)
+  // ---- host: per item, the layers it has storage for (capped at maxLevel) and the keys the host holds ----
+  std::vector<uint64_t> fmask((size_t)np, 0);
+  std::vector<int64_t> pair_off((size_t)np + 1, 0), prop_off((size_t)np + 1, 0);
+  for (int64_t t = 0; t < np; ++t) {
+    const uint32_t p = P[(size_t)t];
+    const int32_t sl = ix->upper_slot_h[p];
+    const int stor = sl < 0 ? 0 : ix->upper_base_h[(size_t)sl + 1] - ix->upper_base_h[(size_t)sl];
+    uint64_t fm = ix->has0[p] ? 1ull : 0ull;
+    for (int l = 1; l <= stor && sl >= 0; ++l)
+      if (ix->has_upper[(size_t)sl][(size_t)l - 1]) fm |= 1ull << l;
+    fmask[(size_t)t] = fm;
+    const int stop = std::min(stor, ix->max_level);
+    pair_off[(size_t)t + 1] = pair_off[(size_t)t] + (int64_t)(stop + 1) * ix->m;
+    prop_off[(size_t)t + 1] = prop_off[(size_t)t] + (int64_t)(stop + 1) * ix->m0;
+  }
+  int64_t max_keys = 1, max_props = 1, max_items = 0, n_rounds = 0;
+  for (int64_t r0 = 0; r0 < np; r0 += B) {
+    const int64_t r1 = std::min(np, r0 + B);
+    max_keys = std::max(max_keys, pair_off[(size_t)r1] - pair_off[(size_t)r0]);
+    max_props = std::max(max_props, prop_off[(size_t)r1] - prop_off[(size_t)r0]);
+    max_items = std::max(max_items, r1 - r0);
+    n_rounds++;
+  }
+  if (max_props >= (int64_t)1 << 27) return fail(HNSW_EINVAL, "batch * max_m too large");
+  // ---- scratch (a failed allocation leaves the index as it was) ----
+  const int64_t cap = std::max(ix->cap, ix->n);
+  const int64_t vwords = ((cap + 31) / 32 + 255) / 256 * 256;
+  const bool use_vlog = vwords >= VLOG_MIN_VWORDS || getenv("HNSW_DEBUG_VLOG") != nullptr;  // (as in the builder)
+  HTRY(ix->u_pos.reserve((size_t)np * 4));
+  HTRY(ix->u_fmask.reserve((size_t)np * 8));
+  HTRY(ix->u_top.reserve((size_t)np * 4));
+  HTRY(ix->u_pair_off.reserve(((size_t)np + 1) * 8));
+  HTRY(ix->u_prop_off.reserve(((size_t)np + 1) * 8));
+  HTRY(ix->u_props.reserve((size_t)max_props * (ix->m0 + 1) * 4));
+  HTRY(ix->u_pkeys.reserve((size_t)max_props * 8));
+  HTRY(ix->u_psorted.reserve((size_t)max_props * 8));
+  HTRY(ix->u_own.reserve((size_t)(max_keys / ix->m + 1) * (ix->m + 1) * 4));
+  HTRY(ix->u_rows.reserve((size_t)np * ix->d * 4));
+  HTRY(ix->b_keys.reserve((size_t)max_keys * 8));
+  HTRY(ix->b_sorted.reserve((size_t)max_keys * 8));
+  HTRY(ix->b_bstats.reserve(8 * 8));
+  size_t tb_keys = 0, tb_props = 0;
+  HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb_keys, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)max_keys, 0, 64, (hipStream_t)0));
+  HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb_props, ix->u_pkeys.as<uint64_t>(), ix->u_psorted.as<uint64_t>(), (int)max_props, 0, 64, (hipStream_t)0));
+  HTRY(ix->b_tmp.reserve(std::max(tb_keys, tb_props)));
+  if (graph_on && (vwords != ix->bv_vwords || max_items > ix->bv_items)) {  // a new bitmap layout (as append_impl)
+    const int64_t items = std::max(max_items, vwords == ix->bv_vwords ? std::min<int64_t>(2 * ix->bv_items, B) : 0);
+    ix->bv_items = ix->bv_vwords = 0;
+    ix->bv_clean = false;
+    HTRY(ix->b_visited.reserve((size_t)items * vwords * 4));
+    ix->bv_items = items;
+    ix->bv_vwords = vwords;
+  }
+  if (graph_on && use_vlog) HTRY(ix->b_vlog.reserve((size_t)ix->bv_items * VLOG_CAP * 4));
+
+  // ---- from here on the index changes: a device error leaves it broken ----
+  ix->broken = true;
+  HTRY(hipMemcpy(ix->u_rows.p, rows.data(), (size_t)np * ix->d * 4, hipMemcpyHostToDevice));
+  HTRY(hipMemcpy(ix->u_pos.p, P.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+  HTRY(hipMemcpy(ix->u_fmask.p, fmask.data(), (size_t)np * 8, hipMemcpyHostToDevice));
+  HTRY(hipMemcpy(ix->u_pair_off.p, pair_off.data(), ((size_t)np + 1) * 8, hipMemcpyHostToDevice));
+  HTRY(hipMemcpy(ix->u_prop_off.p, prop_off.data(), ((size_t)np + 1) * 8, hipMemcpyHostToDevice));
+  HTRY(hipMemsetAsync(ix->b_bstats.p, 0, 8 * 8, 0));
+  if (graph_on && use_vlog && !ix->bv_clean) HTRY(hipMemsetAsync(ix->b_visited.p, 0, (size_t)ix->bv_items * vwords * 4, 0));
+  if (graph_on) ix->bv_clean = use_vlog;
+  BuildArgs a{};
+  a.x = ix->x.as<_Float16>();
+  a.adj0 = ix->adj0.as<uint32_t>();
+  a.upper_slot = ix->upper_slot.as<int32_t>();
+  a.upper_base = ix->upper_base.as<int32_t>();
+  a.upper_adj = ix->upper_adj.as<uint32_t>();
+  a.order = ix->u_pos.as<uint32_t>();
+  a.levels = nullptr;
+  a.pair_off = ix->u_pair_off.as<int64_t>();
+  a.visited = ix->b_visited.as<uint32_t>();
+  a.vlog = use_vlog ? ix->b_vlog.as<uint32_t>() : nullptr;
+  a.bstats = ix->b_bstats.as<unsigned long long>();
+  a.vwords = vwords;
+  a.dpad = ix->dpad;
+  a.metric = ix->metric;
+  a.m = ix->m;
+  a.m0 = ix->m0;
+  a.efc = efc;
+  a.ccap = BUILD_CCAP;
+  if (const char *e = std::getenv("HNSW_BUILD_CCAP")) a.ccap = std::max(2, std::min(BUILD_CCAP, std::atoi(e)));
+  a.entry = (uint32_t)std::max<int64_t>(ix->entry, 0);  // an update never moves the entry point or maxLevel
+  a.max_level = ix->max_level;
+  a.utop = ix->u_top.as<int32_t>();
+  a.fmask = ix->u_fmask.as<uint64_t>();
+  a.prop_off = ix->u_prop_off.as<int64_t>();
+  a.props = ix->u_props.as<uint32_t>();
+  a.own = ix->u_own.as<uint32_t>();
+  const int chunks = ix->dpad / 64;
+  for (int64_t r0 = 0; r0 < np; r0 += B) {
+    const int64_t r1 = std::min(np, r0 + B), m = r1 - r0;
+    a.at = (uint32_t)r0;
+    a.count = (uint32_t)m;
+    // 1. the round's rows
+    hipLaunchKernelGGL(hnsw_update_rows_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, ix->u_rows.as<float>() + r0 * ix->d, m,
+                       ix->u_pos.as<uint32_t>() + r0, ix->d, ix->dpad, ix->metric == HNSW_METRIC_COSINE ? 1 : 0, ix->x.as<_Float16>());
+    HTRY(hipGetLastError());
+    if (!graph_on) continue;
+    const int64_t n_pk = prop_off[(size_t)r1] - prop_off[(size_t)r0], n_k = pair_off[(size_t)r1] - pair_off[(size_t)r0];
+    // 2. relink: every proposal against the graph as the round found it, then the latest per (layer, v)
+    HTRY(hipMemsetAsync(ix->u_pkeys.p, 0xff, (size_t)n_pk * 8, 0));
+    BuildArgs ar = a;
+    ar.pkeys = ix->u_pkeys.as<uint64_t>();
+    launch_update_any(chunks, ar, 0, 0, (unsigned)m);
+    size_t tb = tb_props;
+    HTRY(hipcub::DeviceRadixSort::SortKeys(ix->b_tmp.p, tb, ix->u_pkeys.as<uint64_t>(), ix->u_psorted.as<uint64_t>(), (int)n_pk, 0, 64, (hipStream_t)0));
+    BuildArgs ac = a;
+    ac.pkeys = ix->u_psorted.as<uint64_t>();
+    ac.n_pkeys = (uint32_t)n_pk;
+    hipLaunchKernelGGL(hnsw_update_relink_commit_kernel, dim3((unsigned)((n_pk + 255) / 256)), dim3(256), 0, 0, ac);
+    // 3. wire: the walks, then the items' own lists
+    HTRY(hipMemsetAsync(ix->b_keys.p, 0xff, (size_t)n_k * 8, 0));
+    BuildArgs aw = a;
+    aw.keys = ix->b_keys.as<uint64_t>();
+    launch_update_any(chunks, aw, 0, 1, (unsigned)m);
+    hipLaunchKernelGGL(hnsw_update_own_commit_kernel, dim3((unsigned)m), dim3(64), 0, 0, aw);
+    // 4. back links
+    tb = tb_keys;
+    HTRY(hipcub::DeviceRadixSort::SortKeys(ix->b_tmp.p, tb, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)n_k, 0, 64, (hipStream_t)0));
+    BuildArgs al = a;
+    al.keys = ix->b_sorted.as<uint64_t>();
+    al.n_keys = (uint32_t)n_k;
+    launch_update_any(chunks, al, 0, 2, (unsigned)n_k);
+    HTRY(hipGetLastError());
+  }
+  HTRY(hipDeviceSynchronize());
+  unsigned long long bs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HTRY(hipMemcpy(bs, ix->b_bstats.p, sizeof(bs), hipMemcpyDeviceToHost));
+  ix->broken = false;
+  ix->host_stale = true;
+  ix->upd_rounds = n_rounds;
+  ix->upd_empty = (int64_t)bs[3];
+  ix->upd_relinks = (int64_t)bs[4];
+  ix->upd_superseded = (int64_t)bs[5];
+  ix->upd_present = (int64_t)bs[6];
+  ix->upd_evals = (int64_t)bs[7];
+  return HNSW_OK;
+}
+
+static int update_impl(hnsw_index *ix, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction, uint64_t seed,
+                       int32_t batch, int64_t *out_appended) {
+  if (out_appended) *out_appended = 0;
+  // ---- everything that can be refused is refused before anything changes ----
+  if (!ix) return fail(HNSW_EINVAL, "NULL index");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
+  if (n < 0) return fail(HNSW_EINVAL, "n must not be negative");
+  if (ef_construction < 1 || ef_construction > BUILD_EF_MAX) return fail(HNSW_EINVAL, "ef_construction must be in 1..256");
+  if (batch < 0 || batch > (1 << 20)) return fail(HNSW_EINVAL, "batch must be in 0..2^20");
+  if (n == 0) return HNSW_OK;
+  if (!vectors || !ids) return fail(HNSW_EINVAL, "NULL vectors or ids");
+  {
+    std::vector<int64_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int64_t i = 1; i < n; ++i)
+      if (sorted[(size_t)i] == sorted[(size_t)i - 1])
+        return fail(HNSW_EINVAL, "key " + std::to_string(sorted[(size_t)i]) + " appears twice in the update");
+  }
+  const int64_t n_old = ix->n;
+  HTRY(hipSetDevice(ix->device));
+  std::vector<int64_t> pos;
+  if (ix->keyed) {
+    const int rc = update_positions(ix, n, ids, pos);
+    if (rc) return rc;
+  } else {
+    for (int64_t i = 0; i < n; ++i)
+      if (ids[i] < 0 || ids[i] >= n_old)
+        return fail(HNSW_EINVAL, "position " + std::to_string(ids[i]) + " is not in the index (its keys are positions 0.." +
+                                     std::to_string(n_old - 1) + ")");
+    pos.assign(ids, ids + n);
+  }
+  std::vector<uint32_t> P;
+  std::vector<float> rows, arows;
+  std::vector<int64_t> akeys;
+  for (int64_t i = 0; i < n; ++i) {
+    const float *v = vectors + (size_t)i * ix->d;
+    if (pos[(size_t)i] >= 0) {
+      P.push_back((uint32_t)pos[(size_t)i]);
+      rows.insert(rows.end(), v, v + ix->d);
+    } else {
+      akeys.push_back(ids[i]);
+      arows.insert(arows.end(), v, v + ix->d);
+    }
+  }
+  if (n_old + (int64_t)akeys.size() >= (int64_t)0x7fffffff) return fail(HNSW_EINVAL, "the index would reach 2^31 - 1 rows");
+  ix->upd_rounds = ix->upd_relinks = ix->upd_superseded = ix->upd_present = ix->upd_evals = ix->upd_empty = 0;
+  if (!P.empty()) {
+    const int rc = update_rounds(ix, P, rows, ef_construction, batch);
+    if (rc) return rc;
+  }
+  if (!akeys.empty()) {  // Hnsw.update of a new key: insert (Hnsw.scala:172-173), by the append path, in request order
+    const int rc = append_impl(ix, (int64_t)akeys.size(), arows.data(), akeys.data(), ef_construction, seed, nullptr, batch);
+    if (rc && !P.empty())  // (everything refusable was refused above: this is the append running out of room, or the device)
+      return fail(rc, std::string("the present keys were updated, the absent ones not appended: ") + hnsw_last_error());
+    if (rc) return rc;
+    if (out_appended) *out_appended = (int64_t)akeys.size();
+  }
+  return HNSW_OK;
+}
+
+int hnsw_index_update(hnsw_index_t *ix, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction, uint64_t seed,
+                      int32_t batch, int64_t *out_appended) try {
+  return update_impl(ix, n, vectors, ids, ef_construction, seed, batch, out_appended);
+} ABI_CATCH
+
+int hnsw_index_update_stats(const hnsw_index_t *ix, int64_t *rounds, int64_t *relinks, int64_t *relinks_superseded,
+                            int64_t *additions_already_present, int64_t *distance_evals, int64_t *lists_kept) try {
+  if (!ix) return fail(HNSW_EINVAL, "NULL index");
+  if (rounds) *rounds = ix->upd_rounds;
+  if (relinks) *relinks = ix->upd_relinks;
+  if (relinks_superseded) *relinks_superseded = ix->upd_superseded;
+  if (additions_already_present) *additions_already_present = ix->upd_present;
+  if (distance_evals) *distance_evals = ix->upd_evals;
+  if (lists_kept) *lists_kept = ix->upd_empty;
+  return HNSW_OK;
 } ABI_CATCH
 
 int hnsw_index_reserve(hnsw_index_t *ix, int64_t capacity) try {

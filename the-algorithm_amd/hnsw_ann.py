@@ -31,6 +31,9 @@ PROTOS = {
                                                      C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "hnsw_index_append": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32]),
     "hnsw_index_append_levels": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "hnsw_index_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32,
+                                    C.POINTER(C.c_int64)]),
+    "hnsw_index_update_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 6),
     "hnsw_index_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
     "hnsw_index_build_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hnsw_index_graph_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
@@ -151,6 +154,33 @@ class Hnsw:
         n = C.c_int64()
         _check(lib, lib.hnsw_index_info(self._h, C.byref(n), None, None, None))
         self.n = n.value
+
+    def update(self, vectors: np.ndarray, ids: Sequence[int], *, ef_construction: int = 200, seed: int = 1, batch: int = 0) -> int:
+        """Hnsw.update for every row of `vectors` (hnsw_index_update): a key already in the index gets the new embedding and is
+        re-inserted (HnswIndex.reInsert) on the device, `batch` rows per round (0 = 4096); absent keys are then appended as by
+        append(ef_construction, seed, batch).  ids are keys, or positions on an index created without ids (no upsert there).
+        A key repeated in the call, or a position out of range, raises HnswError and leaves the index unchanged.  Returns the
+        number of rows appended.  One caller at a time."""
+        lib = _lib()
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.d:
+            raise ValueError(f"vectors must be [n][{self.d}], got shape {v.shape}")
+        i = np.ascontiguousarray(ids, np.int64)
+        if i.shape != (v.shape[0],):
+            raise ValueError("ids must hold one key per vector")
+        appended = C.c_int64()
+        _check(lib, lib.hnsw_index_update(self._h, v.shape[0], _p(v), _p(i), ef_construction, seed, batch, C.byref(appended)))
+        n = C.c_int64()
+        _check(lib, lib.hnsw_index_info(self._h, C.byref(n), None, None, None))
+        self.n = n.value
+        return appended.value
+
+    def update_stats(self):
+        """Counters of the last update: rounds, relinks, relinks_superseded, additions_already_present, distance_evals, lists_kept."""
+        v = [C.c_int64() for _ in range(6)]
+        _check(_lib(), _lib().hnsw_index_update_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("rounds", "relinks", "relinks_superseded", "additions_already_present", "distance_evals", "lists_kept"),
+                        (x.value for x in v)))
 
     def reserve(self, capacity: int) -> None:
         """Room for `capacity` rows without reallocating (hnsw_index_reserve); never shrinks."""

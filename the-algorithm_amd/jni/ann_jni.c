@@ -165,6 +165,31 @@ JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_hnswIndexAppend(JNIEnv *e
                         (uint64_t)seed, 0) != HNSW_OK)
     throw_runtime(env, hnsw_last_error());
 }
+/* void hnswIndexUpdate(long index, long n, int d, ByteBuffer vectors /+ float[n][d] +/, ByteBuffer ids /+ long[n] +/,
+ *                      int efConstruction, long seed)
+ * Hnsw.update / SerializableHnsw.update for n rows on the device (hnsw_index_update, 4096 rows per round): a key already in the
+ * index is re-inserted with its new embedding, an absent key inserted; ids are positions on an index created without ids.  One
+ * writer at a time per index (Hnsw.update takes readWriteFuturePool.write) */
+JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_hnswIndexUpdate(JNIEnv *env, jclass cls, jlong index, jlong n, jint d, jobject vectors,
+                                                                       jobject ids, jint efConstruction, jlong seed) {
+  (void)cls;
+  if (n < 0 || d < 1 || (n > 0 && (!vectors || CAP(vectors) / 4 / d < n || !ids || CAP(ids) / 8 < n))) {
+    throw_runtime(env, "vectors must hold n x d floats and ids n longs");
+    return;
+  }
+  if (!index) {
+    throw_runtime(env, "null index");
+    return;
+  }
+  int32_t dim = 0;
+  if (hnsw_index_info((const hnsw_index_t *)(intptr_t)index, NULL, &dim, NULL, NULL) != HNSW_OK || dim != d) {
+    throw_runtime(env, "d is not the index's dimension");
+    return;
+  }
+  if (hnsw_index_update((hnsw_index_t *)(intptr_t)index, n, (const float *)BUF(vectors), (const int64_t *)BUF(ids), efConstruction,
+                        (uint64_t)seed, 0, NULL) != HNSW_OK)
+    throw_runtime(env, hnsw_last_error());
+}
 /* void hnswSearch(long index, int nq, int d, ByteBuffer x, int k, int ef, ByteBuffer distances, ByteBuffer labels, ByteBuffer counts)
  * = Hnsw.queryWithDistance for nq queries (HnswParams.ef; Hnsw.scala:125-147) */
 JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_hnswSearch(JNIEnv *env, jclass cls, jlong index, jint nq, jint d, jobject x, jint k, jint ef,

@@ -45,6 +45,13 @@ public final class AnnJni {
   public static native void hnswIndexAppend(long index, long n, int d, ByteBuffer vectors, ByteBuffer ids, int efConstruction, long seed);
 
   /**
+   * Hnsw.update / SerializableHnsw.update for n rows, on the device: vectors float[n][d] (d = the index's); ids long[n], keys (a
+   * key already present is re-inserted with its new embedding, HnswIndex.reInsert; an absent one inserted), or positions when the
+   * index was created without ids. One writer at a time (Hnsw.update holds readWriteFuturePool.write).
+   */
+  public static native void hnswIndexUpdate(long index, long n, int d, ByteBuffer vectors, ByteBuffer ids, int efConstruction, long seed);
+
+  /**
    * ComposedQueryable.queryWithDistance (ShardApi.scala:71-87) over the batched answers of one index per GPU: ids long[nShards][nq][kIn],
    * distances float[nShards][nq][kIn], counts int[nShards][nq] in; the k nearest per query, by (distance, id), out.
    */
