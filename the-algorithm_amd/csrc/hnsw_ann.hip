@@ -38,6 +38,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hnsw_ann.h"
@@ -71,12 +72,15 @@ constexpr int VLOG_CAP = 1 << 16;       // visited nodes a walk remembers for cl
 struct Buf {
   void *p = nullptr;
   size_t bytes = 0;
-  ~Buf() { if (p) (void)hipFree(p); }
-  hipError_t reserve(size_t n) {
-    if (n <= bytes && p) return hipSuccess;
+  ~Buf() { release(); }
+  void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
     bytes = 0;
+  }
+  hipError_t reserve(size_t n) {
+    if (n <= bytes && p) return hipSuccess;
+    release();
     hipError_t e = hipMalloc(&p, n ? n : 8);
     if (e == hipSuccess) bytes = n ? n : 8;
     return e;
@@ -1171,41 +1175,30 @@ __global__ void hnsw_iota_kernel(int64_t *__restrict__ out, int64_t n) {
   if (i < n) out[i] = i;
 }
 
-template <int CH>
-void launch_update_round(const BuildArgs &a, hipStream_t st, int which, unsigned grid) {
-  if (which == 0) hipLaunchKernelGGL((hnsw_update_relink_kernel<CH>), dim3(grid), dim3(64), 0, st, a);
-  else if (which == 1) hipLaunchKernelGGL((hnsw_build_insert_kernel<CH, true>), dim3(grid), dim3(64), 0, st, a);
-  else hipLaunchKernelGGL((hnsw_build_backlink_kernel<CH, true>), dim3(grid), dim3(64), 0, st, a);
-}
-void launch_update_any(int chunks, const BuildArgs &a, hipStream_t st, int which, unsigned grid) {
-  switch (chunks) {
-    case 1: return launch_update_round<1>(a, st, which, grid);
-    case 2: return launch_update_round<2>(a, st, which, grid);
-    case 3: return launch_update_round<3>(a, st, which, grid);
-    case 4: return launch_update_round<4>(a, st, which, grid);
-    case 5: return launch_update_round<5>(a, st, which, grid);
-    case 6: return launch_update_round<6>(a, st, which, grid);
-    case 7: return launch_update_round<7>(a, st, which, grid);
-    default: return launch_update_round<8>(a, st, which, grid);
-  }
+// The kernels are compiled for rows of CH = 1..8 blocks of 64 elements (dpad = 64 * CH, MAX_D = 512): calls f with CH as a
+// std::integral_constant, so that f names the instantiation
+template <int CH = 1, class F>
+void for_chunks(int chunks, F &&f) {
+  if constexpr (CH == 8) f(std::integral_constant<int, 8>());
+  else if (chunks == CH) f(std::integral_constant<int, CH>());
+  else for_chunks<CH + 1>(chunks, f);
 }
 
-template <int CH>
-void launch_build_round(const BuildArgs &a_ins, const BuildArgs &a_link, hipStream_t st, int which) {
-  if (which == 0) hipLaunchKernelGGL((hnsw_build_insert_kernel<CH, false>), dim3(a_ins.count), dim3(64), 0, st, a_ins);
-  else hipLaunchKernelGGL((hnsw_build_backlink_kernel<CH, false>), dim3(a_link.n_keys), dim3(64), 0, st, a_link);
+void launch_update_any(int chunks, const BuildArgs &a, hipStream_t st, int which, unsigned grid) {
+  for_chunks(chunks, [&](auto ch) {
+    constexpr int CH = decltype(ch)::value;
+    if (which == 0) hipLaunchKernelGGL((hnsw_update_relink_kernel<CH>), dim3(grid), dim3(64), 0, st, a);
+    else if (which == 1) hipLaunchKernelGGL((hnsw_build_insert_kernel<CH, true>), dim3(grid), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((hnsw_build_backlink_kernel<CH, true>), dim3(grid), dim3(64), 0, st, a);
+  });
 }
+
 void launch_build_any(int chunks, const BuildArgs &a_ins, const BuildArgs &a_link, hipStream_t st, int which) {
-  switch (chunks) {
-    case 1: return launch_build_round<1>(a_ins, a_link, st, which);
-    case 2: return launch_build_round<2>(a_ins, a_link, st, which);
-    case 3: return launch_build_round<3>(a_ins, a_link, st, which);
-    case 4: return launch_build_round<4>(a_ins, a_link, st, which);
-    case 5: return launch_build_round<5>(a_ins, a_link, st, which);
-    case 6: return launch_build_round<6>(a_ins, a_link, st, which);
-    case 7: return launch_build_round<7>(a_ins, a_link, st, which);
-    default: return launch_build_round<8>(a_ins, a_link, st, which);
-  }
+  for_chunks(chunks, [&](auto ch) {
+    constexpr int CH = decltype(ch)::value;
+    if (which == 0) hipLaunchKernelGGL((hnsw_build_insert_kernel<CH, false>), dim3(a_ins.count), dim3(64), 0, st, a_ins);
+    else hipLaunchKernelGGL((hnsw_build_backlink_kernel<CH, false>), dim3(a_link.n_keys), dim3(64), 0, st, a_link);
+  });
 }
 
 // rows (fp32) -> fp16 rows padded to dpad; Cosine rows are normalised first (Hnsw.scala:149-155)
@@ -1320,17 +1313,18 @@ struct hnsw_index {
   int32_t last_spilled = 0;
   int64_t last_peak = 0, last_adm = 0;
   float last_ms = 0;
-  int64_t build_rounds = 0, build_truncated = 0, build_prunes = 0, build_dropped = 0;  // hnsw_index_build_insert_gpu / _append
+  int64_t build_rounds = 0, build_truncated = 0, build_prunes = 0, build_dropped = 0;  // the last insert_rows (device build, append)
   int64_t search_vwords = 0;  // bitmap layout of the last search: a different one is a fresh layout (visited_dirty)
-  // ---- hnsw_index_append: room, host-mirror state, and construction scratch kept across calls ----
+  // ---- insert_rows (device build, append): room, host-mirror state, and construction scratch kept across calls ----
   int64_t cap = 0;              // rows the per-row buffers (x, adj0, upper_slot, ids, levels) hold; 0 = n
   int64_t upper_rows_cap = 0, upper_slots_cap = 0;
   bool keyed = false;           // created with ids (has_ids may be false only because n was 0)
   bool broken = false;          // a device error part-way through an append: every later call fails with HNSW_EDEVICE
   mutable bool host_stale = false;  // level0 / upper / has0 / has_upper behind the device graph (refreshed by an export)
-  Buf levels;                   // [cap] levels of appended rows (read by the insert kernel by position)
+  Buf levels;                   // [cap] levels of inserted rows (read by the insert kernel by position)
   Buf b_order, b_pair_off, b_keys, b_sorted, b_tmp, b_bstats, b_visited, b_vlog;
-  int64_t bv_items = 0, bv_vwords = 0;
+  int64_t bv_items = 0, bv_vwords = 0;  // layout of b_visited: walks at a time, words per walk (reserve_visited)
+  bool bv_log = false;          // the walks keep an undo log in b_vlog
   bool bv_clean = false;        // b_visited is all zeros (what a walk with an undo log needs at its start)
   Buf key_table, key_next, key_in, key_batch, key_tmp, key_bad;  // sorted keys of the index (built at the first append)
   int64_t key_n = -1;           // entries of key_table; -1 = not built yet
@@ -1631,8 +1625,23 @@ int upload_graph(hnsw_index *ix, const HostGraph &g) {
   return HNSW_OK;
 }
 
-int create_index(int32_t device, int32_t metric, int64_t n, int32_t d, const float *vectors, const int64_t *ids, int32_t max_m,
-                 std::unique_ptr<hnsw_index> &ix, std::vector<float> *host_rows) {
+// fp32 rows from the host into x from row `at` on, through hnsw_prep_rows, in chunks of 128 MB staged in `stage`
+int stage_rows(hnsw_index *ix, Buf &stage, const float *vectors, int64_t n, int64_t at) {
+  const int64_t chunk = std::max<int64_t>(1, (int64_t)(128u << 20) / ((int64_t)ix->d * 4));
+  HTRY(stage.reserve((size_t)std::min(chunk, n) * ix->d * 4));
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t m = std::min(chunk, n - r0);
+    HTRY(hipMemcpy(stage.p, vectors + r0 * ix->d, (size_t)m * ix->d * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(hnsw_prep_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, stage.as<float>(), m, ix->d, ix->dpad,
+                       ix->metric == HNSW_METRIC_COSINE ? 1 : 0, ix->x.as<_Float16>() + (at + r0) * ix->dpad);
+    HTRY(hipGetLastError());
+    if (r0 + chunk < n) HTRY(hipDeviceSynchronize());  // (the next chunk overwrites the staging buffer)
+  }
+  return HNSW_OK;
+}
+
+// the checks every way of making an index shares, and a handle that holds no rows yet
+int new_index(int32_t device, int32_t metric, int64_t n, int32_t d, const float *vectors, int32_t max_m, std::unique_ptr<hnsw_index> &ix) {
   if (metric < HNSW_METRIC_L2 || metric > HNSW_METRIC_INNER_PRODUCT) return fail(HNSW_EINVAL, "unknown metric");
   if (n < 0 || n >= (int64_t)0x7fffffff) return fail(HNSW_EINVAL, "vector count out of range");
   if (d < 1 || d > MAX_D) return fail(HNSW_EINVAL, "dimension must be in 1..512");
@@ -1641,26 +1650,25 @@ int create_index(int32_t device, int32_t metric, int64_t n, int32_t d, const flo
   ix.reset(new hnsw_index);
   ix->device = device;
   ix->metric = metric;
-  ix->n = n;
   ix->d = d;
   ix->dpad = (d + 63) / 64 * 64;
   ix->m = max_m;
   ix->m0 = 2 * max_m;
   HTRY(hipSetDevice(device));
   for (auto &e : ix->ev) HTRY(hipEventCreate(&e));
+  return HNSW_OK;
+}
+
+// a handle with its rows and ids on the device and no graph yet (upload_graph brings one)
+int create_index(int32_t device, int32_t metric, int64_t n, int32_t d, const float *vectors, const int64_t *ids, int32_t max_m,
+                 std::unique_ptr<hnsw_index> &ix, std::vector<float> *host_rows) {
+  if (int rc = new_index(device, metric, n, d, vectors, max_m, ix)) return rc;
+  ix->n = n;
   HTRY(ix->x.reserve((size_t)std::max<int64_t>(n, 1) * ix->dpad * sizeof(_Float16)));
   if (n > 0) {
     Buf stage;
-    const int64_t chunk = std::max<int64_t>(1, (int64_t)(128u << 20) / ((int64_t)d * 4));
-    HTRY(stage.reserve((size_t)std::min(chunk, n) * d * 4));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-      const int64_t m = std::min(chunk, n - r0);
-      HTRY(hipMemcpy(stage.p, vectors + r0 * d, (size_t)m * d * 4, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(hnsw_prep_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, stage.as<float>(), m, d, ix->dpad,
-                         metric == HNSW_METRIC_COSINE ? 1 : 0, ix->x.as<_Float16>() + r0 * ix->dpad);
-      HTRY(hipGetLastError());
-      HTRY(hipDeviceSynchronize());
-    }
+    if (int rc = stage_rows(ix.get(), stage, vectors, n, 0)) return rc;
+    HTRY(hipDeviceSynchronize());  // (before the staging buffer is freed)
   }
   if (ids && n > 0) {
     HTRY(ix->ids.reserve((size_t)n * 8));
@@ -1677,23 +1685,107 @@ int create_index(int32_t device, int32_t metric, int64_t n, int32_t d, const flo
   return HNSW_OK;
 }
 
-template <int CH>
-int launch_search(int blocks, const SearchArgs &a, hipStream_t st) {
-  const size_t lds = (size_t)(a.ef + 1 + a.ccap_lds) * sizeof(HEntry);
-  hipLaunchKernelGGL((hnsw_search_kernel<CH>), dim3(blocks), dim3(64), lds, st, a);
+// levels of the rows at positions first .. first + n - 1: the given ones (each in 0..60), or getRandomLevel
+// (HnswIndex.java:369-371) drawn from the seed and the row's position in the whole index
+int draw_levels(uint64_t seed, int64_t first, int64_t n, int32_t max_m, const int32_t *given_levels, std::vector<int32_t> &out) {
+  out.assign((size_t)std::max<int64_t>(n, 0), 0);
+  const double level_mult = 1.0 / std::log(1.0 * max_m);  // HnswIndex.java:118
+  for (int64_t i = 0; i < n; ++i) {
+    if (given_levels) {
+      if (given_levels[i] < 0 || given_levels[i] > 60) return fail(HNSW_EINVAL, "a level is outside 0..60");
+      out[(size_t)i] = given_levels[i];
+      continue;
+    }
+    const uint64_t h = sann::mix64(seed ^ ((uint64_t)(first + i) * 0x9E3779B97F4A7C15ull));
+    const double u = ((double)(h >> 11) + 1.0) * (1.0 / 9007199254740992.0);  // (0, 1]
+    out[(size_t)i] = std::min(60, (int)(-std::log(u) * level_mult));
+  }
   return HNSW_OK;
 }
-int launch_search_any(int chunks, int blocks, const SearchArgs &a, hipStream_t st) {
-  switch (chunks) {
-    case 1: return launch_search<1>(blocks, a, st);
-    case 2: return launch_search<2>(blocks, a, st);
-    case 3: return launch_search<3>(blocks, a, st);
-    case 4: return launch_search<4>(blocks, a, st);
-    case 5: return launch_search<5>(blocks, a, st);
-    case 6: return launch_search<6>(blocks, a, st);
-    case 7: return launch_search<7>(blocks, a, st);
-    default: return launch_search<8>(blocks, a, st);
+
+// ef_construction and batch of a device build, an append or an update; batch 0 is the default
+// (tools/hnsw_update_probe.py: 4096 beats 1024 and 256)
+int check_construction_args(int32_t ef_construction, int32_t &batch) {
+  if (ef_construction < 1 || ef_construction > BUILD_EF_MAX) return fail(HNSW_EINVAL, "ef_construction must be in 1..256");
+  if (batch < 0 || batch > (1 << 20)) return fail(HNSW_EINVAL, "batch must be in 0..2^20");
+  if (batch == 0) batch = 4096;
+  return HNSW_OK;
+}
+
+// rows the per-row buffers must hold for `need` rows: what they hold, or amortised growth (>= 1.5x)
+int64_t grown_capacity(const hnsw_index *ix, int64_t need) {
+  const int64_t cap = std::max(ix->cap, ix->n);
+  return need > cap ? std::max(need, cap + cap / 2) : cap;
+}
+
+// the per-row buffers grown to `capacity` rows, device to device; a failed growth leaves the index as it was
+int grow_rows(hnsw_index *ix, int64_t capacity) {
+  const int64_t n = ix->n;
+  HTRY(grow_keep(ix->x, (size_t)n * ix->dpad * sizeof(_Float16), (size_t)capacity * ix->dpad * sizeof(_Float16)));
+  HTRY(grow_keep(ix->adj0, (size_t)n * (ix->m0 + 1) * 4, (size_t)capacity * (ix->m0 + 1) * 4));
+  HTRY(grow_keep(ix->upper_slot, (size_t)n * 4, (size_t)capacity * 4));
+  HTRY(grow_keep(ix->levels, 0, (size_t)capacity * 4));
+  if (ix->keyed) HTRY(grow_keep(ix->ids, (size_t)n * 8, (size_t)capacity * 8));
+  ix->cap = capacity;
+  return HNSW_OK;
+}
+
+// a round's keys (walks write them, back links read them sorted) and the radix sort's scratch, for rounds of up to `max_keys`
+int reserve_round_keys(hnsw_index *ix, int64_t max_keys, size_t &tmp_bytes) {
+  HTRY(ix->b_keys.reserve((size_t)max_keys * 8));
+  HTRY(ix->b_sorted.reserve((size_t)max_keys * 8));
+  HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)max_keys, 0, 64, (hipStream_t)0));
+  HTRY(ix->b_tmp.reserve(tmp_bytes));
+  return HNSW_OK;
+}
+
+// The visited bitmaps of construction walks, `max_items` at a time (a round; rounds have at most `batch`), over the capacity
+// of the index, and whether the walks keep an undo log (bitmaps of 1 MB and more; tests force it on small graphs by the variable
+// read below).  Walks with the log need clean bitmaps and leave them clean, so those are wiped once per layout; walks without it
+// wipe their own and leave them dirty.
+int reserve_visited(hnsw_index *ix, int64_t max_items, int64_t batch) {
+  const int64_t cap = std::max(ix->cap, ix->n), vwords = ((cap + 31) / 32 + 255) / 256 * 256;
+  ix->bv_log = vwords >= VLOG_MIN_VWORDS || getenv("HNSW_DEBUG_VLOG") != nullptr;
+  if (vwords != ix->bv_vwords || max_items > ix->bv_items) {  // a new layout
+    const int64_t items = std::max(max_items, vwords == ix->bv_vwords ? std::min<int64_t>(2 * ix->bv_items, batch) : 0);
+    ix->bv_items = ix->bv_vwords = 0;
+    ix->bv_clean = false;
+    HTRY(ix->b_visited.reserve((size_t)items * vwords * 4));
+    ix->bv_items = items;
+    ix->bv_vwords = vwords;
   }
+  if (ix->bv_log) HTRY(ix->b_vlog.reserve((size_t)ix->bv_items * VLOG_CAP * 4));
+  if (ix->bv_log && !ix->bv_clean) HTRY(hipMemsetAsync(ix->b_visited.p, 0, (size_t)ix->bv_items * vwords * 4, 0));
+  ix->bv_clean = ix->bv_log;
+  return HNSW_OK;
+}
+
+// what every construction kernel reads of the index and its scratch (after reserve_visited); the caller adds its work list
+BuildArgs build_args(const hnsw_index *ix, int32_t efc) {
+  BuildArgs a{};
+  a.x = ix->x.as<_Float16>();
+  a.adj0 = ix->adj0.as<uint32_t>();
+  a.upper_slot = ix->upper_slot.as<int32_t>();
+  a.upper_base = ix->upper_base.as<int32_t>();
+  a.upper_adj = ix->upper_adj.as<uint32_t>();
+  a.visited = ix->b_visited.as<uint32_t>();
+  a.vlog = ix->bv_log ? ix->b_vlog.as<uint32_t>() : nullptr;
+  a.bstats = ix->b_bstats.as<unsigned long long>();
+  a.vwords = ix->bv_vwords;
+  a.dpad = ix->dpad;
+  a.metric = ix->metric;
+  a.m = ix->m;
+  a.m0 = ix->m0;
+  a.efc = efc;
+  a.ccap = BUILD_CCAP;
+  if (const char *e = std::getenv("HNSW_BUILD_CCAP")) a.ccap = std::max(2, std::min(BUILD_CCAP, std::atoi(e)));  // (tests: make the prune path run)
+  return a;
+}
+
+int launch_search_any(int chunks, int blocks, const SearchArgs &a, hipStream_t st) {
+  const size_t lds = (size_t)(a.ef + 1 + a.ccap_lds) * sizeof(HEntry);
+  for_chunks(chunks, [&](auto ch) { hipLaunchKernelGGL((hnsw_search_kernel<decltype(ch)::value>), dim3(blocks), dim3(64), lds, st, a); });
+  return HNSW_OK;
 }
 
 }  // namespace
@@ -1764,8 +1856,6 @@ int hnsw_index_build_insert_levels(int32_t device, int32_t metric, int64_t n, in
                                    const int64_t *ids, int32_t max_m, int32_t ef_construction, const int32_t *levels,
                                    int32_t n_threads, hnsw_index_t **out) try {
   if (!levels && n > 0) return fail(HNSW_EINVAL, "levels is NULL");
-  for (int64_t i = 0; i < n; ++i)
-    if (levels[i] < 0 || levels[i] > 60) return fail(HNSW_EINVAL, "a level is outside 0..60");
   return build_insert_impl(device, metric, n, d, vectors, ids, max_m, ef_construction, 0, levels, n_threads, out);
 } ABI_CATCH
 
@@ -1779,17 +1869,9 @@ static int build_insert_impl(int32_t device, int32_t metric, int64_t n, int32_t 
   std::vector<float> rows;
   int rc = create_index(device, metric, n, d, vectors, ids, max_m, ix, &rows);
   if (rc) return rc;
-  const double level_mult = 1.0 / std::log(1.0 * max_m);  // HnswIndex.java:118
-  std::vector<int32_t> levels((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    if (given_levels) {
-      levels[(size_t)i] = given_levels[i];
-      continue;
-    }
-    const uint64_t h = sann::mix64(seed ^ ((uint64_t)i * 0x9E3779B97F4A7C15ull));
-    const double u = ((double)(h >> 11) + 1.0) * (1.0 / 9007199254740992.0);  // (0, 1]
-    levels[(size_t)i] = std::min(60, (int)(-std::log(u) * level_mult));       // getRandomLevel, :369-371
-  }
+  std::vector<int32_t> levels;
+  rc = draw_levels(seed, 0, n, max_m, given_levels, levels);
+  if (rc) return rc;
   HostGraph g;
   g.init(n, max_m, levels);
   HostVectors hv;
@@ -1826,152 +1908,189 @@ static int build_insert_impl(int32_t device, int32_t metric, int64_t n, int32_t 
   return HNSW_OK;
 }
 
-// Construction on the device: see the comment above hnsw_build_insert_kernel.  The host only works out the insertion
-// order and the round schedule (both functions of the levels alone) and enqueues kernels; nothing comes back before the end.
+static const char *const BROKEN = "an earlier append failed on the device part-way: the index is unusable";
+
+// ---- insertion rounds on the device ------------------------------------------------------------------------------------
+// Construction on the device: see the comment above hnsw_build_insert_kernel and include/hnsw_ann.h.  One driver serves the
+// one-shot build and the append, because a build is the rounds of an append to an empty graph.  The host works out the
+// insertion order of the new rows, the round schedule and the entry point and maxLevel of every round (functions of the
+// levels and of the rows already linked alone), grows the buffers device to device, and enqueues kernels; nothing comes back
+// before the end, and then only the round counters.  Everything that can be refused is refused before anything changes; from
+// the first change on a device error leaves the index broken.  `ids`, for a keyed index, are the new rows' keys.
+static int insert_rows(hnsw_index *ix, int64_t n, const float *vectors, const int64_t *ids, const std::vector<int32_t> &lv,
+                       int32_t ef_construction, int32_t batch) {
+  if (n == 0) return HNSW_OK;
+  const int64_t n_old = ix->n;
+  // ---- order, rounds, entry point per round (host: functions of the levels and n_old) ----
+  std::vector<uint32_t> order((size_t)n);
+  for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (uint32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return lv[x] > lv[y]; });
+  struct Round {
+    int64_t at, count, entry;
+    int max_level;
+  };
+  std::vector<Round> rounds;
+  std::vector<int64_t> pair_off((size_t)n + 1, 0);
+  std::vector<int32_t> wired_top((size_t)n, -1);  // layers each new row is wired on (-1: it became the entry of an empty graph)
+  int64_t entry = ix->entry, at = 0, linked = n_old, max_keys = 0, max_items = 0;
+  int max_level = ix->max_level;
+  if (entry < 0) {  // an empty graph: the first row in order is the entry point and is never wired (HnswIndex.java:184-186)
+    entry = n_old + order[0];
+    max_level = lv[order[0]];
+    at = 1;
+    linked = n_old + 1;
+  }
+  while (at < n) {  // the schedule: rounds of min(batch, max(1, linked / 8)) items
+    const int64_t m = std::min<int64_t>(n - at, std::min<int64_t>(batch, std::max<int64_t>(1, linked / 8)));
+    rounds.push_back({at, m, entry, max_level});
+    int64_t up = -1;
+    for (int64_t e = at; e < at + m; ++e) {
+      const uint32_t r = order[(size_t)e];
+      wired_top[r] = std::min(lv[r], max_level);
+      pair_off[(size_t)e + 1] = pair_off[(size_t)e] + (int64_t)(wired_top[r] + 1) * ix->m;
+      if (up < 0 && lv[r] > max_level) up = r;  // HnswIndex.java:193-198, the round as the unit of interleaving
+    }
+    max_keys = std::max(max_keys, pair_off[(size_t)(at + m)] - pair_off[(size_t)at]);
+    max_items = std::max(max_items, m);
+    if (up >= 0) {
+      entry = n_old + up;
+      max_level = lv[(size_t)up];
+    }
+    at += m;
+    linked += m;
+  }
+  if (max_keys >= (int64_t)1 << 31) return fail(HNSW_EINVAL, "batch * max_m too large");
+  // ---- new upper slots (rows at levels >= 1) at the end ----
+  const int64_t old_slots = (int64_t)ix->upper_base_h.size() - 1, old_rows = ix->upper_base_h.back();
+  std::vector<int32_t> new_slot((size_t)n, -1), new_base;
+  for (int64_t i = 0; i < n; ++i)
+    if (lv[(size_t)i] > 0) {
+      new_slot[(size_t)i] = (int32_t)(old_slots + (int64_t)new_base.size());
+      new_base.push_back((new_base.empty() ? (int32_t)old_rows : new_base.back()) + lv[(size_t)i]);
+    }
+  const int64_t n_slots = old_slots + (int64_t)new_base.size(), n_rows = new_base.empty() ? old_rows : new_base.back();
+  // ---- room: amortised (>= 1.5x), device to device; a failed growth leaves the index as it was ----
+  HTRY(hipSetDevice(ix->device));
+  if (int rc = grow_rows(ix, grown_capacity(ix, n_old + n))) return rc;
+  int64_t slots_cap = std::max(ix->upper_slots_cap, old_slots + 1), rows_cap = std::max(ix->upper_rows_cap, std::max<int64_t>(old_rows, 1));
+  if (n_slots + 1 > slots_cap) slots_cap = std::max(n_slots + 1, slots_cap + slots_cap / 2);
+  if (n_rows > rows_cap) rows_cap = std::max(n_rows, rows_cap + rows_cap / 2);
+  HTRY(grow_keep(ix->upper_base, (size_t)(old_slots + 1) * 4, (size_t)slots_cap * 4));
+  HTRY(grow_keep(ix->upper_adj, (size_t)old_rows * (ix->m + 1) * 4, (size_t)rows_cap * (ix->m + 1) * 4));
+  ix->upper_slots_cap = slots_cap;
+  ix->upper_rows_cap = rows_cap;
+  // construction scratch (kept on the handle)
+  size_t tmp_bytes = 0;
+  HTRY(ix->b_order.reserve((size_t)n * 4));
+  HTRY(ix->b_pair_off.reserve(((size_t)n + 1) * 8));
+  HTRY(ix->b_bstats.reserve(4 * 8));
+  if (int rc = reserve_round_keys(ix, std::max<int64_t>(max_keys, 1), tmp_bytes)) return rc;
+  if (max_items > 0)
+    if (int rc = reserve_visited(ix, max_items, batch)) return rc;
+
+  // ---- from here on the index changes: a device error leaves it broken ----
+  ix->broken = true;
+  if (int rc = stage_rows(ix, ix->q_in, vectors, n, n_old)) return rc;
+  if (ix->keyed) HTRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  HTRY(hipMemcpy(ix->upper_slot.as<int32_t>() + n_old, new_slot.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  if (!new_base.empty())
+    HTRY(hipMemcpy(ix->upper_base.as<int32_t>() + old_slots + 1, new_base.data(), new_base.size() * 4, hipMemcpyHostToDevice));
+  HTRY(hipMemsetAsync(ix->adj0.as<uint32_t>() + (size_t)n_old * (ix->m0 + 1), 0, (size_t)n * (ix->m0 + 1) * 4, 0));
+  if (n_rows > old_rows)
+    HTRY(hipMemsetAsync(ix->upper_adj.as<uint32_t>() + (size_t)old_rows * (ix->m + 1), 0, (size_t)(n_rows - old_rows) * (ix->m + 1) * 4, 0));
+  HTRY(hipMemcpy(ix->levels.as<int32_t>() + n_old, lv.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  std::vector<uint32_t> gorder((size_t)n);
+  for (int64_t e = 0; e < n; ++e) gorder[(size_t)e] = (uint32_t)(n_old + order[(size_t)e]);
+  HTRY(hipMemcpy(ix->b_order.p, gorder.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  HTRY(hipMemcpy(ix->b_pair_off.p, pair_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+  HTRY(hipMemsetAsync(ix->b_bstats.p, 0, 4 * 8, 0));
+  if (max_items > 0) {
+    BuildArgs a = build_args(ix, ef_construction);
+    a.order = ix->b_order.as<uint32_t>();
+    a.levels = ix->levels.as<int32_t>();
+    a.pair_off = ix->b_pair_off.as<int64_t>();
+    const int chunks = ix->dpad / 64;
+    for (const Round &r : rounds) {
+      a.entry = (uint32_t)r.entry;  // per round: a row above maxLevel moves the entry point for the rounds after its own
+      a.max_level = r.max_level;
+      a.at = (uint32_t)r.at;
+      a.count = (uint32_t)r.count;
+      a.n_keys = (uint32_t)(pair_off[(size_t)(r.at + r.count)] - pair_off[(size_t)r.at]);
+      BuildArgs a_ins = a, a_link = a;
+      a_ins.keys = ix->b_keys.as<uint64_t>();
+      a_link.keys = ix->b_sorted.as<uint64_t>();
+      launch_build_any(chunks, a_ins, a_link, 0, 0);
+      size_t tb = tmp_bytes;
+      HTRY(hipcub::DeviceRadixSort::SortKeys(ix->b_tmp.p, tb, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)a.n_keys, 0, 64, (hipStream_t)0));
+      launch_build_any(chunks, a_ins, a_link, 0, 1);
+      HTRY(hipGetLastError());
+    }
+  }
+  HTRY(hipDeviceSynchronize());
+  unsigned long long bs[4] = {0, 0, 0, 0};
+  HTRY(hipMemcpy(bs, ix->b_bstats.p, sizeof(bs), hipMemcpyDeviceToHost));
+  ix->broken = false;
+  // ---- the host side: O(n) of new rows; the lists themselves are read back only when exported (refresh_host) ----
+  ix->build_truncated = (int64_t)bs[0];
+  ix->build_prunes = (int64_t)bs[1];
+  ix->build_dropped = (int64_t)bs[2];
+  ix->build_rounds = (int64_t)rounds.size();
+  ix->n = n_old + n;
+  ix->entry = entry;
+  ix->max_level = std::max(max_level, 0);
+  ix->has_ids = ix->keyed;
+  ix->upper_slot_h.resize((size_t)n_old);
+  ix->upper_slot_h.insert(ix->upper_slot_h.end(), new_slot.begin(), new_slot.end());
+  ix->upper_base_h.insert(ix->upper_base_h.end(), new_base.begin(), new_base.end());
+  ix->level0.resize((size_t)(n_old + n));
+  ix->has0.resize((size_t)n_old);
+  int top_all = (int)ix->upper.size();
+  for (int64_t i = 0; i < n; ++i) {
+    ix->has0.push_back(wired_top[(size_t)i] >= 0 ? 1 : 0);
+    if (lv[(size_t)i] > 0) {
+      std::vector<uint8_t> h((size_t)lv[(size_t)i], 0);
+      for (int l = 1; l <= lv[(size_t)i]; ++l) h[(size_t)l - 1] = l <= wired_top[(size_t)i] ? 1 : 0;
+      ix->has_upper.push_back(std::move(h));
+      top_all = std::max(top_all, lv[(size_t)i]);
+    }
+  }
+  ix->upper.resize((size_t)top_all);
+  for (auto &layer : ix->upper) layer.resize((size_t)n_slots);
+  ix->host_stale = true;
+  return HNSW_OK;
+}
+
+// Construction scratch does not outlive a build: at 50M rows the visited bitmaps of 4096 walks alone are 25.6 GB, beside what
+// hnsw_search budgets for itself.  (An append keeps its scratch on purpose; the one after a build makes it anew, `levels`
+// too, which is read only for rows being inserted.)
+static void release_build_scratch(hnsw_index *ix) {
+  for (Buf *b : {&ix->b_order, &ix->b_pair_off, &ix->b_keys, &ix->b_sorted, &ix->b_tmp, &ix->b_bstats, &ix->b_visited, &ix->b_vlog,
+                 &ix->levels, &ix->q_in})
+    b->release();
+  ix->bv_items = ix->bv_vwords = 0;
+  ix->bv_clean = false;
+}
+
+// the one-shot build: insert_rows over all rows into an empty graph.  Unlike an append it does not look for repeated keys and
+// does not build the sorted key table (the first append does).
 static int build_insert_gpu_impl(int32_t device, int32_t metric, int64_t n, int32_t d, const float *vectors, const int64_t *ids,
                                  int32_t max_m, int32_t ef_construction, uint64_t seed, const int32_t *given_levels, int32_t batch,
                                  hnsw_index_t **out) {
   if (!out) return fail(HNSW_EINVAL, "out is NULL");
-  if (ef_construction < 1 || ef_construction > BUILD_EF_MAX) return fail(HNSW_EINVAL, "ef_construction must be in 1..256");
-  if (batch < 0 || batch > (1 << 20)) return fail(HNSW_EINVAL, "batch must be in 0..2^20");
-  if (batch == 0) batch = 4096;
+  int rc = check_construction_args(ef_construction, batch);
+  if (rc) return rc;
   std::unique_ptr<hnsw_index> ix;
-  int rc = create_index(device, metric, n, d, vectors, nullptr, max_m, ix, nullptr);  // (positions as labels while building)
+  rc = new_index(device, metric, n, d, vectors, max_m, ix);
   if (rc) return rc;
-  const double level_mult = 1.0 / std::log(1.0 * max_m);  // HnswIndex.java:118
-  std::vector<int32_t> levels((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    if (given_levels) {
-      if (given_levels[i] < 0 || given_levels[i] > 60) return fail(HNSW_EINVAL, "a level is outside 0..60");
-      levels[(size_t)i] = given_levels[i];
-      continue;
-    }
-    const uint64_t h = sann::mix64(seed ^ ((uint64_t)i * 0x9E3779B97F4A7C15ull));
-    const double u = ((double)(h >> 11) + 1.0) * (1.0 / 9007199254740992.0);  // (0, 1]
-    levels[(size_t)i] = std::min(60, (int)(-std::log(u) * level_mult));       // getRandomLevel, :369-371
-  }
-  // the empty graph with every row in place (rows are a function of the levels); the kernels fill it
-  HostGraph g;
-  g.init(n, max_m, levels);
-  std::vector<uint32_t> order((size_t)n);
-  for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (uint32_t)i;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return levels[x] > levels[y]; });
-  if (n > 0) {
-    g.entry = order[0];
-    g.max_level = levels[order[0]];
-  }
-  rc = upload_graph(ix.get(), g);
+  std::vector<int32_t> levels;
+  rc = draw_levels(seed, 0, n, max_m, given_levels, levels);
   if (rc) return rc;
-  ix->build_truncated = ix->build_prunes = ix->build_dropped = ix->build_rounds = 0;
-  if (n > 1) {
-    HTRY(hipSetDevice(device));
-    const int max_level = ix->max_level;
-    std::vector<int64_t> pair_off((size_t)n + 1, 0);
-    for (int64_t e = 0; e < n; ++e) pair_off[(size_t)e + 1] = pair_off[(size_t)e] + (int64_t)(std::min(levels[order[(size_t)e]], max_level) + 1) * max_m;
-    // the schedule: rounds of min(batch, max(1, linked / 8)) items
-    std::vector<std::pair<int64_t, int64_t>> rounds;
-    int64_t max_keys = 0, max_items = 0;
-    for (int64_t at = 1, linked = 1; at < n;) {
-      const int64_t m = std::min<int64_t>(n - at, std::min<int64_t>(batch, std::max<int64_t>(1, linked / 8)));
-      rounds.emplace_back(at, m);
-      max_keys = std::max(max_keys, pair_off[(size_t)(at + m)] - pair_off[(size_t)at]);
-      max_items = std::max(max_items, m);
-      at += m;
-      linked += m;
-    }
-    if (max_keys >= (int64_t)1 << 31) return fail(HNSW_EINVAL, "batch * max_m too large");
-    Buf d_order, d_levels, d_pair_off, d_keys, d_sorted, d_tmp, d_bstats, d_visited, d_vlog;
-    HTRY(d_order.reserve((size_t)n * 4));
-    HTRY(d_levels.reserve((size_t)n * 4));
-    HTRY(d_pair_off.reserve(((size_t)n + 1) * 8));
-    HTRY(hipMemcpy(d_order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HTRY(hipMemcpy(d_levels.p, levels.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HTRY(hipMemcpy(d_pair_off.p, pair_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    HTRY(d_keys.reserve((size_t)max_keys * 8));
-    HTRY(d_sorted.reserve((size_t)max_keys * 8));
-    HTRY(d_bstats.reserve(4 * 8));
-    HTRY(hipMemset(d_bstats.p, 0, 4 * 8));
-    const int64_t vwords = ((n + 31) / 32 + 255) / 256 * 256;
-    HTRY(d_visited.reserve((size_t)max_items * vwords * 4));
-    const bool use_vlog = vwords >= VLOG_MIN_VWORDS || getenv("HNSW_DEBUG_VLOG") != nullptr;  // (the variable: tests force the log on small graphs)
-    if (use_vlog) {
-      HTRY(hipMemset(d_visited.p, 0, (size_t)max_items * vwords * 4));  // once: every walk cleans up after itself
-      HTRY(d_vlog.reserve((size_t)max_items * VLOG_CAP * 4));
-    }
-    size_t tmp_bytes = 0;
-    HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, d_keys.as<uint64_t>(), d_sorted.as<uint64_t>(), (int)max_keys, 0, 64, (hipStream_t)0));
-    HTRY(d_tmp.reserve(tmp_bytes));
-    BuildArgs a;
-    a.x = ix->x.as<_Float16>();
-    a.adj0 = ix->adj0.as<uint32_t>();
-    a.upper_slot = ix->upper_slot.as<int32_t>();
-    a.upper_base = ix->upper_base.as<int32_t>();
-    a.upper_adj = ix->upper_adj.as<uint32_t>();
-    a.order = d_order.as<uint32_t>();
-    a.levels = d_levels.as<int32_t>();
-    a.pair_off = d_pair_off.as<int64_t>();
-    a.visited = d_visited.as<uint32_t>();
-    a.vlog = use_vlog ? d_vlog.as<uint32_t>() : nullptr;
-    a.bstats = d_bstats.as<unsigned long long>();
-    a.vwords = vwords;
-    a.dpad = ix->dpad;
-    a.metric = ix->metric;
-    a.m = ix->m;
-    a.m0 = ix->m0;
-    a.efc = ef_construction;
-    a.max_level = max_level;
-    a.ccap = BUILD_CCAP;
-    if (const char *e = std::getenv("HNSW_BUILD_CCAP")) a.ccap = std::max(2, std::min(BUILD_CCAP, std::atoi(e)));  // (tests: make the prune path run)
-    a.entry = (uint32_t)ix->entry;
-    const int chunks = ix->dpad / 64;
-    for (const auto &r : rounds) {
-      a.at = (uint32_t)r.first;
-      a.count = (uint32_t)r.second;
-      a.n_keys = (uint32_t)(pair_off[(size_t)(r.first + r.second)] - pair_off[(size_t)r.first]);
-      BuildArgs a_ins = a, a_link = a;
-      a_ins.keys = d_keys.as<uint64_t>();
-      a_link.keys = d_sorted.as<uint64_t>();
-      launch_build_any(chunks, a_ins, a_link, 0, 0);
-      size_t tb = tmp_bytes;
-      HTRY(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tb, d_keys.as<uint64_t>(), d_sorted.as<uint64_t>(), (int)a.n_keys, 0, 64, (hipStream_t)0));
-      launch_build_any(chunks, a_ins, a_link, 0, 1);
-      HTRY(hipGetLastError());
-    }
-    HTRY(hipDeviceSynchronize());
-    unsigned long long bs[4] = {0, 0, 0, 0};
-    HTRY(hipMemcpy(bs, d_bstats.p, sizeof(bs), hipMemcpyDeviceToHost));
-    ix->build_truncated = (int64_t)bs[0];
-    ix->build_prunes = (int64_t)bs[1];
-    ix->build_dropped = (int64_t)bs[2];
-    ix->build_rounds = (int64_t)rounds.size();
-    // ---- the finished graph back to the host copy (export, files).  The map holds HnswNode(level, item) for every wired item
-    //      and layer; the first item was never wired (:184-186: no entry point yet) and has a key only where a back link put one
-    std::vector<uint32_t> adj0((size_t)n * (ix->m0 + 1));
-    HTRY(hipMemcpy(adj0.data(), ix->adj0.p, adj0.size() * 4, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) {
-      const uint32_t *row = &adj0[(size_t)i * (ix->m0 + 1)];
-      ix->level0[(size_t)i].assign(row + 1, row + 1 + row[0]);
-      ix->has0[(size_t)i] = (row[0] > 0 || i != ix->entry) ? 1 : 0;
-    }
-    const int64_t urows = ix->upper_base_h.back();
-    std::vector<uint32_t> uadj((size_t)std::max<int64_t>(urows, 1) * (ix->m + 1));
-    if (urows > 0) HTRY(hipMemcpy(uadj.data(), ix->upper_adj.p, (size_t)urows * (ix->m + 1) * 4, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t sl = ix->upper_slot_h[(size_t)i];
-      if (sl < 0) continue;
-      for (int l = 1; l <= levels[(size_t)i]; ++l) {
-        const uint32_t *row = uadj.data() + (size_t)(ix->upper_base_h[(size_t)sl] + l - 1) * (ix->m + 1);
-        ix->upper[(size_t)l - 1][(size_t)sl].assign(row + 1, row + 1 + row[0]);
-        ix->has_upper[(size_t)sl][(size_t)l - 1] = (row[0] > 0 || i != ix->entry) ? 1 : 0;
-      }
-    }
-  }
-  if (ids && n > 0) {
-    HTRY(ix->ids.reserve((size_t)n * 8));
-    HTRY(hipMemcpy(ix->ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
-    ix->has_ids = true;
-  }
+  rc = upload_graph(ix.get(), HostGraph());  // no rows, no entry point
+  if (rc) return rc;
   ix->keyed = ids != nullptr;
+  rc = insert_rows(ix.get(), n, vectors, ids, levels, ef_construction, batch);
+  if (rc) return rc;
+  release_build_scratch(ix.get());
   *out = ix.release();
   return HNSW_OK;
 }
@@ -1988,11 +2107,8 @@ int hnsw_index_build_insert_gpu_levels(int32_t device, int32_t metric, int64_t n
 } ABI_CATCH
 
 // ---- hnsw_index_append -------------------------------------------------------------------------------------------------
-// Rounds of the device builder continued on a live index: see include/hnsw_ann.h.  The host works out the new rows' levels,
-// their order and the round schedule (functions of the levels and n_old alone), grows the buffers device to device, and
-// enqueues kernels; what comes back per call is O(1): the first duplicate key, if any, and the round counters.
-static const char *const BROKEN = "an earlier append failed on the device part-way: the index is unusable";
-
+// insert_rows on a live index, see include/hnsw_ann.h; what is an append's alone is here: the refusals, and for a keyed index the
+// first duplicate key, if any (all that comes back besides the round counters), and the sorted table of the keys.
 static int append_keys_check(hnsw_index *ix, int64_t n, const int64_t *ids) {
   const int64_t n_old = ix->n;
   size_t tmp_bytes = 0;
@@ -2030,7 +2146,7 @@ static int append_keys_check(hnsw_index *ix, int64_t n, const int64_t *ids) {
   return HNSW_OK;
 }
 
-// the host copy of the graph after appends: every list from the device; a key exists where the host recorded one (loaded,
+// the host copy of the graph behind the device's: every list from the device; a key exists where the host recorded one (loaded,
 // or wired by a build or an append) or where a list is not empty (a back link made it)
 static int refresh_host(const hnsw_index *cix) {
   if (!cix->host_stale) return HNSW_OK;
@@ -2064,227 +2180,29 @@ static int append_impl(hnsw_index *ix, int64_t n, const float *vectors, const in
   if (!ix) return fail(HNSW_EINVAL, "NULL index");
   if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
   if (n < 0) return fail(HNSW_EINVAL, "n must not be negative");
-  if (ef_construction < 1 || ef_construction > BUILD_EF_MAX) return fail(HNSW_EINVAL, "ef_construction must be in 1..256");
-  if (batch < 0 || batch > (1 << 20)) return fail(HNSW_EINVAL, "batch must be in 0..2^20");
-  if (batch == 0) batch = 4096;
+  if (int rc = check_construction_args(ef_construction, batch)) return rc;
   if (n == 0) return HNSW_OK;
   if (!vectors) return fail(HNSW_EINVAL, "NULL vectors");
   if (ix->keyed && !ids) return fail(HNSW_EINVAL, "the index was created with ids: an append must give ids");
   if (!ix->keyed && ids) return fail(HNSW_EINVAL, "the index was created without ids (its keys are positions): ids must be NULL");
-  const int64_t n_old = ix->n;
-  if (n_old + n >= (int64_t)0x7fffffff) return fail(HNSW_EINVAL, "the index would reach 2^31 - 1 rows");
-  std::vector<int32_t> lv((size_t)n);
-  const double level_mult = 1.0 / std::log(1.0 * ix->m);  // HnswIndex.java:118
-  for (int64_t i = 0; i < n; ++i) {
-    if (given_levels) {
-      if (given_levels[i] < 0 || given_levels[i] > 60) return fail(HNSW_EINVAL, "a level is outside 0..60");
-      lv[(size_t)i] = given_levels[i];
-      continue;
-    }
-    const uint64_t h = sann::mix64(seed ^ ((uint64_t)(n_old + i) * 0x9E3779B97F4A7C15ull));  // the builder's draw, global position
-    const double u = ((double)(h >> 11) + 1.0) * (1.0 / 9007199254740992.0);
-    lv[(size_t)i] = std::min(60, (int)(-std::log(u) * level_mult));
-  }
+  if (ix->n + n >= (int64_t)0x7fffffff) return fail(HNSW_EINVAL, "the index would reach 2^31 - 1 rows");
+  std::vector<int32_t> lv;
+  if (int rc = draw_levels(seed, ix->n, n, ix->m, given_levels, lv)) return rc;  // the builder's draw, at the global position
   HTRY(hipSetDevice(ix->device));
-  if (ix->keyed) {
-    const int rc = append_keys_check(ix, n, ids);
-    if (rc) return rc;
-  }
-  // ---- order, rounds, entry point per round (host: functions of the levels and n_old) ----
-  std::vector<uint32_t> order((size_t)n);
-  for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (uint32_t)i;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return lv[x] > lv[y]; });
-  struct Round {
-    int64_t at, count, entry;
-    int max_level;
-  };
-  std::vector<Round> rounds;
-  std::vector<int64_t> pair_off((size_t)n + 1, 0);
-  std::vector<int32_t> wired_top((size_t)n, -1);  // layers each new row is wired on (-1: it became the entry of an empty graph)
-  int64_t entry = ix->entry, at = 0, linked = n_old, max_keys = 0, max_items = 0;
-  int max_level = ix->max_level;
-  if (entry < 0) {  // an empty graph: the first row in order is the entry point, as in a build
-    entry = n_old + order[0];
-    max_level = lv[order[0]];
-    at = 1;
-    linked = n_old + 1;
-  }
-  while (at < n) {
-    const int64_t m = std::min<int64_t>(n - at, std::min<int64_t>(batch, std::max<int64_t>(1, linked / 8)));
-    rounds.push_back({at, m, entry, max_level});
-    int64_t up = -1;
-    for (int64_t e = at; e < at + m; ++e) {
-      const uint32_t r = order[(size_t)e];
-      wired_top[r] = std::min(lv[r], max_level);
-      pair_off[(size_t)e + 1] = pair_off[(size_t)e] + (int64_t)(wired_top[r] + 1) * ix->m;
-      if (up < 0 && lv[r] > max_level) up = r;  // HnswIndex.java:193-198, the round as the unit of interleaving
-    }
-    max_keys = std::max(max_keys, pair_off[(size_t)(at + m)] - pair_off[(size_t)at]);
-    max_items = std::max(max_items, m);
-    if (up >= 0) {
-      entry = n_old + up;
-      max_level = lv[(size_t)up];
-    }
-    at += m;
-    linked += m;
-  }
-  if (max_keys >= (int64_t)1 << 31) return fail(HNSW_EINVAL, "batch * max_m too large");
-  // ---- new upper slots (rows at levels >= 1) at the end ----
-  const int64_t old_slots = (int64_t)ix->upper_base_h.size() - 1, old_rows = ix->upper_base_h.back();
-  std::vector<int32_t> new_slot((size_t)n, -1), new_base;
-  for (int64_t i = 0; i < n; ++i)
-    if (lv[(size_t)i] > 0) {
-      new_slot[(size_t)i] = (int32_t)(old_slots + (int64_t)new_base.size());
-      new_base.push_back((new_base.empty() ? (int32_t)old_rows : new_base.back()) + lv[(size_t)i]);
-    }
-  const int64_t n_slots = old_slots + (int64_t)new_base.size(), n_rows = new_base.empty() ? old_rows : new_base.back();
-  // ---- room: amortised (>= 1.5x), device to device; a failed growth leaves the index as it was ----
-  const int64_t need = n_old + n;
-  int64_t cap = std::max(ix->cap, n_old);
-  if (need > cap) cap = std::max(need, cap + cap / 2);
-  HTRY(grow_keep(ix->x, (size_t)n_old * ix->dpad * sizeof(_Float16), (size_t)cap * ix->dpad * sizeof(_Float16)));
-  HTRY(grow_keep(ix->adj0, (size_t)n_old * (ix->m0 + 1) * 4, (size_t)cap * (ix->m0 + 1) * 4));
-  HTRY(grow_keep(ix->upper_slot, (size_t)n_old * 4, (size_t)cap * 4));
-  HTRY(grow_keep(ix->levels, 0, (size_t)cap * 4));
-  if (ix->keyed) HTRY(grow_keep(ix->ids, (size_t)n_old * 8, (size_t)cap * 8));
-  ix->cap = cap;
-  int64_t slots_cap = std::max(ix->upper_slots_cap, old_slots + 1), rows_cap = std::max(ix->upper_rows_cap, std::max<int64_t>(old_rows, 1));
-  if (n_slots + 1 > slots_cap) slots_cap = std::max(n_slots + 1, slots_cap + slots_cap / 2);
-  if (n_rows > rows_cap) rows_cap = std::max(n_rows, rows_cap + rows_cap / 2);
-  HTRY(grow_keep(ix->upper_base, (size_t)(old_slots + 1) * 4, (size_t)slots_cap * 4));
-  HTRY(grow_keep(ix->upper_adj, (size_t)old_rows * (ix->m + 1) * 4, (size_t)rows_cap * (ix->m + 1) * 4));
-  ix->upper_slots_cap = slots_cap;
-  ix->upper_rows_cap = rows_cap;
-  // construction scratch (kept on the handle)
-  const int64_t vwords = ((cap + 31) / 32 + 255) / 256 * 256;
-  const bool use_vlog = vwords >= VLOG_MIN_VWORDS || getenv("HNSW_DEBUG_VLOG") != nullptr;  // (as in the builder)
-  size_t tmp_bytes = 0;
-  HTRY(ix->b_order.reserve((size_t)n * 4));
-  HTRY(ix->b_pair_off.reserve(((size_t)n + 1) * 8));
-  HTRY(ix->b_keys.reserve((size_t)std::max<int64_t>(max_keys, 1) * 8));
-  HTRY(ix->b_sorted.reserve((size_t)std::max<int64_t>(max_keys, 1) * 8));
-  HTRY(ix->b_bstats.reserve(4 * 8));
-  HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)std::max<int64_t>(max_keys, 1), 0, 64, (hipStream_t)0));
-  HTRY(ix->b_tmp.reserve(tmp_bytes));
-  if (max_items > 0 && (vwords != ix->bv_vwords || max_items > ix->bv_items)) {  // a new bitmap layout
-    const int64_t items = std::max(max_items, vwords == ix->bv_vwords ? std::min<int64_t>(2 * ix->bv_items, batch) : 0);
-    ix->bv_items = ix->bv_vwords = 0;
-    ix->bv_clean = false;
-    HTRY(ix->b_visited.reserve((size_t)items * vwords * 4));
-    ix->bv_items = items;
-    ix->bv_vwords = vwords;
-  }
-  if (max_items > 0 && use_vlog) HTRY(ix->b_vlog.reserve((size_t)ix->bv_items * VLOG_CAP * 4));
-  if (ix->keyed) HTRY(ix->key_next.reserve((size_t)cap * 8));
-
-  // ---- from here on the index changes: a device error leaves it broken ----
-  ix->broken = true;
-  {
-    const int64_t chunk = std::max<int64_t>(1, (int64_t)(128u << 20) / ((int64_t)ix->d * 4));
-    HTRY(ix->q_in.reserve((size_t)std::min(chunk, n) * ix->d * 4));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {  // hnsw_prep_rows, as at build time
-      const int64_t m = std::min(chunk, n - r0);
-      HTRY(hipMemcpy(ix->q_in.p, vectors + r0 * ix->d, (size_t)m * ix->d * 4, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(hnsw_prep_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, ix->q_in.as<float>(), m, ix->d, ix->dpad,
-                         ix->metric == HNSW_METRIC_COSINE ? 1 : 0, ix->x.as<_Float16>() + (n_old + r0) * ix->dpad);
-      HTRY(hipGetLastError());
-    }
-  }
-  if (ix->keyed) HTRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ix->key_in.p, (size_t)n * 8, hipMemcpyDeviceToDevice));
-  HTRY(hipMemcpy(ix->upper_slot.as<int32_t>() + n_old, new_slot.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  if (!new_base.empty())
-    HTRY(hipMemcpy(ix->upper_base.as<int32_t>() + old_slots + 1, new_base.data(), new_base.size() * 4, hipMemcpyHostToDevice));
-  HTRY(hipMemsetAsync(ix->adj0.as<uint32_t>() + (size_t)n_old * (ix->m0 + 1), 0, (size_t)n * (ix->m0 + 1) * 4, 0));
-  if (n_rows > old_rows)
-    HTRY(hipMemsetAsync(ix->upper_adj.as<uint32_t>() + (size_t)old_rows * (ix->m + 1), 0, (size_t)(n_rows - old_rows) * (ix->m + 1) * 4, 0));
-  HTRY(hipMemcpy(ix->levels.as<int32_t>() + n_old, lv.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  std::vector<uint32_t> gorder((size_t)n);
-  for (int64_t e = 0; e < n; ++e) gorder[(size_t)e] = (uint32_t)(n_old + order[(size_t)e]);
-  HTRY(hipMemcpy(ix->b_order.p, gorder.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  HTRY(hipMemcpy(ix->b_pair_off.p, pair_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-  HTRY(hipMemsetAsync(ix->b_bstats.p, 0, 4 * 8, 0));
-  if (max_items > 0) {
-    if (use_vlog && !ix->bv_clean) HTRY(hipMemsetAsync(ix->b_visited.p, 0, (size_t)ix->bv_items * vwords * 4, 0));  // once per layout
-    ix->bv_clean = use_vlog;  // (walks with the log leave their bitmaps clean; walks without it leave them dirty)
-    BuildArgs a;
-    a.x = ix->x.as<_Float16>();
-    a.adj0 = ix->adj0.as<uint32_t>();
-    a.upper_slot = ix->upper_slot.as<int32_t>();
-    a.upper_base = ix->upper_base.as<int32_t>();
-    a.upper_adj = ix->upper_adj.as<uint32_t>();
-    a.order = ix->b_order.as<uint32_t>();
-    a.levels = ix->levels.as<int32_t>();
-    a.pair_off = ix->b_pair_off.as<int64_t>();
-    a.visited = ix->b_visited.as<uint32_t>();
-    a.vlog = use_vlog ? ix->b_vlog.as<uint32_t>() : nullptr;
-    a.bstats = ix->b_bstats.as<unsigned long long>();
-    a.vwords = vwords;
-    a.dpad = ix->dpad;
-    a.metric = ix->metric;
-    a.m = ix->m;
-    a.m0 = ix->m0;
-    a.efc = ef_construction;
-    a.ccap = BUILD_CCAP;
-    if (const char *e = std::getenv("HNSW_BUILD_CCAP")) a.ccap = std::max(2, std::min(BUILD_CCAP, std::atoi(e)));
-    const int chunks = ix->dpad / 64;
-    for (const Round &r : rounds) {
-      a.entry = (uint32_t)r.entry;  // per round: a row above maxLevel moves the entry point for the rounds after its own
-      a.max_level = r.max_level;
-      a.at = (uint32_t)r.at;
-      a.count = (uint32_t)r.count;
-      a.n_keys = (uint32_t)(pair_off[(size_t)(r.at + r.count)] - pair_off[(size_t)r.at]);
-      BuildArgs a_ins = a, a_link = a;
-      a_ins.keys = ix->b_keys.as<uint64_t>();
-      a_link.keys = ix->b_sorted.as<uint64_t>();
-      launch_build_any(chunks, a_ins, a_link, 0, 0);
-      size_t tb = tmp_bytes;
-      HTRY(hipcub::DeviceRadixSort::SortKeys(ix->b_tmp.p, tb, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)a.n_keys, 0, 64, (hipStream_t)0));
-      launch_build_any(chunks, a_ins, a_link, 0, 1);
-      HTRY(hipGetLastError());
-    }
-  }
-  if (ix->keyed) {  // the new keys into the sorted table (merge path), then the tables swap
+  if (ix->keyed) {  // the new keys merged with the sorted table (merge path) into key_next, which is nothing until the tables swap
+    if (int rc = append_keys_check(ix, n, ids)) return rc;
+    HTRY(ix->key_next.reserve((size_t)grown_capacity(ix, ix->n + n) * 8));
     const int64_t total = ix->key_n + n, threads = (total + MERGE_ITEMS - 1) / MERGE_ITEMS;
     hipLaunchKernelGGL(hnsw_key_merge_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, ix->key_table.as<int64_t>(), ix->key_n,
                        ix->key_batch.as<int64_t>(), n, ix->key_next.as<int64_t>());
     HTRY(hipGetLastError());
   }
-  HTRY(hipDeviceSynchronize());
-  unsigned long long bs[4] = {0, 0, 0, 0};
-  HTRY(hipMemcpy(bs, ix->b_bstats.p, sizeof(bs), hipMemcpyDeviceToHost));
-  ix->broken = false;
+  if (int rc = insert_rows(ix, n, vectors, ids, lv, ef_construction, batch)) return rc;  // (it ends with a synchronise: the merge is done)
   if (ix->keyed) {
     std::swap(ix->key_table.p, ix->key_next.p);
     std::swap(ix->key_table.bytes, ix->key_next.bytes);
     ix->key_n += n;
   }
-  // ---- the host side: O(n) of appended rows; the lists themselves are read back only when exported ----
-  ix->build_truncated = (int64_t)bs[0];
-  ix->build_prunes = (int64_t)bs[1];
-  ix->build_dropped = (int64_t)bs[2];
-  ix->build_rounds = (int64_t)rounds.size();
-  ix->n = n_old + n;
-  ix->entry = entry;
-  ix->max_level = std::max(max_level, 0);
-  ix->has_ids = ix->keyed;
-  ix->upper_slot_h.resize((size_t)n_old);
-  ix->upper_slot_h.insert(ix->upper_slot_h.end(), new_slot.begin(), new_slot.end());
-  ix->upper_base_h.insert(ix->upper_base_h.end(), new_base.begin(), new_base.end());
-  ix->level0.resize((size_t)(n_old + n));
-  ix->has0.resize((size_t)n_old);
-  int top_all = (int)ix->upper.size();
-  for (int64_t i = 0; i < n; ++i) {
-    ix->has0.push_back(wired_top[(size_t)i] >= 0 ? 1 : 0);
-    if (lv[(size_t)i] > 0) {
-      std::vector<uint8_t> h((size_t)lv[(size_t)i], 0);
-      for (int l = 1; l <= lv[(size_t)i]; ++l) h[(size_t)l - 1] = l <= wired_top[(size_t)i] ? 1 : 0;
-      ix->has_upper.push_back(std::move(h));
-      top_all = std::max(top_all, lv[(size_t)i]);
-    }
-  }
-  ix->upper.resize((size_t)top_all);
-  for (auto &layer : ix->upper) layer.resize((size_t)n_slots);
-  ix->host_stale = true;
   return HNSW_OK;
 }
 
@@ -2337,7 +2255,7 @@ static int update_positions(hnsw_index *ix, int64_t n, const int64_t *ids, std::
 
 // the rounds over the present rows: their positions in request order and their rows as given (fp32 [np][d], prepared on the device)
 static int update_rounds(hnsw_index *ix, const std::vector<uint32_t> &P, const std::vector<float> &rows, int32_t efc, int32_t batch) {
-  const int64_t np = (int64_t)P.size(), B = batch == 0 ? 4096 : batch;  // (tools/hnsw_update_probe.py: 4096 beats 1024 and 256)
+  const int64_t np = (int64_t)P.size(), B = batch;
   const bool graph_on = ix->entry >= 0;  // (an empty graph: HnswIndex.reInsert's checkState(entryPoint.isPresent); rows alone)
   // ---- host: per item, the layers it has storage for (capped at maxLevel) and the keys the host holds ----
   std::vector<uint64_t> fmask((size_t)np, 0);
@@ -2364,9 +2282,6 @@ static int update_rounds(hnsw_index *ix, const std::vector<uint32_t> &P, const s
   }
   if (max_props >= (int64_t)1 << 27) return fail(HNSW_EINVAL, "batch * max_m too large");
   // ---- scratch (a failed allocation leaves the index as it was) ----
-  const int64_t cap = std::max(ix->cap, ix->n);
-  const int64_t vwords = ((cap + 31) / 32 + 255) / 256 * 256;
-  const bool use_vlog = vwords >= VLOG_MIN_VWORDS || getenv("HNSW_DEBUG_VLOG") != nullptr;  // (as in the builder)
   HTRY(ix->u_pos.reserve((size_t)np * 4));
   HTRY(ix->u_fmask.reserve((size_t)np * 8));
   HTRY(ix->u_top.reserve((size_t)np * 4));
@@ -2377,22 +2292,13 @@ static int update_rounds(hnsw_index *ix, const std::vector<uint32_t> &P, const s
   HTRY(ix->u_psorted.reserve((size_t)max_props * 8));
   HTRY(ix->u_own.reserve((size_t)(max_keys / ix->m + 1) * (ix->m + 1) * 4));
   HTRY(ix->u_rows.reserve((size_t)np * ix->d * 4));
-  HTRY(ix->b_keys.reserve((size_t)max_keys * 8));
-  HTRY(ix->b_sorted.reserve((size_t)max_keys * 8));
   HTRY(ix->b_bstats.reserve(8 * 8));
   size_t tb_keys = 0, tb_props = 0;
-  HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb_keys, ix->b_keys.as<uint64_t>(), ix->b_sorted.as<uint64_t>(), (int)max_keys, 0, 64, (hipStream_t)0));
+  if (int rc = reserve_round_keys(ix, max_keys, tb_keys)) return rc;
   HTRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tb_props, ix->u_pkeys.as<uint64_t>(), ix->u_psorted.as<uint64_t>(), (int)max_props, 0, 64, (hipStream_t)0));
   HTRY(ix->b_tmp.reserve(std::max(tb_keys, tb_props)));
-  if (graph_on && (vwords != ix->bv_vwords || max_items > ix->bv_items)) {  // a new bitmap layout (as append_impl)
-    const int64_t items = std::max(max_items, vwords == ix->bv_vwords ? std::min<int64_t>(2 * ix->bv_items, B) : 0);
-    ix->bv_items = ix->bv_vwords = 0;
-    ix->bv_clean = false;
-    HTRY(ix->b_visited.reserve((size_t)items * vwords * 4));
-    ix->bv_items = items;
-    ix->bv_vwords = vwords;
-  }
-  if (graph_on && use_vlog) HTRY(ix->b_vlog.reserve((size_t)ix->bv_items * VLOG_CAP * 4));
+  if (graph_on)
+    if (int rc = reserve_visited(ix, max_items, B)) return rc;
 
   // ---- from here on the index changes: a device error leaves it broken ----
   ix->broken = true;
@@ -2402,28 +2308,9 @@ static int update_rounds(hnsw_index *ix, const std::vector<uint32_t> &P, const s
   HTRY(hipMemcpy(ix->u_pair_off.p, pair_off.data(), ((size_t)np + 1) * 8, hipMemcpyHostToDevice));
   HTRY(hipMemcpy(ix->u_prop_off.p, prop_off.data(), ((size_t)np + 1) * 8, hipMemcpyHostToDevice));
   HTRY(hipMemsetAsync(ix->b_bstats.p, 0, 8 * 8, 0));
-  if (graph_on && use_vlog && !ix->bv_clean) HTRY(hipMemsetAsync(ix->b_visited.p, 0, (size_t)ix->bv_items * vwords * 4, 0));
-  if (graph_on) ix->bv_clean = use_vlog;
-  BuildArgs a{};
-  a.x = ix->x.as<_Float16>();
-  a.adj0 = ix->adj0.as<uint32_t>();
-  a.upper_slot = ix->upper_slot.as<int32_t>();
-  a.upper_base = ix->upper_base.as<int32_t>();
-  a.upper_adj = ix->upper_adj.as<uint32_t>();
+  BuildArgs a = build_args(ix, efc);
   a.order = ix->u_pos.as<uint32_t>();
-  a.levels = nullptr;
   a.pair_off = ix->u_pair_off.as<int64_t>();
-  a.visited = ix->b_visited.as<uint32_t>();
-  a.vlog = use_vlog ? ix->b_vlog.as<uint32_t>() : nullptr;
-  a.bstats = ix->b_bstats.as<unsigned long long>();
-  a.vwords = vwords;
-  a.dpad = ix->dpad;
-  a.metric = ix->metric;
-  a.m = ix->m;
-  a.m0 = ix->m0;
-  a.efc = efc;
-  a.ccap = BUILD_CCAP;
-  if (const char *e = std::getenv("HNSW_BUILD_CCAP")) a.ccap = std::max(2, std::min(BUILD_CCAP, std::atoi(e)));
   a.entry = (uint32_t)std::max<int64_t>(ix->entry, 0);  // an update never moves the entry point or maxLevel
   a.max_level = ix->max_level;
   a.utop = ix->u_top.as<int32_t>();
@@ -2489,8 +2376,7 @@ static int update_impl(hnsw_index *ix, int64_t n, const float *vectors, const in
   if (!ix) return fail(HNSW_EINVAL, "NULL index");
   if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
   if (n < 0) return fail(HNSW_EINVAL, "n must not be negative");
-  if (ef_construction < 1 || ef_construction > BUILD_EF_MAX) return fail(HNSW_EINVAL, "ef_construction must be in 1..256");
-  if (batch < 0 || batch > (1 << 20)) return fail(HNSW_EINVAL, "batch must be in 0..2^20");
+  if (int rc = check_construction_args(ef_construction, batch)) return rc;
   if (n == 0) return HNSW_OK;
   if (!vectors || !ids) return fail(HNSW_EINVAL, "NULL vectors or ids");
   {
@@ -2566,16 +2452,11 @@ int hnsw_index_reserve(hnsw_index_t *ix, int64_t capacity) try {
   const int64_t n = ix->n;
   if (capacity <= std::max(ix->cap, n)) return HNSW_OK;  // never shrinks
   HTRY(hipSetDevice(ix->device));
-  HTRY(grow_keep(ix->x, (size_t)n * ix->dpad * sizeof(_Float16), (size_t)capacity * ix->dpad * sizeof(_Float16)));
-  HTRY(grow_keep(ix->adj0, (size_t)n * (ix->m0 + 1) * 4, (size_t)capacity * (ix->m0 + 1) * 4));
-  HTRY(grow_keep(ix->upper_slot, (size_t)n * 4, (size_t)capacity * 4));
-  HTRY(grow_keep(ix->levels, 0, (size_t)capacity * 4));
+  if (int rc = grow_rows(ix, capacity)) return rc;
   if (ix->keyed) {
-    HTRY(grow_keep(ix->ids, (size_t)n * 8, (size_t)capacity * 8));
     if (ix->key_n >= 0) HTRY(grow_keep(ix->key_table, (size_t)ix->key_n * 8, (size_t)capacity * 8));
     HTRY(ix->key_next.reserve((size_t)capacity * 8));
   }
-  ix->cap = capacity;
   return HNSW_OK;
 } ABI_CATCH
 
