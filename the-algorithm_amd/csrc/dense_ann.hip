@@ -45,6 +45,7 @@
 #include "../../include/dense_ann.h"
 #include "sann_device.h"  // mix64
 #include "abi_guard.h"
+#include "ann_by_id_internal.h"
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, DANN_ENOMEM, DANN_EINTERNAL); }
 
 namespace {
@@ -761,6 +762,10 @@ struct dann_index {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float t_a = 0, t_b = 0, t_sel = 0;
   int last_rounds = 0;  // passes B of the last search (1 unless a query overflowed its buffer or, in exact mode, failed its proof)
+  // by-id queries (ann_by_id.hip): (id, position) sorted by id, built when a query by the index's own ids finds kp_n != n
+  Buf kp_keys, kp_pos;
+  int64_t kp_n = -1;
+  std::shared_ptr<void> by_id;  // their scratch, freed with the index
   ~dann_index() {
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -1008,10 +1013,15 @@ int dann_search(dann_index_t *ix, int32_t nq, const float *queries, int32_t k, f
   return DANN_OK;
 } ABI_CATCH
 
-static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int32_t k, float *out_dist, int64_t *out_ids,
-                        int32_t *out_counts) {
-  DTRY(hipSetDevice(ix->device));
-  const int S = ix->S, d = ix->d;
+// Geometry of one chunk's search: derived from (index, nq, k) alone, so the halves below agree on it.
+struct ChunkGeom {
+  int nqb, nq_pad;
+  int64_t wg_vecs, pitch;
+  uint32_t n_wg, n_full, n_swg;
+  bool l2, tail;
+};
+static ChunkGeom chunk_geometry(const dann_index_t *ix, int32_t nq, int32_t k) {
+  ChunkGeom g;
   const int nqb = (nq + 31) / 32, nq_pad = nqb * 32;
   const int64_t wg_vecs = (int64_t)W2 * ix->VB * 32;
   const uint32_t n_wg = (uint32_t)(ix->n_pad / wg_vecs);
@@ -1036,6 +1046,26 @@ static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int3
   }
   const int64_t pitch = (int64_t)n_swg * TILE_MAXIMA;
 
+  g.nqb = nqb;
+  g.nq_pad = nq_pad;
+  g.wg_vecs = wg_vecs;
+  g.pitch = pitch;
+  g.n_wg = n_wg;
+  g.n_full = n_full;
+  g.n_swg = n_swg;
+  g.l2 = l2;
+  g.tail = tail;
+  return g;
+}
+
+// First half, shared: room for one chunk's buffers, and the ones a search expects reset.  The caller then prepares the queries
+// into qf / qsumsq (and q_in, which the exact mode's second scoring reads).
+static int chunk_open(dann_index_t *ix, int32_t nq, int32_t k) {
+  DTRY(hipSetDevice(ix->device));
+  const int S = ix->S, d = ix->d;
+  const ChunkGeom g = chunk_geometry(ix, nq, k);
+  const int nq_pad = g.nq_pad;
+  const int64_t pitch = g.pitch;
   DTRY(ix->q_in.reserve((size_t)nq * d * sizeof(float)));
   DTRY(ix->qf.reserve((size_t)nq_pad * S * 16 * sizeof(_Float16)));
   DTRY(ix->qsumsq.reserve((size_t)nq_pad * sizeof(float)));
@@ -1051,14 +1081,23 @@ static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int3
   DTRY(ix->o_cnt.reserve((size_t)nq * sizeof(int32_t)));
 
   hipStream_t st = 0;
-  DTRY(hipMemcpyAsync(ix->q_in.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
   DTRY(hipMemsetAsync(ix->qf.p, 0, (size_t)nq_pad * S * 16 * sizeof(_Float16), st));
   DTRY(hipMemsetAsync(ix->status.p, 0, (size_t)nq_pad * sizeof(int), st));
   DTRY(hipMemsetAsync(ix->done_cnt.p, 0xff, (size_t)nq_pad * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, ix->q_in.as<float>(), (int64_t)nq, d,
-                     S, ix->metric == DANN_METRIC_COSINE ? 1 : 0, (int64_t)0, ix->qf.as<_Float16>(), ix->qsumsq.as<float>());
-  DTRY(hipGetLastError());
+  return DANN_OK;
+}
 
+// Second half, shared by dann_search and the by-id query (ann_by_id.hip): the GEMM passes, the re-arm rounds and the selection
+// over the prepared queries of the chunk, into the given device outputs.  Ends synchronised.  d2h: the control bytes read back.
+static int chunk_search_prepared(dann_index_t *ix, int32_t nq, int32_t k, float *o_dist, int64_t *o_ids, int32_t *o_cnt,
+                                 int64_t *d2h) {
+  const int S = ix->S, d = ix->d;
+  const ChunkGeom g = chunk_geometry(ix, nq, k);
+  const int nqb = g.nqb, nq_pad = g.nq_pad;
+  const int64_t pitch = g.pitch;
+  const uint32_t n_full = g.n_full, n_swg = g.n_swg;
+  const bool l2 = g.l2, tail = g.tail;
+  hipStream_t st = 0;
   GemmArgs a;
   a.xf = ix->xf.as<_Float16>();
   a.bias = ix->bias.as<float>();
@@ -1111,6 +1150,7 @@ static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int3
                        d_tau_used);
     DTRY(hipGetLastError());
     DTRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    *d2h += (int64_t)sizeof(int);
     DTRY(hipStreamSynchronize(st));
     if (flags & 2) return fail(DANN_ELIMIT, "more than 8192 stored vectors tie at the k-th distance of a query");
     if (round >= 16) return fail(DANN_ELIMIT, "threshold refinement did not converge");
@@ -1132,6 +1172,7 @@ static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int3
                        ix->status.as<int>(), ix->flags.as<int>());
     DTRY(hipGetLastError());
     DTRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    *d2h += (int64_t)sizeof(int);
     DTRY(hipStreamSynchronize(st));
     if (!(flags & 1)) {  // every query proven
       ix->last_rounds = round + 1;
@@ -1144,16 +1185,32 @@ static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int3
   hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
                      ix->done_cnt.as<uint32_t>(), ix->qsumsq.as<float>(), ix->has_ids ? ix->ids.as<int64_t>() : nullptr,
                      ix->id_order ? nullptr : ix->rank.as<uint32_t>(), ix->id_order ? nullptr : ix->rpos.as<uint32_t>(),
-                     ix->metric, k, ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
+                     ix->metric, k, o_dist, o_ids, o_cnt);
   DTRY(hipGetLastError());
   DTRY(hipEventRecord(ix->ev[3], st));
-  DTRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-  DTRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  DTRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   DTRY(hipStreamSynchronize(st));
   (void)hipEventElapsedTime(&ix->t_a, ix->ev[0], ix->ev[1]);
   (void)hipEventElapsedTime(&ix->t_b, ix->ev[1], ix->ev[2]);
   (void)hipEventElapsedTime(&ix->t_sel, ix->ev[2], ix->ev[3]);
+  return DANN_OK;
+}
+
+static int search_chunk(dann_index_t *ix, int32_t nq, const float *queries, int32_t k, float *out_dist, int64_t *out_ids,
+                        int32_t *out_counts) {
+  if (int rc = chunk_open(ix, nq, k)) return rc;
+  const int S = ix->S, d = ix->d;
+  hipStream_t st = 0;
+  DTRY(hipMemcpyAsync(ix->q_in.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, ix->q_in.as<float>(), (int64_t)nq, d,
+                     S, ix->metric == DANN_METRIC_COSINE ? 1 : 0, (int64_t)0, ix->qf.as<_Float16>(), ix->qsumsq.as<float>());
+  DTRY(hipGetLastError());
+
+  int64_t d2h = 0;
+  if (int rc = chunk_search_prepared(ix, nq, k, ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>(), &d2h)) return rc;
+  DTRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  DTRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DTRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  DTRY(hipStreamSynchronize(st));
   return DANN_OK;
 }
 
@@ -1305,3 +1362,73 @@ int dann_compose_shards(int32_t n_shards, int32_t nq, int32_t k_in, const int64_
 } ABI_CATCH
 
 }  // extern "C"
+
+// ---- the seam of the by-id queries (ann_by_id_internal.h) ----
+namespace {
+__global__ void kp_iota_kernel(int64_t *__restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = i;
+}
+
+// the (id, position) table of an index with ids, sorted by id: (re)built at first use and after an append
+int ensure_key_positions(dann_index *ix) {
+  if (ix->kp_n == ix->n) return DANN_OK;
+  ix->kp_n = -1;
+  const int64_t n = ix->n;
+  size_t tb = 0;
+  DTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const int64_t *)nullptr,
+                                          (int64_t *)nullptr, (int)n, 0, 64, (hipStream_t)0));
+  Buf tmp, iota;
+  DTRY(tmp.reserve(tb));
+  DTRY(iota.reserve((size_t)n * 8));
+  DTRY(ix->kp_keys.reserve((size_t)n * 8));
+  DTRY(ix->kp_pos.reserve((size_t)n * 8));
+  hipLaunchKernelGGL(kp_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, iota.as<int64_t>(), n);
+  DTRY(hipGetLastError());
+  DTRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, ix->ids.as<int64_t>(), ix->kp_keys.as<int64_t>(), iota.as<int64_t>(),
+                                          ix->kp_pos.as<int64_t>(), (int)n, 0, 64, (hipStream_t)0));
+  DTRY(hipDeviceSynchronize());  // (before tmp and iota are freed)
+  ix->kp_n = n;
+  return DANN_OK;
+}
+}  // namespace
+
+namespace ann_by_id {
+
+int dann_open(dann_index *ix, int32_t k, bool own_keys, DannTarget *out) {
+  if (!ix || !out) return fail(DANN_EINVAL, "null argument");
+  if (k < 1 || k > MAX_K) return fail(DANN_EINVAL, "k must be in 1..1024");
+  DTRY(hipSetDevice(ix->device));
+  const bool table = own_keys && ix->has_ids;
+  if (table)
+    if (int rc = ensure_key_positions(ix)) return rc;
+  out->device = ix->device;
+  out->metric = ix->metric;
+  out->d = ix->d;
+  out->S = ix->S;
+  out->n = ix->n;
+  out->exact = ix->exact;
+  out->xf = ix->xf.as<_Float16>();
+  out->kp_keys = table ? ix->kp_keys.as<int64_t>() : nullptr;
+  out->kp_pos = table ? ix->kp_pos.as<int64_t>() : nullptr;
+  out->kp_n = table ? ix->kp_n : 0;
+  return DANN_OK;
+}
+
+int dann_chunk_open(dann_index *ix, int32_t nq, int32_t k, DannChunk *out) {
+  static_assert(DANN_CHUNK == MAX_NQ, "the by-id query chunks as dann_search does");
+  if (int rc = chunk_open(ix, nq, k)) return rc;
+  out->qf = ix->qf.as<_Float16>();
+  out->qsumsq = ix->qsumsq.as<float>();
+  out->q_in = ix->q_in.as<float>();
+  return DANN_OK;
+}
+
+int dann_chunk_search_prepared(dann_index *ix, int32_t nq, int32_t k, float *o_dist, int64_t *o_ids, int32_t *o_cnt,
+                               int64_t *d2h_bytes) {
+  return chunk_search_prepared(ix, nq, k, o_dist, o_ids, o_cnt, d2h_bytes);
+}
+
+std::shared_ptr<void> &dann_scratch(dann_index *ix) { return ix->by_id; }
+
+}  // namespace ann_by_id

@@ -44,6 +44,7 @@
 #include "../../include/hnsw_ann.h"
 #include "sann_device.h"  // mix64
 #include "abi_guard.h"
+#include "ann_by_id_internal.h"
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, HNSW_ENOMEM, HNSW_EINTERNAL); }
 
 namespace {
@@ -1333,6 +1334,7 @@ struct hnsw_index {
   int64_t kp_n = -1;
   Buf u_pos, u_fmask, u_top, u_pair_off, u_prop_off, u_props, u_pkeys, u_psorted, u_own, u_rows;
   int64_t upd_rounds = 0, upd_relinks = 0, upd_superseded = 0, upd_present = 0, upd_evals = 0, upd_empty = 0;  // the last update
+  std::shared_ptr<void> by_id;  // scratch of the by-id queries (ann_by_id.hip), freed with the index
   ~hnsw_index() {
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -2222,27 +2224,33 @@ int hnsw_index_append_levels(hnsw_index_t *ix, int64_t n, const float *vectors, 
 // device, absent ones appended afterwards by append_impl.  See include/hnsw_ann.h for the semantics.
 
 // positions of the requested keys of a keyed index (-1: absent), by the device's (key, position) table
+// the device's (key, position) table of a keyed index, sorted by key: (re)built at first use and after an append
+static int ensure_key_positions(hnsw_index *ix) {
+  const int64_t n_old = ix->n;
+  if (ix->kp_n == n_old) return HNSW_OK;
+  ix->kp_n = -1;
+  size_t tb = 0;
+  HTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const int64_t *)nullptr,
+                                          (int64_t *)nullptr, (int)n_old, 0, 64, (hipStream_t)0));
+  Buf tmp, iota;  // (the sort's scratch and the positions it permutes live only for the sort)
+  HTRY(tmp.reserve(tb));
+  HTRY(iota.reserve((size_t)n_old * 8));
+  HTRY(ix->kp_keys.reserve((size_t)n_old * 8));
+  HTRY(ix->kp_pos.reserve((size_t)n_old * 8));
+  hipLaunchKernelGGL(hnsw_iota_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, 0, iota.as<int64_t>(), n_old);
+  HTRY(hipGetLastError());
+  HTRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, ix->ids.as<int64_t>(), ix->kp_keys.as<int64_t>(), iota.as<int64_t>(),
+                                          ix->kp_pos.as<int64_t>(), (int)n_old, 0, 64, (hipStream_t)0));
+  HTRY(hipDeviceSynchronize());  // (before tmp and iota are freed)
+  ix->kp_n = n_old;
+  return HNSW_OK;
+}
+
 static int update_positions(hnsw_index *ix, int64_t n, const int64_t *ids, std::vector<int64_t> &pos) {
   const int64_t n_old = ix->n;
   pos.assign((size_t)n, -1);
   if (n_old == 0 || !ix->has_ids) return HNSW_OK;
-  if (ix->kp_n != n_old) {  // (re)built after the first update and after an append
-    ix->kp_n = -1;
-    size_t tb = 0;
-    HTRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const int64_t *)nullptr,
-                                            (int64_t *)nullptr, (int)n_old, 0, 64, (hipStream_t)0));
-    Buf tmp, iota;  // (the sort's scratch and the positions it permutes live only for the sort)
-    HTRY(tmp.reserve(tb));
-    HTRY(iota.reserve((size_t)n_old * 8));
-    HTRY(ix->kp_keys.reserve((size_t)n_old * 8));
-    HTRY(ix->kp_pos.reserve((size_t)n_old * 8));
-    hipLaunchKernelGGL(hnsw_iota_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, 0, iota.as<int64_t>(), n_old);
-    HTRY(hipGetLastError());
-    HTRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, ix->ids.as<int64_t>(), ix->kp_keys.as<int64_t>(), iota.as<int64_t>(),
-                                            ix->kp_pos.as<int64_t>(), (int)n_old, 0, 64, (hipStream_t)0));
-    HTRY(hipDeviceSynchronize());  // (before tmp and iota are freed)
-    ix->kp_n = n_old;
-  }
+  if (int rc = ensure_key_positions(ix)) return rc;
   HTRY(ix->kp_q.reserve((size_t)n * 8));
   HTRY(ix->kp_out.reserve((size_t)n * 8));
   HTRY(hipMemcpy(ix->kp_q.p, ids, (size_t)n * 8, hipMemcpyHostToDevice));
@@ -2562,21 +2570,11 @@ int hnsw_index_destroy(hnsw_index_t *ix) try {
   return HNSW_OK;
 } ABI_CATCH
 
-int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t ef, float *out_dist, int64_t *out_ids,
-                int32_t *out_counts) try {
-  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(HNSW_EINVAL, "NULL argument");
-  if (nq < 1) return fail(HNSW_EINVAL, "nq must be positive");
-  if (k < 1 || ef < 1) return fail(HNSW_EINVAL, "k and ef must be positive");
-  const int beam = std::max(ef, k);  // HnswIndex.java:545
-  if (beam > MAX_EF) return fail(HNSW_ELIMIT, "max(ef, k) above 1024");
-  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
-  ix->last_dist = ix->last_exp = 0;
-  ix->last_spilled = 0;
-  ix->last_ms = 0;
-  if (ix->entry < 0) {  // metadata.getEntryPoint() absent: Collections.emptyList() (:550-552)
-    for (int32_t q = 0; q < nq; ++q) out_counts[q] = 0;
-    return HNSW_OK;
-  }
+// The second half of a search: the walks over the first nq rows of the prepared-query buffer ix->q (fp16 [nq][dpad]), the second
+// pass for the queries that outgrow their queues included.  Ends synchronised with the answers in o_dist / o_ids / o_cnt on
+// the device.  hnsw_search and the by-id query (ann_by_id.hip) share it.  h2d / d2h: the control bytes it moved.
+static int search_prepared(hnsw_index *ix, int32_t nq, int32_t k, int beam, int64_t *h2d, int64_t *d2h) {
+  *h2d = *d2h = 0;
   HTRY(hipSetDevice(ix->device));
   const int64_t vwords = (ix->n + 31) / 32;
   // concurrent queries per launch: bounded by the visited bitmaps -- n bits per query, up to 48 GiB of the 288 (at 50M
@@ -2584,8 +2582,6 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
   // and a 4096-query batch took twelve launches: profiles/r03_hnsw_bench_50M_*)
   int64_t per_launch = std::min<int64_t>(nq, std::max<int64_t>(64, (int64_t)(48ull << 30) / (vwords * 4)));
   per_launch = std::min<int64_t>(per_launch, 1 << 16);
-  HTRY(ix->q_in.reserve((size_t)nq * ix->d * 4));
-  HTRY(ix->q.reserve((size_t)nq * ix->dpad * sizeof(_Float16)));
   {
     const void *before = ix->visited.p;
     HTRY(ix->visited.reserve((size_t)per_launch * vwords * 4));
@@ -2599,10 +2595,6 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
   HTRY(ix->spill.reserve((size_t)nq * 4));
   HTRY(ix->stats.reserve(128));
   hipStream_t st = 0;
-  HTRY(hipMemcpyAsync(ix->q_in.p, queries, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(hnsw_prep_rows, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, ix->q_in.as<float>(), (int64_t)nq, ix->d,
-                     ix->dpad, ix->metric == HNSW_METRIC_COSINE ? 1 : 0, ix->q.as<_Float16>());
-  HTRY(hipGetLastError());
   HTRY(hipMemsetAsync(ix->stats.p, 0, 128, st));
   HTRY(hipMemsetAsync(ix->spill.p, 0, (size_t)nq * 4, st));
 
@@ -2661,6 +2653,7 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
     if (!first) {
       HTRY(ix->qlist.reserve(redo.size() * 4));
       HTRY(hipMemcpyAsync(ix->qlist.p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, st));
+      *h2d += (int64_t)redo.size() * 4;
     }
     for (int64_t r0 = 0; r0 < todo; r0 += batch) {
       const int64_t m = std::min<int64_t>(batch, todo - r0);
@@ -2685,6 +2678,7 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
       HTRY(hipGetLastError());
     }
     HTRY(hipMemcpyAsync(spill.data(), ix->spill.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    *d2h += (int64_t)nq * 4;
     HTRY(hipStreamSynchronize(st));
     std::vector<int32_t> still;
     if (first) {
@@ -2701,9 +2695,7 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
   HTRY(hipEventRecord(ix->ev[1], st));
   unsigned long long stats[16] = {0};
   HTRY(hipMemcpyAsync(stats, ix->stats.p, 128, hipMemcpyDeviceToHost, st));
-  HTRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-  HTRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
-  HTRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  *d2h += 128;
   HTRY(hipStreamSynchronize(st));
   ix->visited_dirty = !use_vlog;
   ix->last_dist = (int64_t)stats[0];
@@ -2711,6 +2703,38 @@ int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, i
   ix->last_peak = (int64_t)stats[2];
   ix->last_adm = (int64_t)stats[3];
   (void)hipEventElapsedTime(&ix->last_ms, ix->ev[0], ix->ev[1]);
+  return HNSW_OK;
+}
+
+int hnsw_search(hnsw_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t ef, float *out_dist, int64_t *out_ids,
+                int32_t *out_counts) try {
+  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(HNSW_EINVAL, "NULL argument");
+  if (nq < 1) return fail(HNSW_EINVAL, "nq must be positive");
+  if (k < 1 || ef < 1) return fail(HNSW_EINVAL, "k and ef must be positive");
+  const int beam = std::max(ef, k);  // HnswIndex.java:545
+  if (beam > MAX_EF) return fail(HNSW_ELIMIT, "max(ef, k) above 1024");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
+  ix->last_dist = ix->last_exp = 0;
+  ix->last_spilled = 0;
+  ix->last_ms = 0;
+  if (ix->entry < 0) {  // metadata.getEntryPoint() absent: Collections.emptyList() (:550-552)
+    for (int32_t q = 0; q < nq; ++q) out_counts[q] = 0;
+    return HNSW_OK;
+  }
+  HTRY(hipSetDevice(ix->device));
+  HTRY(ix->q_in.reserve((size_t)nq * ix->d * 4));
+  HTRY(ix->q.reserve((size_t)nq * ix->dpad * sizeof(_Float16)));
+  hipStream_t st = 0;
+  HTRY(hipMemcpyAsync(ix->q_in.p, queries, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(hnsw_prep_rows, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, ix->q_in.as<float>(), (int64_t)nq, ix->d,
+                     ix->dpad, ix->metric == HNSW_METRIC_COSINE ? 1 : 0, ix->q.as<_Float16>());
+  HTRY(hipGetLastError());
+  int64_t h2d = 0, d2h = 0;
+  if (int rc = search_prepared(ix, nq, k, beam, &h2d, &d2h)) return rc;
+  HTRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+  HTRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+  HTRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HTRY(hipStreamSynchronize(st));
   return HNSW_OK;
 } ABI_CATCH
 
@@ -2732,3 +2756,46 @@ int hnsw_last_walk_counters(const hnsw_index_t *ix, int64_t *admissions, int64_t
 } ABI_CATCH
 
 }  // extern "C"
+
+
+// ---- the seam of the by-id queries (ann_by_id_internal.h) ----
+namespace ann_by_id {
+
+int hnsw_open(hnsw_index *ix, int32_t nq_cap, int32_t k, int32_t ef, bool own_keys, HnswTarget *out) {
+  if (!ix || !out) return fail(HNSW_EINVAL, "NULL argument");
+  if (k < 1 || ef < 1) return fail(HNSW_EINVAL, "k and ef must be positive");
+  if (std::max(ef, k) > MAX_EF) return fail(HNSW_ELIMIT, "max(ef, k) above 1024");
+  if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
+  HTRY(hipSetDevice(ix->device));
+  HTRY(ix->q.reserve((size_t)std::max(nq_cap, 1) * ix->dpad * sizeof(_Float16)));
+  if (own_keys && ix->has_ids && ix->n > 0)
+    if (int rc = ensure_key_positions(ix)) return rc;
+  out->device = ix->device;
+  out->metric = ix->metric;
+  out->d = ix->d;
+  out->dpad = ix->dpad;
+  out->n = ix->n;
+  out->empty = ix->entry < 0;
+  out->q = ix->q.as<_Float16>();
+  out->x = ix->x.as<_Float16>();
+  const bool table = own_keys && ix->has_ids && ix->n > 0;
+  out->kp_keys = table ? ix->kp_keys.as<int64_t>() : nullptr;
+  out->kp_pos = table ? ix->kp_pos.as<int64_t>() : nullptr;
+  out->kp_n = table ? ix->kp_n : 0;
+  return HNSW_OK;
+}
+
+int hnsw_search_prepared(hnsw_index *ix, int32_t nq, int32_t k, int32_t ef, DeviceResult *out) {
+  ix->last_dist = ix->last_exp = 0;
+  ix->last_spilled = 0;
+  ix->last_ms = 0;
+  if (int rc = search_prepared(ix, nq, k, std::max(ef, k), &out->h2d_bytes, &out->d2h_bytes)) return rc;
+  out->dist = ix->o_dist.as<float>();
+  out->ids = ix->o_ids.as<int64_t>();
+  out->counts = ix->o_cnt.as<int32_t>();
+  return HNSW_OK;
+}
+
+std::shared_ptr<void> &hnsw_scratch(hnsw_index *ix) { return ix->by_id; }
+
+}  // namespace ann_by_id

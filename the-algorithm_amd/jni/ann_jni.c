@@ -18,6 +18,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/ann_by_id.h"
 #include "../../include/ann_codec.h"
 #include "../../include/dense_ann.h"
 #include "../../include/hnsw_ann.h"
@@ -234,4 +235,74 @@ JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_composeShards(JNIEnv *env
   if (dann_compose_shards(nShards, nq, kIn, (const int64_t *)BUF(ids), (const float *)BUF(distances), (const int32_t *)BUF(counts), k,
                           (int64_t *)BUF(outIds), (float *)BUF(outDistances), (int32_t *)BUF(outCounts)) != DANN_OK)
     throw_runtime(env, dann_last_error());
+}
+
+/* ---- query by id (include/ann_by_id.h: QueryableByIdImplementation.scala:15-91) ---------------------------------------- */
+/* long embeddingStoreBuild(int device, long n, int d, ByteBuffer keys /+ long[n] +/, ByteBuffer vectors /+ float[n][d] +/)
+ * the EmbeddingProducer of the by-id queries, resident on the device; a repeated key is the RuntimeException */
+JNIEXPORT jlong JNICALL Java_com_twitter_ann_gpu_AnnJni_embeddingStoreBuild(JNIEnv *env, jclass cls, jint device, jlong n, jint d, jobject keys,
+                                                                            jobject vectors) {
+  (void)cls;
+  if (n < 0 || d < 1 || (n > 0 && (!keys || !vectors || CAP(keys) / 8 < n || CAP(vectors) / 4 / d < n))) {
+    throw_runtime(env, "keys must hold n longs and vectors n x d floats");
+    return 0;
+  }
+  ann_store_t *st = NULL;
+  if (ann_store_build(device, n, d, (const int64_t *)BUF(keys), (const float *)BUF(vectors), &st) != ANN_BY_ID_OK) {
+    throw_runtime(env, ann_by_id_last_error());
+    return 0;
+  }
+  return (jlong)(intptr_t)st;
+}
+JNIEXPORT void JNICALL Java_com_twitter_ann_gpu_AnnJni_embeddingStoreDestroy(JNIEnv *env, jclass cls, jlong store) {
+  (void)env;
+  (void)cls;
+  ann_store_destroy((ann_store_t *)(intptr_t)store);
+}
+/* the capacities of a by-id call: seeds long[nSeeds], outSeeds / outIds long[cap], outDistances float[cap], outCounts int[nSeeds] */
+static int by_id_buffers_ok(JNIEnv *env, jlong index, jint nSeeds, jobject seeds, jint k, jobject outSeeds, jobject outIds,
+                            jobject outDistances, jlong cap, jobject outCounts) {
+  if (!index || nSeeds < 0 || k < 1 || cap < 0 || (nSeeds > 0 && (!seeds || !outCounts)) || (cap > 0 && (!outSeeds || !outIds || !outDistances))) {
+    throw_runtime(env, "index, nSeeds >= 0, k >= 1, cap >= 0 and the direct buffers they need");
+    return 0;
+  }
+  if (CAP(seeds) / 8 < nSeeds || CAP(outCounts) / 4 < nSeeds || CAP(outSeeds) / 8 < cap || CAP(outIds) / 8 < cap || CAP(outDistances) / 4 < cap) {
+    throw_runtime(env, "a direct buffer is smaller than nSeeds (cap) entries");
+    return 0;
+  }
+  return 1;
+}
+/* long hnswBatchQueryById(long index, long store /+ 0: the index's own keys and rows +/, int nSeeds, ByteBuffer seeds, int k, int ef,
+ *                         ByteBuffer outSeeds, ByteBuffer outIds, ByteBuffer outDistances, long cap, ByteBuffer outCounts)
+ * = QueryableById.batchQueryWithDistanceById: returns the number of (seed, neighbour, distance) triples written, in seed order;
+ * outCounts[i] = -1 for a seed the store does not hold */
+JNIEXPORT jlong JNICALL Java_com_twitter_ann_gpu_AnnJni_hnswBatchQueryById(JNIEnv *env, jclass cls, jlong index, jlong store, jint nSeeds,
+                                                                           jobject seeds, jint k, jint ef, jobject outSeeds, jobject outIds,
+                                                                           jobject outDistances, jlong cap, jobject outCounts) {
+  (void)cls;
+  if (!by_id_buffers_ok(env, index, nSeeds, seeds, k, outSeeds, outIds, outDistances, cap, outCounts)) return 0;
+  int64_t total = 0;
+  if (hnsw_batch_query_by_id((hnsw_index_t *)(intptr_t)index, (const ann_store_t *)(intptr_t)store, nSeeds, (const int64_t *)BUF(seeds), k, ef,
+                             (int64_t *)BUF(outSeeds), (int64_t *)BUF(outIds), (float *)BUF(outDistances), cap, &total,
+                             (int32_t *)BUF(outCounts)) != ANN_BY_ID_OK) {
+    throw_runtime(env, ann_by_id_last_error());
+    return 0;
+  }
+  return (jlong)total;
+}
+/* long denseBatchQueryById(long index, long store, int nSeeds, ByteBuffer seeds, int k, ByteBuffer outSeeds, ByteBuffer outIds,
+ *                          ByteBuffer outDistances, long cap, ByteBuffer outCounts)     the same on the exhaustive index */
+JNIEXPORT jlong JNICALL Java_com_twitter_ann_gpu_AnnJni_denseBatchQueryById(JNIEnv *env, jclass cls, jlong index, jlong store, jint nSeeds,
+                                                                            jobject seeds, jint k, jobject outSeeds, jobject outIds,
+                                                                            jobject outDistances, jlong cap, jobject outCounts) {
+  (void)cls;
+  if (!by_id_buffers_ok(env, index, nSeeds, seeds, k, outSeeds, outIds, outDistances, cap, outCounts)) return 0;
+  int64_t total = 0;
+  if (dann_batch_query_by_id((dann_index_t *)(intptr_t)index, (const ann_store_t *)(intptr_t)store, nSeeds, (const int64_t *)BUF(seeds), k,
+                             (int64_t *)BUF(outSeeds), (int64_t *)BUF(outIds), (float *)BUF(outDistances), cap, &total,
+                             (int32_t *)BUF(outCounts)) != ANN_BY_ID_OK) {
+    throw_runtime(env, ann_by_id_last_error());
+    return 0;
+  }
+  return (jlong)total;
 }

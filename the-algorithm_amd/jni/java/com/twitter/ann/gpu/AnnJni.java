@@ -61,4 +61,24 @@ public final class AnnJni {
   /** Hnsw.queryWithDistance for nq queries (HnswParams.ef; Hnsw.scala:125-147). */
   public static native void hnswSearch(long index, int nq, int d, ByteBuffer x, int k, int ef, ByteBuffer distances, ByteBuffer labels,
                                        ByteBuffer counts);
+
+  /**
+   * The EmbeddingProducer of the by-id queries (EmbeddingProducer.scala), resident on the device: keys long[n] (unique; a repeated key
+   * is the RuntimeException), vectors float[n][d] kept as fp32. Immutable; may serve several indexes.
+   */
+  public static native long embeddingStoreBuild(int device, long n, int d, ByteBuffer keys, ByteBuffer vectors);
+
+  public static native void embeddingStoreDestroy(long store);
+
+  /**
+   * QueryableById.batchQueryWithDistanceById (QueryableByIdImplementation.scala:69-90) on an HNSW index: seeds long[nSeeds] in; the
+   * triples (outSeeds, outIds, outDistances)[cap] in seed order and outCounts int[nSeeds] (-1: the store has no such key) out; returns
+   * the number of triples. store = 0: the index's own keys and rows are the producer. cap must be at least (found seeds) x k.
+   */
+  public static native long hnswBatchQueryById(long index, long store, int nSeeds, ByteBuffer seeds, int k, int ef, ByteBuffer outSeeds,
+                                               ByteBuffer outIds, ByteBuffer outDistances, long cap, ByteBuffer outCounts);
+
+  /** The same on the exhaustive index (no runtime params). */
+  public static native long denseBatchQueryById(long index, long store, int nSeeds, ByteBuffer seeds, int k, ByteBuffer outSeeds,
+                                                ByteBuffer outIds, ByteBuffer outDistances, long cap, ByteBuffer outCounts);
 }
