@@ -61,5 +61,8 @@ int dann_chunk_open(dann_index *ix, int32_t nq, int32_t k, DannChunk *out);
 int dann_chunk_search_prepared(dann_index *ix, int32_t nq, int32_t k, float *o_dist, int64_t *o_ids, int32_t *o_cnt,
                                int64_t *d2h_bytes);
 std::shared_ptr<void> &dann_scratch(dann_index *ix);
+// dann_index_build without ids from rows that are on the device already (row-major fp32 [n][d]): the coarse quantizer of
+// ivf_ann.hip rebuilds its centroid index this way in every k-means round.  Free with dann_index_destroy.
+int dann_build_device(int32_t device, int32_t metric, int64_t n, int32_t d, const float *d_rows, dann_index **out);
 
 }  // namespace ann_by_id

@@ -1,0 +1,1020 @@
+// ivf_ann.hip -- inverted-file index with flat lists (`IVF<nlist>,Flat` in an id map) on the gfx950 matrix cores.
+//
+// What it replaces: the reference's Faiss queryable (ann/src/main/scala/com/twitter/ann/faiss/FaissIndexer.scala:82-92:
+// index_factory -> train -> add_with_ids; QueryableIndexAdapter.scala:139-178: search with FaissRuntimeParam.nprobe),
+// restricted to the coarse quantizer, its training, the inverted lists and the probed scan (include/ivf_ann.h).
+//
+// Shape of the computation.
+//   * The coarse quantizer is the exhaustive search of dense_ann.hip over the centroids: the handle keeps them as a
+//     dann_index and calls the prepared-search seam of ann_by_id_internal.h with k = nprobe (search) or k = 1 (add and
+//     every k-means round).  There is no second GEMM here.
+//   * The rows are kept twice: row-major fp16 in the order they were added (what an add re-lays the lists out from, and
+//     what training sums), and in the lists -- one contiguous buffer in which every list starts on a 32-row block and
+//     is stored in MFMA A-fragment order ([block][k-step][lane][8 halves], lane (r, h) holding x[r][16s + 8h .. +8]),
+//     in (cell, id) order, beside a per-slot bias (0, -|x|^2/2 for L2, -inf for the padding of a list's last block) and
+//     the slot's rank in id order.
+//   * A search inverts its [nq][nprobe] probe table on the device: the (cell, query) pairs are sorted by cell and cut
+//     into groups of <= 32 queries.  One workgroup per group: the group's queries are gathered once into LDS as the B
+//     operand, the four waves stride over the cell's blocks, each block one coalesced 1-KiB load per k-step and one
+//     v_mfma_f32_32x32x16_f16, fp32 accumulation started from the bias.  C has the query on the lane and 16 rows in
+//     the accumulator registers, so the threshold test is register-local.  A cell's rows are read once per group of
+//     queries that probe it, not once per query.
+//   * Candidates go to a per-query survivor buffer (CAP = 8192) by one integer atomic per (lane, block) that reserves
+//     as many slots as the lane has candidates.  Round 0 runs with threshold -inf: a query whose probed lists hold
+//     <= CAP rows has all of them and is finished.  A query that overflowed takes the k-th largest of the CAP scores
+//     it did buffer as its threshold -- a lower bound of its k-th best score, k distinct rows reach it -- and only its
+//     groups are scanned again (fallback round, counted in ivf_last_stats); every row at or above the threshold is
+//     emitted then, so the k best are among the survivors whatever order the workgroups appended in.
+//   * Select sorts a query's survivors by (score desc, rank in id order asc): the order of dense_ann.hip's select.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#include "../../include/dense_ann.h"
+#include "../../include/ivf_ann.h"
+#include "sann_device.h"  // mix64
+#include "abi_guard.h"
+#include "ann_by_id_internal.h"
+#define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
+
+namespace {
+
+thread_local std::string g_err;
+int fail(int code, const std::string &m) {
+  g_err = m;
+  return code;
+}
+#define ITRY(expr)                                                                                \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) return fail(IVF_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+// a call into dense_ann.hip: its status codes carry the same numbers, its message is in dann_last_error()
+#define DCALL(expr)                                              \
+  do {                                                           \
+    int rc_ = (expr);                                            \
+    if (rc_) return fail(rc_, std::string("coarse quantizer: ") + dann_last_error()); \
+  } while (0)
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float float16v __attribute__((ext_vector_type(16)));
+
+constexpr int CAP = 8192;  // survivors kept per query
+constexpr int MAX_K = 1024;
+constexpr int MAX_D = 512;
+constexpr int MAX_NLIST = 65536;
+constexpr int MAX_NPROBE = 1024;
+constexpr int CHUNK = ann_by_id::DANN_CHUNK;  // queries (or rows to assign) per coarse search
+constexpr int CELL_BITS = 17;                 // radix-sort key width of a cell number
+
+struct Survivor {
+  float score;
+  uint32_t slot;
+};
+struct Group {
+  uint32_t cell, p0, count;  // the queries of the group: pairs [p0, p0 + count) of the probe table sorted by cell
+};
+
+__device__ __forceinline__ uint32_t f2key(float f) {  // order-preserving float -> uint
+  uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key2f(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// rows (fp32, row-major) -> fp16 rows (row-major) and the sum of squares of the stored halves.  One wave per row; the
+// arithmetic of dense_ann.hip's prep_rows_kernel (Cosine: divide by the fp32 norm, then round).
+// ---------------------------------------------------------------------------------------------
+__global__ void store_rows_kernel(const float *__restrict__ src, int64_t n, int d, int normalise, _Float16 *__restrict__ flat,
+                                  float *__restrict__ sumsq) {
+  int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const float *x = src + row * d;
+  double ss = 0;
+  for (int k = lane; k < d; k += 64) ss += (double)x[k] * (double)x[k];
+  ss = wave_sum(ss);
+  float norm = 1.0f;
+  if (normalise) {
+    norm = (float)sqrt(ss);
+    if (!(norm > 0.0f)) norm = 1.0f;
+  }
+  double ss16 = 0;
+  for (int k = lane; k < d; k += 64) {
+    _Float16 hv = (_Float16)(x[k] / norm);
+    float back = (float)hv;
+    ss16 += (double)back * (double)back;
+    flat[row * d + k] = hv;
+  }
+  ss16 = wave_sum(ss16);
+  if (lane == 0) sumsq[row] = (float)ss16;
+}
+
+// fp16 rows -> the B-operand fragments of a query chunk: the coarse search's (S_c k-steps, zeroed by dann_chunk_open) and,
+// with own != NULL, the scan's (S = d / 16).  One thread per (row, 8-half piece).
+__global__ void frag_rows_kernel(const _Float16 *__restrict__ flat, const float *__restrict__ sumsq, int m, int d, int S_c,
+                                 _Float16 *__restrict__ qf_c, float *__restrict__ qsumsq, _Float16 *__restrict__ own) {
+  const int pieces = d >> 3;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)m * pieces) return;
+  const int row = (int)(e / pieces), c = (int)(e % pieces);
+  const half8 v = *(const half8 *)&flat[(size_t)row * d + c * 8];
+  const int g = row >> 5, r = row & 31, s = c >> 1, h = c & 1;
+  *(half8 *)&qf_c[((((size_t)g * S_c + s) * 64) + h * 32 + r) * 8] = v;
+  if (own) *(half8 *)&own[((((size_t)g * (d >> 4) + s) * 64) + h * 32 + r) * 8] = v;
+  if (c == 0) qsumsq[row] = sumsq[row];
+}
+
+__global__ void iota_kernel(uint32_t *__restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (uint32_t)i;
+}
+__global__ void iota64_kernel(int64_t *__restrict__ out, int64_t first, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = first + i;
+}
+// the coarse search's answer (k = 1) -> the cell of each row
+__global__ void cells_kernel(const int64_t *__restrict__ ids, int m, int32_t *__restrict__ cell) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) cell[i] = (int32_t)ids[i];
+}
+__global__ void gather_cells_kernel(const int32_t *__restrict__ cell, const uint32_t *__restrict__ perm, int64_t n,
+                                    uint32_t *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (uint32_t)cell[perm ? perm[i] : i];
+}
+__global__ void hist_kernel(const uint32_t *__restrict__ keys, int64_t n, uint32_t *__restrict__ hist) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) atomicAdd(&hist[keys[i]], 1u);
+}
+__global__ void blocks_of_kernel(const uint32_t *__restrict__ sizes, int n, uint32_t *__restrict__ nblk) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) nblk[i] = (sizes[i] + 31u) >> 5;
+}
+
+// ---------------------------------------------------------------------------------------------
+// list construction: row j of the (cell, id) order goes to its list's next slot, as an A fragment.  One wave per row.
+// ---------------------------------------------------------------------------------------------
+__global__ void scatter_rows_kernel(const _Float16 *__restrict__ flat, const float *__restrict__ sumsq, int64_t n, int d,
+                                    int metric, const uint32_t *__restrict__ cell_sorted, const uint32_t *__restrict__ ord,
+                                    const uint32_t *__restrict__ perm, const uint32_t *__restrict__ start,
+                                    const uint32_t *__restrict__ boff, _Float16 *__restrict__ lf, float *__restrict__ lbias,
+                                    uint32_t *__restrict__ lrank) {
+  const int64_t j = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (j >= n) return;
+  const uint32_t c = cell_sorted[j], rank = ord[j], src = perm[rank];
+  const size_t slot = (size_t)boff[c] * 32 + (size_t)(j - start[c]);
+  const size_t g = slot >> 5;
+  const int r = (int)(slot & 31), S = d >> 4;
+  for (int p = lane; p < (d >> 3); p += 64) {
+    const int s = p >> 1, h = p & 1;
+    *(half8 *)&lf[(((g * S + s) * 64) + h * 32 + r) * 8] = *(const half8 *)&flat[(size_t)src * d + p * 8];
+  }
+  if (lane == 0) {
+    lbias[slot] = metric == IVF_METRIC_L2 ? -0.5f * sumsq[src] : 0.0f;
+    lrank[slot] = rank;
+  }
+}
+__global__ void fill_kernel(float *__restrict__ p, int64_t n, float v) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k-means
+// ---------------------------------------------------------------------------------------------
+__global__ void pick_rows_kernel(const _Float16 *__restrict__ flat, const int64_t *__restrict__ picks, int nlist, int d,
+                                 float *__restrict__ cent) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)nlist * d) return;
+  cent[e] = (float)flat[(size_t)picks[e / d] * d + e % d];
+}
+// InnerProduct: the initial picks scaled to unit length, as every later centroid is.  One wave per centroid.
+__global__ void unit_rows_kernel(float *__restrict__ cent, int nlist, int d) {
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nlist) return;
+  float *x = cent + (size_t)row * d;
+  double ss = 0;
+  for (int k = lane; k < d; k += 64) ss += (double)x[k] * (double)x[k];
+  ss = wave_sum(ss);
+  if (!(ss > 0)) return;
+  const double scale = 1.0 / sqrt(ss);
+  for (int k = lane; k < d; k += 64) x[k] = (float)((double)x[k] * scale);
+}
+
+// One workgroup per cell: component k of the mean is summed by one thread over the cell's rows in position order, in
+// fp64 -- a fixed order, no floating-point atomics.  InnerProduct / Cosine: the mean is scaled to unit length, its
+// squared norm summed by one thread in component order.  A cell without rows keeps its centroid.
+__global__ __launch_bounds__(256) void mean_kernel(const _Float16 *__restrict__ flat, int d, int metric,
+                                                   const uint32_t *__restrict__ ord, const uint32_t *__restrict__ start,
+                                                   const uint32_t *__restrict__ sizes, float *__restrict__ cent) {
+  __shared__ double sq[MAX_D];
+  __shared__ double s_scale;
+  const uint32_t c = blockIdx.x, n = sizes[c], j0 = start[c];
+  if (n == 0) return;
+  double mean[MAX_D / 256];
+#pragma unroll
+  for (int u = 0; u < MAX_D / 256; ++u) {
+    const int k = threadIdx.x + u * 256;
+    double acc = 0;
+    if (k < d)
+      for (uint32_t j = 0; j < n; ++j) acc += (double)(float)flat[(size_t)ord[j0 + j] * d + k];
+    mean[u] = acc / (double)n;
+    if (k < d) sq[k] = mean[u] * mean[u];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double scale = 1.0;
+    if (metric != IVF_METRIC_L2) {
+      double ss = 0;
+      for (int k = 0; k < d; ++k) ss += sq[k];
+      if (ss > 0) scale = 1.0 / sqrt(ss);
+    }
+    s_scale = scale;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < MAX_D / 256; ++u) {
+    const int k = threadIdx.x + u * 256;
+    if (k < d) cent[(size_t)c * d + k] = (float)(mean[u] * s_scale);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// probe inversion
+// ---------------------------------------------------------------------------------------------
+// the coarse search's answer [m][nprobe] -> the probe export, the (cell, query) pairs and the number of queries per cell
+__global__ void probes_kernel(const int64_t *__restrict__ ids, int m, int nprobe, int32_t *__restrict__ probes,
+                              uint32_t *__restrict__ pair_cell, uint32_t *__restrict__ pair_q, uint32_t *__restrict__ per_cell) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)m * nprobe) return;
+  const uint32_t c = (uint32_t)ids[e];
+  probes[e] = (int32_t)c;
+  pair_cell[e] = c;
+  pair_q[e] = (uint32_t)(e / nprobe);
+  atomicAdd(&per_cell[c], 1u);
+}
+// one thread per cell: its groups of <= 32 queries, and its share of the rows scanned (integers: any order gives the sum)
+__global__ void groups_kernel(const uint32_t *__restrict__ per_cell, const uint32_t *__restrict__ pstart,
+                              const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ sizes, int nlist,
+                              Group *__restrict__ groups, unsigned long long *__restrict__ rows_scanned) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nlist) return;
+  const uint32_t cnt = per_cell[c];
+  if (cnt == 0) return;
+  for (uint32_t g = 0; g * 32 < cnt; ++g) groups[gstart[c] + g] = Group{(uint32_t)c, pstart[c] + g * 32, min(32u, cnt - g * 32)};
+  atomicAdd(rows_scanned, (unsigned long long)cnt * sizes[c]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the probed scan
+// ---------------------------------------------------------------------------------------------
+struct ScanArgs {
+  const _Float16 *lf;     // list fragments
+  const float *lbias;     // per slot
+  const uint32_t *boff;   // first block of a cell's list
+  const uint32_t *nblk;   // its blocks
+  const _Float16 *qf;     // query fragments of the chunk, S = d / 16
+  const Group *groups;
+  const uint32_t *pair_q; // queries of the pairs sorted by cell
+  const float *tau;       // [nq]: emit scores >= tau; +inf = the query is finished
+  uint32_t *cnt;          // [nq]
+  Survivor *surv;         // [nq][CAP]
+  int S;
+};
+
+__global__ __launch_bounds__(256) void scan_kernel(ScanArgs a) {
+  extern __shared__ half8 sq[];  // [S][64]: the group's queries as the B operand
+  __shared__ int s_q[32];
+  __shared__ float s_tau[32];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, S = a.S;
+  const Group g = a.groups[blockIdx.x];
+  if (t < 32) {
+    const int q = t < (int)g.count ? (int)a.pair_q[g.p0 + t] : -1;
+    s_q[t] = q;
+    s_tau[t] = q >= 0 ? a.tau[q] : INFINITY;
+  }
+  __syncthreads();
+  const int myq = s_q[lane & 31];
+  const float thr = s_tau[lane & 31];
+  if (!__syncthreads_or(thr < INFINITY)) return;  // a fallback round: every query of this group is finished
+  for (int i = t; i < S * 64; i += 256) {
+    const int s = i >> 6, l = i & 63, q = s_q[l & 31];
+    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (q >= 0) v = *(const half8 *)&a.qf[((((size_t)(q >> 5) * S + s) * 64) + (l >> 5) * 32 + (q & 31)) * 8];
+    sq[i] = v;
+  }
+  __syncthreads();
+  const uint32_t b0 = a.boff[g.cell], nb = a.nblk[g.cell];
+  for (uint32_t blk = w; blk < nb; blk += 4) {
+    const size_t gb = (size_t)b0 + blk;
+    // row of accumulator register i on this lane: (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
+    const float *bp = a.lbias + gb * 32 + 4 * (lane >> 5);
+    float16v acc;
+#pragma unroll
+    for (int i4 = 0; i4 < 4; ++i4) {
+      const float4 bv = *(const float4 *)(bp + 8 * i4);
+      acc[4 * i4 + 0] = bv.x;
+      acc[4 * i4 + 1] = bv.y;
+      acc[4 * i4 + 2] = bv.z;
+      acc[4 * i4 + 3] = bv.w;
+    }
+    const half8 *ap = (const half8 *)a.lf + gb * S * 64 + lane;
+    for (int s = 0; s < S; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ap[(size_t)s * 64], sq[s * 64 + lane], acc, 0, 0, 0);
+    if (myq < 0) continue;
+    // padding rows carry the bias -inf: they pass no threshold, not even -inf
+    uint32_t pass = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) pass |= (uint32_t)(acc[i] >= thr && acc[i] > -INFINITY) << i;
+    if (pass == 0) continue;
+    uint32_t pos = atomicAdd(&a.cnt[myq], (uint32_t)__popc(pass));
+    const uint32_t slot0 = (uint32_t)(gb * 32) + 4u * (uint32_t)(lane >> 5);
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (pass >> i & 1) {
+        if (pos < (uint32_t)CAP) a.surv[(size_t)myq * CAP + pos] = Survivor{acc[i], slot0 + (i & 3) + 8 * (i >> 2)};
+        ++pos;
+      }
+  }
+}
+
+// k-th largest of n floats (stride in floats), one workgroup, 4 radix passes over an LDS histogram (as dense_ann.hip)
+__device__ float wg_kth_largest(const float *vals, int64_t n, int stride, int k, uint32_t *hist /*[258]*/) {
+  uint32_t prefix = 0, mask = 0;
+  uint32_t want = (uint32_t)k;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+      uint32_t key = f2key(vals[i * stride]);
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t acc = 0;
+      int dgt = 255;
+      for (; dgt > 0; --dgt) {
+        if (acc + hist[dgt] >= want) break;
+        acc += hist[dgt];
+      }
+      hist[256] = (uint32_t)dgt;
+      hist[257] = want - acc;
+    }
+    __syncthreads();
+    prefix |= hist[256] << shift;
+    mask |= 255u << shift;
+    want = hist[257];
+    __syncthreads();
+  }
+  return key2f(prefix);
+}
+
+// after a scan round: a query whose candidates fitted is finished (tau = +inf); one that overflowed is re-armed with the
+// k-th largest buffered score.  flags: 1 = another round, 2 = cannot tighten (more than CAP scores tie at the k-th).
+__global__ void refine_kernel(float *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ done_cnt,
+                              const Survivor *__restrict__ surv, int k, int *__restrict__ flags) {
+  __shared__ uint32_t hist[258];
+  const int q = blockIdx.x;
+  if (done_cnt[q] != 0xffffffffu) return;  // finished in an earlier round
+  const uint32_t c = cnt[q];
+  if (c <= (uint32_t)CAP) {
+    if (threadIdx.x == 0) {
+      done_cnt[q] = c;
+      tau[q] = INFINITY;
+    }
+    return;
+  }
+  const float old = tau[q];
+  const float nt = wg_kth_largest(&surv[(size_t)q * CAP].score, CAP, 2, k, hist);
+  if (threadIdx.x == 0) {
+    if (nt > old) {
+      tau[q] = nt;
+      cnt[q] = 0;
+      atomicOr(&flags[0], 1);
+    } else {
+      tau[q] = INFINITY;
+      atomicOr(&flags[0], 2);
+    }
+  }
+}
+__global__ void arm_kernel(float *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ done_cnt, int nq) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  tau[q] = -INFINITY;
+  cnt[q] = 0;
+  done_cnt[q] = 0xffffffffu;
+}
+
+// per query: sort survivors by (score desc, rank in id order asc), emit the k nearest as distances (dense_ann.hip's select
+// with the list slot in place of the position)
+__global__ __launch_bounds__(512) void select_kernel(const Survivor *__restrict__ surv, const uint32_t *__restrict__ done_cnt,
+                                                     const float *__restrict__ qsumsq, const uint32_t *__restrict__ lrank,
+                                                     const int64_t *__restrict__ ids_sorted, int metric, int k,
+                                                     float *__restrict__ out_dist, int64_t *__restrict__ out_ids,
+                                                     int32_t *__restrict__ out_counts) {
+  extern __shared__ unsigned long long keys[];
+  const int q = blockIdx.x;
+  const uint32_t c = min(done_cnt[q], (uint32_t)CAP);
+  uint32_t n2 = 64;
+  while (n2 < c) n2 <<= 1;
+  for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
+    unsigned long long key = 0;
+    if (i < c) {
+      Survivor s = surv[(size_t)q * CAP + i];
+      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - lrank[s.slot]);
+    }
+    keys[i] = key;
+  }
+  __syncthreads();
+  for (uint32_t size = 2; size <= n2; size <<= 1)
+    for (uint32_t str = size >> 1; str > 0; str >>= 1) {
+      for (uint32_t i = threadIdx.x; i < n2 / 2; i += blockDim.x) {
+        uint32_t lo = 2 * i - (i & (str - 1));
+        uint32_t hi = lo + str;
+        bool desc = (lo & size) == 0;
+        unsigned long long x = keys[lo], y = keys[hi];
+        if ((x < y) == desc) {
+          keys[lo] = y;
+          keys[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  const uint32_t m = min(c, (uint32_t)k);
+  for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
+    float dist = 0.0f;
+    int64_t id = 0;
+    if (i < m) {
+      unsigned long long key = keys[i];
+      float sc = key2f((uint32_t)(key >> 32));
+      id = ids_sorted[0xffffffffu - (uint32_t)key];
+      if (metric == IVF_METRIC_L2) dist = sqrtf(fmaxf(0.0f, qsumsq[q] - 2.0f * sc));
+      else dist = 1.0f - sc;
+    }
+    out_dist[(size_t)q * k + i] = dist;
+    out_ids[(size_t)q * k + i] = id;
+  }
+  if (threadIdx.x == 0) out_counts[q] = (int32_t)m;
+}
+
+struct Buf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  ~Buf() { if (p) (void)hipFree(p); }
+  hipError_t reserve(size_t n) {
+    if (n <= bytes) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    hipError_t e = hipMalloc(&p, n ? n : 8);
+    if (e == hipSuccess) bytes = n ? n : 8;
+    return e;
+  }
+  // growth that keeps the first `keep` bytes (device to device)
+  hipError_t grow_keep(size_t keep, size_t want) {
+    if (p && want <= bytes) return hipSuccess;
+    void *np = nullptr;
+    hipError_t e = hipMalloc(&np, want ? want : 8);
+    if (e != hipSuccess) return e;
+    if (keep && p) {
+      e = hipMemcpy(np, p, keep, hipMemcpyDeviceToDevice);
+      if (e != hipSuccess) {
+        (void)hipFree(np);
+        return e;
+      }
+    }
+    if (p) (void)hipFree(p);
+    p = np;
+    bytes = want ? want : 8;
+    return hipSuccess;
+  }
+  template <class T> T *as() const { return (T *)p; }
+};
+
+inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
+}  // namespace
+
+struct ivf_index {
+  int device = 0, metric = 0, d = 0, nlist = 0;
+  int64_t n = 0;
+  int ids_mode = -1;  // -1: no add yet; 0: ids are positions; 1: ids given
+  dann_index *coarse = nullptr;
+  // the rows in the order they were added
+  Buf flat, sumsq, cell, ids;
+  // the lists
+  Buf ids_sorted, perm, cell_r, cell_sorted, ord, iota, sizes, start, nblk, boff, lf, lbias, lrank, sort_tmp, ids_tmp;
+  std::vector<int64_t> h_sizes;
+  int64_t total_blocks = 0;
+  // per-call scratch
+  Buf stage, c_dist, c_ids, c_cnt, qf, qsumsq;
+  Buf pair_cell, pair_q, pair_cell_s, pair_q_s, per_cell, pstart, ngrp, gstart, groups, rows_acc;
+  Buf tau, cnt, done_cnt, surv, flags, o_dist, o_ids, o_cnt;
+  // the last search
+  Buf probes;
+  int32_t last_nq = 0, last_nprobe = 0, last_rounds = 0;
+  int64_t last_rows = 0;
+  float t_coarse = 0, t_scan = 0, t_sel = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~ivf_index() {
+    if (coarse) (void)dann_index_destroy(coarse);
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+namespace {
+
+int check_shape(int32_t metric, int32_t d, int32_t nlist) {
+  if (metric < IVF_METRIC_L2 || metric > IVF_METRIC_INNER_PRODUCT) return fail(IVF_EINVAL, "unknown metric");
+  if (d < 16 || d > MAX_D || d % 16) return fail(IVF_EINVAL, "dimension must be a multiple of 16 in 16..512");
+  if (nlist < 1 || nlist > MAX_NLIST) return fail(IVF_EINVAL, "nlist must be in 1..65536");
+  return IVF_OK;
+}
+
+int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, std::unique_ptr<ivf_index> &ix) {
+  ITRY(hipSetDevice(device));
+  ix.reset(new ivf_index);
+  ix->device = device;
+  ix->metric = metric;
+  ix->d = d;
+  ix->nlist = nlist;
+  ix->h_sizes.assign((size_t)nlist, 0);
+  for (auto &e : ix->ev) ITRY(hipEventCreate(&e));
+  ITRY(ix->sizes.reserve((size_t)nlist * 4));
+  ITRY(ix->start.reserve((size_t)nlist * 4));
+  ITRY(ix->nblk.reserve((size_t)nlist * 4));
+  ITRY(ix->boff.reserve((size_t)nlist * 4));
+  ITRY(hipMemset(ix->sizes.p, 0, (size_t)nlist * 4));
+  ITRY(hipMemset(ix->start.p, 0, (size_t)nlist * 4));
+  ITRY(hipMemset(ix->nblk.p, 0, (size_t)nlist * 4));
+  ITRY(hipMemset(ix->boff.p, 0, (size_t)nlist * 4));
+  return IVF_OK;
+}
+
+// host rows -> fp16 rows at flat[row0 ..) and their sums of squares, through a staging buffer
+int upload_rows(ivf_index *ix, const float *rows, int64_t n, Buf &flat, Buf &sumsq, int64_t row0) {
+  const int d = ix->d;
+  const int64_t slab = std::max<int64_t>(1, (int64_t)(64 << 20) / (d * 4));
+  ITRY(ix->stage.reserve((size_t)std::min(slab, n) * d * sizeof(float)));
+  for (int64_t r0 = 0; r0 < n; r0 += slab) {
+    const int64_t m = std::min(slab, n - r0);
+    ITRY(hipMemcpy(ix->stage.p, rows + r0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, ix->stage.as<float>(), m, d,
+                       ix->metric == IVF_METRIC_COSINE ? 1 : 0, flat.as<_Float16>() + (size_t)(row0 + r0) * d,
+                       sumsq.as<float>() + row0 + r0);
+    ITRY(hipGetLastError());
+    ITRY(hipDeviceSynchronize());
+  }
+  return IVF_OK;
+}
+
+// stable sort of n (cell number, value) pairs by cell
+int sort_by_cell(ivf_index *ix, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out, int64_t n) {
+  size_t tb = 0;
+  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
+  ITRY(ix->sort_tmp.reserve(tb));
+  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
+  return IVF_OK;
+}
+int exclusive_sum(ivf_index *ix, const uint32_t *in, uint32_t *out, int n) {
+  size_t tb = 0;
+  ITRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, (hipStream_t)0));
+  ITRY(ix->sort_tmp.reserve(tb));
+  ITRY(hipcub::DeviceScan::ExclusiveSum(ix->sort_tmp.p, tb, in, out, n, (hipStream_t)0));
+  return IVF_OK;
+}
+
+// the nearest centroid of each of n fp16 rows (the coarse search with k = 1, CHUNK rows at a time) -> cell[0 .. n)
+int assign_rows(ivf_index *ix, dann_index *coarse, const _Float16 *flat, const float *sumsq, int64_t n, int32_t *cell) {
+  ann_by_id::DannTarget tgt;
+  DCALL(ann_by_id::dann_open(coarse, 1, false, &tgt));
+  ITRY(ix->c_dist.reserve((size_t)CHUNK * sizeof(float)));
+  ITRY(ix->c_ids.reserve((size_t)CHUNK * sizeof(int64_t)));
+  ITRY(ix->c_cnt.reserve((size_t)CHUNK * sizeof(int32_t)));
+  const int d = ix->d;
+  for (int64_t r0 = 0; r0 < n; r0 += CHUNK) {
+    const int m = (int)std::min<int64_t>(CHUNK, n - r0);
+    ann_by_id::DannChunk ch;
+    DCALL(ann_by_id::dann_chunk_open(coarse, m, 1, &ch));
+    hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)m * (d >> 3))), dim3(256), 0, 0, flat + (size_t)r0 * d,
+                       sumsq + r0, m, d, tgt.S, ch.qf, ch.qsumsq, (_Float16 *)nullptr);
+    ITRY(hipGetLastError());
+    int64_t d2h = 0;
+    DCALL(ann_by_id::dann_chunk_search_prepared(coarse, m, 1, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
+                                                ix->c_cnt.as<int32_t>(), &d2h));
+    hipLaunchKernelGGL(cells_kernel, dim3(blocks_for(m)), dim3(256), 0, 0, ix->c_ids.as<int64_t>(), m, cell + r0);
+    ITRY(hipGetLastError());
+  }
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+}
+
+// cells of n rows -> their order by (cell, position): ord, and per cell its size and first place in that order
+int segment_by_cell(ivf_index *ix, const uint32_t *perm, int64_t n) {
+  ITRY(ix->cell_r.reserve((size_t)n * 4));
+  ITRY(ix->cell_sorted.reserve((size_t)n * 4));
+  ITRY(ix->ord.reserve((size_t)n * 4));
+  ITRY(ix->iota.reserve((size_t)n * 4));
+  ITRY(hipMemset(ix->sizes.p, 0, (size_t)ix->nlist * 4));
+  if (n > 0) {
+    hipLaunchKernelGGL(gather_cells_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell.as<int32_t>(), perm, n,
+                       ix->cell_r.as<uint32_t>());
+    ITRY(hipGetLastError());
+    hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->iota.as<uint32_t>(), n);
+    ITRY(hipGetLastError());
+    if (int rc = sort_by_cell(ix, ix->cell_r.as<uint32_t>(), ix->cell_sorted.as<uint32_t>(), ix->iota.as<uint32_t>(),
+                              ix->ord.as<uint32_t>(), n))
+      return rc;
+    hipLaunchKernelGGL(hist_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell_r.as<uint32_t>(), n, ix->sizes.as<uint32_t>());
+    ITRY(hipGetLastError());
+  }
+  return exclusive_sum(ix, ix->sizes.as<uint32_t>(), ix->start.as<uint32_t>(), ix->nlist);
+}
+
+// all lists again from the rows in the order added: (cell, id) order, every list on a block boundary
+int layout_lists(ivf_index *ix) {
+  const int64_t n = ix->n;
+  const int d = ix->d, nlist = ix->nlist;
+  // rank in (id, position) order: ids_sorted[rank], perm[rank] = position
+  ITRY(ix->ids_sorted.reserve((size_t)n * 8));
+  ITRY(ix->perm.reserve((size_t)n * 4));
+  ITRY(ix->iota.reserve((size_t)n * 4));
+  hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->iota.as<uint32_t>(), n);
+  ITRY(hipGetLastError());
+  size_t tb = 0;
+  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const uint32_t *)nullptr,
+                                          (uint32_t *)nullptr, (int)n, 0, 64, (hipStream_t)0));
+  ITRY(ix->sort_tmp.reserve(tb));
+  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, ix->ids.as<int64_t>(), ix->ids_sorted.as<int64_t>(),
+                                          ix->iota.as<uint32_t>(), ix->perm.as<uint32_t>(), (int)n, 0, 64, (hipStream_t)0));
+  ITRY(hipDeviceSynchronize());  // (segment_by_cell may replace sort_tmp)
+  // ranks by (cell, rank)
+  if (int rc = segment_by_cell(ix, ix->perm.as<uint32_t>(), n)) return rc;
+  hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, 0, ix->sizes.as<uint32_t>(), nlist, ix->nblk.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = exclusive_sum(ix, ix->nblk.as<uint32_t>(), ix->boff.as<uint32_t>(), nlist)) return rc;
+  std::vector<uint32_t> hs((size_t)nlist);
+  ITRY(hipMemcpy(hs.data(), ix->sizes.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
+  int64_t blocks = 0;
+  for (int c = 0; c < nlist; ++c) {
+    ix->h_sizes[(size_t)c] = hs[(size_t)c];
+    blocks += (hs[(size_t)c] + 31) / 32;
+  }
+  if (blocks * 32 >= (int64_t)0xffffff00u) return fail(IVF_ELIMIT, "the lists would hold 2^32 slots or more");
+  ix->total_blocks = blocks;
+  const size_t slots = (size_t)blocks * 32;
+  ITRY(ix->lf.reserve(slots * d * sizeof(_Float16)));
+  ITRY(ix->lbias.reserve(slots * sizeof(float)));
+  ITRY(ix->lrank.reserve(slots * sizeof(uint32_t)));
+  ITRY(hipMemset(ix->lf.p, 0, slots * d * sizeof(_Float16)));
+  ITRY(hipMemset(ix->lrank.p, 0, slots * sizeof(uint32_t)));
+  hipLaunchKernelGGL(fill_kernel, dim3(blocks_for((int64_t)slots)), dim3(256), 0, 0, ix->lbias.as<float>(), (int64_t)slots, -INFINITY);
+  ITRY(hipGetLastError());
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, 0, ix->flat.as<_Float16>(), ix->sumsq.as<float>(), n, d,
+                     ix->metric, ix->cell_sorted.as<uint32_t>(), ix->ord.as<uint32_t>(), ix->perm.as<uint32_t>(),
+                     ix->start.as<uint32_t>(), ix->boff.as<uint32_t>(), ix->lf.as<_Float16>(), ix->lbias.as<float>(),
+                     ix->lrank.as<uint32_t>());
+  ITRY(hipGetLastError());
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+}
+
+int build_coarse(ivf_index *ix, const float *d_cent) {
+  dann_index *c = nullptr;
+  DCALL(ann_by_id::dann_build_device(ix->device, ix->metric, ix->nlist, ix->d, d_cent, &c));
+  if (ix->coarse) (void)dann_index_destroy(ix->coarse);
+  ix->coarse = c;
+  return IVF_OK;
+}
+
+int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
+                 int64_t *out_ids, int32_t *out_counts) {
+  const int d = ix->d, S = d >> 4, nlist = ix->nlist;
+  const int64_t np = (int64_t)nq * nprobe;
+  hipStream_t st = 0;
+  ann_by_id::DannTarget tgt;
+  DCALL(ann_by_id::dann_open(ix->coarse, nprobe, false, &tgt));
+  ann_by_id::DannChunk ch;
+  DCALL(ann_by_id::dann_chunk_open(ix->coarse, nq, nprobe, &ch));
+  const int nq_pad = (nq + 31) / 32 * 32;
+  ITRY(ix->stage.reserve((size_t)nq * d * sizeof(float)));
+  ITRY(ix->qf.reserve((size_t)nq_pad * d * sizeof(_Float16) * 2));  // the fp16 rows, then the scan's fragments
+  ITRY(ix->qsumsq.reserve((size_t)nq_pad * sizeof(float)));
+  ITRY(ix->c_dist.reserve((size_t)np * sizeof(float)));
+  ITRY(ix->c_ids.reserve((size_t)np * sizeof(int64_t)));
+  ITRY(ix->c_cnt.reserve((size_t)std::max(nq, CHUNK) * sizeof(int32_t)));
+  ITRY(ix->pair_cell.reserve((size_t)np * 4));
+  ITRY(ix->pair_q.reserve((size_t)np * 4));
+  ITRY(ix->pair_cell_s.reserve((size_t)np * 4));
+  ITRY(ix->pair_q_s.reserve((size_t)np * 4));
+  ITRY(ix->per_cell.reserve((size_t)nlist * 4));
+  ITRY(ix->pstart.reserve((size_t)nlist * 4));
+  ITRY(ix->ngrp.reserve((size_t)nlist * 4));
+  ITRY(ix->gstart.reserve((size_t)nlist * 4));
+  ITRY(ix->rows_acc.reserve(8));
+  ITRY(ix->tau.reserve((size_t)nq * 4));
+  ITRY(ix->cnt.reserve((size_t)nq * 4));
+  ITRY(ix->done_cnt.reserve((size_t)nq * 4));
+  ITRY(ix->flags.reserve(sizeof(int)));
+  ITRY(ix->surv.reserve((size_t)nq * CAP * sizeof(Survivor)));
+  ITRY(ix->o_dist.reserve((size_t)nq * k * sizeof(float)));
+  ITRY(ix->o_ids.reserve((size_t)nq * k * sizeof(int64_t)));
+  ITRY(ix->o_cnt.reserve((size_t)nq * sizeof(int32_t)));
+  _Float16 *q16 = ix->qf.as<_Float16>(), *qfrag = q16 + (size_t)nq_pad * d;
+
+  // coarse: the nprobe nearest centroids of every query
+  ITRY(hipEventRecord(ix->ev[0], st));
+  ITRY(hipMemcpyAsync(ix->stage.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, ix->stage.as<float>(), (int64_t)nq, d,
+                     ix->metric == IVF_METRIC_COSINE ? 1 : 0, q16, ix->qsumsq.as<float>());
+  ITRY(hipGetLastError());
+  hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, q16, ix->qsumsq.as<float>(), nq, d,
+                     tgt.S, ch.qf, ch.qsumsq, qfrag);
+  ITRY(hipGetLastError());
+  int64_t d2h = 0;
+  DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, nq, nprobe, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
+                                              ix->c_cnt.as<int32_t>(), &d2h));
+
+  // inversion: (cell, query) pairs sorted by cell, cut into groups of <= 32 queries
+  ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
+  ITRY(hipMemsetAsync(ix->rows_acc.p, 0, 8, st));
+  hipLaunchKernelGGL(probes_kernel, dim3(blocks_for(np)), dim3(256), 0, st, ix->c_ids.as<int64_t>(), nq, nprobe,
+                     ix->probes.as<int32_t>() + (size_t)q0 * nprobe, ix->pair_cell.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
+                     ix->per_cell.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = sort_by_cell(ix, ix->pair_cell.as<uint32_t>(), ix->pair_cell_s.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
+                            ix->pair_q_s.as<uint32_t>(), np))
+    return rc;
+  hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), nlist, ix->ngrp.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = exclusive_sum(ix, ix->per_cell.as<uint32_t>(), ix->pstart.as<uint32_t>(), nlist)) return rc;
+  if (int rc = exclusive_sum(ix, ix->ngrp.as<uint32_t>(), ix->gstart.as<uint32_t>(), nlist)) return rc;
+  uint32_t last[2] = {0, 0};
+  ITRY(hipMemcpy(&last[0], ix->gstart.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
+  ITRY(hipMemcpy(&last[1], ix->ngrp.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
+  const uint32_t n_groups = last[0] + last[1];
+  ITRY(ix->groups.reserve((size_t)n_groups * sizeof(Group)));
+  hipLaunchKernelGGL(groups_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), ix->pstart.as<uint32_t>(),
+                     ix->gstart.as<uint32_t>(), ix->sizes.as<uint32_t>(), nlist, ix->groups.as<Group>(),
+                     ix->rows_acc.as<unsigned long long>());
+  ITRY(hipGetLastError());
+  hipLaunchKernelGGL(arm_kernel, dim3(blocks_for(nq)), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
+                     ix->done_cnt.as<uint32_t>(), nq);
+  ITRY(hipGetLastError());
+  ITRY(hipEventRecord(ix->ev[1], st));
+
+  // scan rounds
+  ScanArgs a;
+  a.lf = ix->lf.as<_Float16>();
+  a.lbias = ix->lbias.as<float>();
+  a.boff = ix->boff.as<uint32_t>();
+  a.nblk = ix->nblk.as<uint32_t>();
+  a.qf = qfrag;
+  a.groups = ix->groups.as<Group>();
+  a.pair_q = ix->pair_q_s.as<uint32_t>();
+  a.tau = ix->tau.as<float>();
+  a.cnt = ix->cnt.as<uint32_t>();
+  a.surv = ix->surv.as<Survivor>();
+  a.S = S;
+  int rounds = 0;
+  for (;; ++rounds) {
+    if (ix->n > 0) {
+      hipLaunchKernelGGL(scan_kernel, dim3(n_groups), dim3(256), (size_t)S * 64 * sizeof(half8), st, a);
+      ITRY(hipGetLastError());
+    }
+    int flags = 0;
+    ITRY(hipMemsetAsync(ix->flags.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(refine_kernel, dim3(nq), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
+                       ix->done_cnt.as<uint32_t>(), ix->surv.as<Survivor>(), k, ix->flags.as<int>());
+    ITRY(hipGetLastError());
+    ITRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    ITRY(hipStreamSynchronize(st));
+    if (flags & 2) return fail(IVF_ELIMIT, "more than 8192 rows of the probed lists tie at the k-th distance of a query");
+    if (rounds >= 16) return fail(IVF_ELIMIT, "threshold refinement did not converge");
+    if (!(flags & 1)) break;
+  }
+  ITRY(hipEventRecord(ix->ev[2], st));
+
+  ITRY(hipFuncSetAttribute((const void *)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
+  hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
+                     ix->done_cnt.as<uint32_t>(), ix->qsumsq.as<float>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(),
+                     ix->metric, k, ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
+  ITRY(hipGetLastError());
+  ITRY(hipEventRecord(ix->ev[3], st));
+  ITRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  ITRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ITRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  unsigned long long rows = 0;
+  ITRY(hipMemcpyAsync(&rows, ix->rows_acc.p, 8, hipMemcpyDeviceToHost, st));
+  ITRY(hipStreamSynchronize(st));
+  float tc = 0, ts = 0, tl = 0;
+  (void)hipEventElapsedTime(&tc, ix->ev[0], ix->ev[1]);
+  (void)hipEventElapsedTime(&ts, ix->ev[1], ix->ev[2]);
+  (void)hipEventElapsedTime(&tl, ix->ev[2], ix->ev[3]);
+  ix->t_coarse += tc;
+  ix->t_scan += ts;
+  ix->t_sel += tl;
+  ix->last_rows += (int64_t)rows;
+  ix->last_rounds = std::max(ix->last_rounds, rounds + 1);
+  return IVF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *ivf_last_error(void) { return g_err.c_str(); }
+
+int ivf_index_load(int32_t device, int32_t metric, int32_t d, int32_t nlist, const float *centroids, ivf_index_t **out) try {
+  if (!centroids || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist)) return rc;
+  std::unique_ptr<ivf_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, ix)) return rc;
+  Buf cent;
+  ITRY(cent.reserve((size_t)nlist * d * sizeof(float)));
+  ITRY(hipMemcpy(cent.p, centroids, (size_t)nlist * d * sizeof(float), hipMemcpyHostToDevice));
+  if (int rc = build_coarse(ix.get(), cent.as<float>())) return rc;
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t n_train, const float *train_vectors,
+                    int32_t niter, uint64_t seed, ivf_index_t **out) try {
+  if (!train_vectors || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist)) return rc;
+  if (n_train < nlist) return fail(IVF_EINVAL, "n_train must be at least nlist");
+  if (n_train >= ((int64_t)1 << 31)) return fail(IVF_EINVAL, "n_train out of range");
+  if (niter < -1) return fail(IVF_EINVAL, "niter must be -1 (initial picks), 0 (20 rounds) or a number of rounds");
+  const int rounds = niter == 0 ? 20 : niter == -1 ? 0 : niter;
+  std::unique_ptr<ivf_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, ix)) return rc;
+  // the training rows, prepared as stored rows are; they go with this call
+  Buf tflat, tsumsq, picks_d, cent;
+  ITRY(tflat.reserve((size_t)n_train * d * sizeof(_Float16)));
+  ITRY(tsumsq.reserve((size_t)n_train * sizeof(float)));
+  if (int rc = upload_rows(ix.get(), train_vectors, n_train, tflat, tsumsq, 0)) return rc;
+  // initial centroids: rows mix64(seed + t) mod n_train, t = 0, 1, ..., without repetition
+  std::vector<int64_t> picks;
+  picks.reserve((size_t)nlist);
+  std::unordered_set<int64_t> seen;
+  for (uint64_t t = 0; (int)picks.size() < nlist; ++t) {
+    const int64_t r = (int64_t)(sann::mix64(seed + t) % (uint64_t)n_train);
+    if (seen.insert(r).second) picks.push_back(r);
+  }
+  ITRY(picks_d.reserve((size_t)nlist * 8));
+  ITRY(hipMemcpy(picks_d.p, picks.data(), (size_t)nlist * 8, hipMemcpyHostToDevice));
+  ITRY(cent.reserve((size_t)nlist * d * sizeof(float)));
+  hipLaunchKernelGGL(pick_rows_kernel, dim3(blocks_for((int64_t)nlist * d)), dim3(256), 0, 0, tflat.as<_Float16>(),
+                     picks_d.as<int64_t>(), nlist, d, cent.as<float>());
+  ITRY(hipGetLastError());
+  if (metric == IVF_METRIC_INNER_PRODUCT) {
+    hipLaunchKernelGGL(unit_rows_kernel, dim3(blocks_for(nlist, 4)), dim3(256), 0, 0, cent.as<float>(), nlist, d);
+    ITRY(hipGetLastError());
+  }
+  ITRY(hipDeviceSynchronize());
+  if (int rc = build_coarse(ix.get(), cent.as<float>())) return rc;
+  ITRY(ix->cell.reserve((size_t)n_train * 4));
+  for (int it = 0; it < rounds; ++it) {
+    if (int rc = assign_rows(ix.get(), ix->coarse, tflat.as<_Float16>(), tsumsq.as<float>(), n_train, ix->cell.as<int32_t>())) return rc;
+    if (int rc = segment_by_cell(ix.get(), nullptr, n_train)) return rc;
+    hipLaunchKernelGGL(mean_kernel, dim3(nlist), dim3(256), 0, 0, tflat.as<_Float16>(), d, metric, ix->ord.as<uint32_t>(),
+                       ix->start.as<uint32_t>(), ix->sizes.as<uint32_t>(), cent.as<float>());
+    ITRY(hipGetLastError());
+    ITRY(hipDeviceSynchronize());
+    if (int rc = build_coarse(ix.get(), cent.as<float>())) return rc;
+  }
+  // the index starts empty
+  ITRY(hipMemset(ix->sizes.p, 0, (size_t)nlist * 4));
+  ITRY(hipMemset(ix->start.p, 0, (size_t)nlist * 4));
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_add(ivf_index_t *ix, int64_t n, const float *vectors, const int64_t *ids) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (n < 0) return fail(IVF_EINVAL, "n must not be negative");
+  if (ix->ids_mode == 1 && !ids) return fail(IVF_EINVAL, "the index holds rows added with ids: an add must give ids");
+  if (ix->ids_mode == 0 && ids) return fail(IVF_EINVAL, "the index holds rows added without ids (its ids are positions): ids must be NULL");
+  if (n == 0) return IVF_OK;
+  if (!vectors) return fail(IVF_EINVAL, "null vectors");
+  const int64_t n_old = ix->n, total = n_old + n;
+  if (total >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
+  ITRY(hipSetDevice(ix->device));
+  const int d = ix->d;
+  ITRY(ix->flat.grow_keep((size_t)n_old * d * sizeof(_Float16), (size_t)total * d * sizeof(_Float16)));
+  ITRY(ix->sumsq.grow_keep((size_t)n_old * 4, (size_t)total * 4));
+  ITRY(ix->cell.grow_keep((size_t)n_old * 4, (size_t)total * 4));
+  ITRY(ix->ids.grow_keep((size_t)n_old * 8, (size_t)total * 8));
+  if (int rc = upload_rows(ix, vectors, n, ix->flat, ix->sumsq, n_old)) return rc;
+  if (ids) {
+    ITRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  } else {
+    hipLaunchKernelGGL(iota64_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->ids.as<int64_t>() + n_old, n_old, n);
+    ITRY(hipGetLastError());
+  }
+  if (int rc = assign_rows(ix, ix->coarse, ix->flat.as<_Float16>() + (size_t)n_old * d, ix->sumsq.as<float>() + n_old, n,
+                           ix->cell.as<int32_t>() + n_old))
+    return rc;
+  ix->n = total;
+  ix->ids_mode = ids ? 1 : 0;
+  return layout_lists(ix);
+} ABI_CATCH
+
+int ivf_search(ivf_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist, int64_t *out_ids,
+               int32_t *out_counts) try {
+  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
+  if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
+  if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
+  nprobe = std::min(nprobe, ix->nlist);
+  ITRY(hipSetDevice(ix->device));
+  ITRY(ix->probes.reserve((size_t)nq * nprobe * sizeof(int32_t)));
+  ix->last_nq = 0;
+  ix->last_nprobe = nprobe;
+  ix->last_rows = 0;
+  ix->last_rounds = 0;
+  ix->t_coarse = ix->t_scan = ix->t_sel = 0;
+  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
+    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
+    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, k, nprobe, out_dist + (size_t)q0 * k,
+                              out_ids + (size_t)q0 * k, out_counts + q0))
+      return rc;
+  }
+  ix->last_nq = nq;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_info(const ivf_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (n) *n = ix->n;
+  if (d) *d = ix->d;
+  if (metric) *metric = ix->metric;
+  if (nlist) *nlist = ix->nlist;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_get_centroids(const ivf_index_t *ix, float *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  DCALL(dann_index_get_vectors(ix->coarse, 0, ix->nlist, out));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_list_sizes(const ivf_index_t *ix, int64_t *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  std::copy(ix->h_sizes.begin(), ix->h_sizes.end(), out);
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_get_assignment(const ivf_index_t *ix, int64_t *out_ids, int32_t *out_cells) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (ix->n == 0) return IVF_OK;
+  ITRY(hipSetDevice(ix->device));
+  if (out_ids) ITRY(hipMemcpy(out_ids, ix->ids.p, (size_t)ix->n * 8, hipMemcpyDeviceToHost));
+  if (out_cells) ITRY(hipMemcpy(out_cells, ix->cell.p, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_last_probes(const ivf_index_t *ix, int32_t *nq, int32_t *nprobe, int32_t *out_cells) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (nq) *nq = ix->last_nq;
+  if (nprobe) *nprobe = ix->last_nprobe;
+  if (out_cells && ix->last_nq > 0) {
+    ITRY(hipSetDevice(ix->device));
+    ITRY(hipMemcpy(out_cells, ix->probes.p, (size_t)ix->last_nq * ix->last_nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_last_stats(const ivf_index_t *ix, int64_t *rows_scanned, int32_t *rounds, float *coarse_ms, float *scan_ms,
+                   float *select_ms) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (rows_scanned) *rows_scanned = ix->last_rows;
+  if (rounds) *rounds = ix->last_rounds;
+  if (coarse_ms) *coarse_ms = ix->t_coarse;
+  if (scan_ms) *scan_ms = ix->t_scan;
+  if (select_ms) *select_ms = ix->t_sel;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_destroy(ivf_index_t *ix) try {
+  delete ix;
+  return IVF_OK;
+} ABI_CATCH
+
+}  // extern "C"
