@@ -30,7 +30,7 @@ extern "C" {
 #define DANN_OK 0
 #define DANN_EINVAL 1
 #define DANN_EDEVICE 2
-#define DANN_ELIMIT 3
+#define DANN_ELIMIT 3   /* more than 8192 stored vectors at or nearer than a query's k-th nearest: see dann_search */
 #define DANN_ENOMEM 4    /* host allocation failed */
 #define DANN_EINTERNAL 5 /* an unexpected C++ exception was caught at the ABI; the message says which */
 
@@ -79,7 +79,26 @@ int dann_index_destroy(dann_index_t *index);
 
 /* nq queries (row-major fp32 [nq][d]) -> for each the k nearest stored vectors, ascending by distance
  * (ties: id ascending): out_dist[nq*k], out_ids[nq*k], out_counts[nq] (= min(k, n)).  k <= 1024.
- * Distances: L2 = ||q - x||, Cosine = 1 - cos(q, x), InnerProduct = 1 - <q, x>. */
+ * Distances: L2 = ||q - x||, Cosine = 1 - cos(q, x), InnerProduct = 1 - <q, x>.
+ *
+ * The one limit that depends on the data.  For a query let s_k be its k-th best score of the fp16 pass (the k-th nearest
+ * distance) and T the number of stored vectors that score >= s_k: T = k, plus whatever ties with the k-th.  The search keeps
+ * at most 8192 survivors per query, and:
+ *   T <= 8192  the call succeeds and returns the exact top-k, ties in id order -- however the rows are ordered, duplicated
+ *              or clustered, and whatever else ties below s_k (a mass of equal rows under the k-th is not a limit);
+ *   T >  8192  for any query of the call: DANN_ELIMIT for the call as a whole, with a message that names the limit.  Every
+ *              out_counts[0..nq) is 0 and out_dist / out_ids hold no answer (their contents are unspecified).
+ *              (The zeroed counts are dann_search's: the by-id query and the IVF coarse search, which share the passes,
+ *              return the same code and message under their own output rules.)
+ * A refused call leaves the index as it was: the next search on it answers as if the refused one had not been made.
+ * T is a property of the stored rows, the query and k alone.  Exact mode scores on from a threshold lowered by its rounding
+ * bound, so there the rows within that bound below s_k count towards the 8192 as well.
+ * One more refusal exists: a search that needs more than 16 passes over the index to settle its thresholds fails with
+ * DANN_ELIMIT and a message that says so.  A pass over an overflowed query either tightens its threshold past 8192 - k of the
+ * buffered rows or, when more than 8192 rows tie at the threshold, spends two passes (overflow, then the probe above the tie)
+ * on that one score.  What can reach the cap with T <= 8192 is therefore a stack of about eight such masses of equal rows,
+ * each of more than 8192, all under the k-th best and above the first threshold (eight groups of duplicated embeddings in
+ * an index too small for the sampled first pass, say). */
 int dann_search(dann_index_t *index, int32_t nq, const float *queries, int32_t k, float *out_dist, int64_t *out_ids,
                 int32_t *out_counts);
 /* Full passes over the index the last dann_search needed: 1, plus one per round in which some query overflowed its

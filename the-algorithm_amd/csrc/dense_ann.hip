@@ -25,7 +25,8 @@
 //   pass B  the GEMM over the whole index appends every score >= tau_q to a per-query buffer.
 //   refine  a query whose buffer overflowed takes the k-th largest buffered score as a tighter bound
 //           and pass B is repeated for it (never happens at the sizes pass A is tuned for; it is the
-//           general fallback for tiny indexes / huge k).
+//           general fallback for tiny indexes / huge k).  When that bound is no tighter -- more than CAP rows tie at
+//           the threshold -- the next float up is probed before the query is refused: see refine_kernel.
 //   select  per query: sort the <= CAP survivors by (score desc, position asc), convert to distances.
 // Positions are in id order (the builder sorts by id), so ties resolve by id ascending.
 #include <hip/hip_runtime.h>
@@ -536,7 +537,13 @@ __global__ void tau_kernel(const float *__restrict__ tmax, int64_t pitch, int64_
 }
 
 // after pass B: overflowed queries get a tighter tau and are re-armed; the others are parked at +inf.
-// status: 0 done, 1 redo, 2 cannot tighten (more than CAP scores tie at the k-th)
+// status: 0 done, 1 redo, 2 refused (more than CAP stored vectors score at or above the k-th best), 3 redo as a probe.
+// The buffered CAP are an arbitrary subset of what passed tau, so their k-th largest is a lower bound of the k-th best score
+// and nothing more: when more than CAP rows tie at tau and few score above it, the buffer may hold fewer than k of the
+// better ones and the bound comes out at tau again.  That does not say the k-th best ties with them.  The query is then
+// re-armed with the next float above tau (a probe): k or more rows passing it make it the new lower bound and the search goes
+// on from there; fewer than k mean that the k-th best score IS the old tau, which more than CAP rows reach -- the one
+// case that is refused.
 __global__ void refine_kernel(float *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ done_cnt,
                               const Survivor *__restrict__ surv, int k, int nq, int *__restrict__ status,
                               int *__restrict__ flags, float *__restrict__ tau_used) {
@@ -545,27 +552,35 @@ __global__ void refine_kernel(float *__restrict__ tau, uint32_t *__restrict__ cn
   if (q >= nq) return;
   if (done_cnt[q] != 0xffffffffu) return;  // finished in an earlier round
   uint32_t c = cnt[q];
+  const bool probe = status[q] == 3;
   if (c <= (uint32_t)CAP) {
     if (threadIdx.x == 0) {
-      done_cnt[q] = c;
-      status[q] = 0;
-      if (tau_used) tau_used[q] = tau[q];  // (exact mode: the threshold this query's survivors passed)
-      tau[q] = INFINITY;
+      if (probe && c < (uint32_t)k) {  // more than CAP rows at the score below the probe, fewer than k above it
+        status[q] = 2;
+        tau[q] = INFINITY;
+        atomicOr(&flags[0], 2);
+      } else {
+        done_cnt[q] = c;
+        status[q] = 0;
+        if (tau_used) tau_used[q] = tau[q];  // (exact mode: the threshold this query's survivors passed)
+        tau[q] = INFINITY;
+      }
     }
     return;
   }
   float old = tau[q];
   float nt = wg_kth_largest(&surv[(size_t)q * CAP].score, CAP, 2, k, hist);
   if (threadIdx.x == 0) {
+    cnt[q] = 0;
+    atomicOr(&flags[0], 1);
     if (nt > old) {
       tau[q] = nt;
-      cnt[q] = 0;
       status[q] = 1;
-      atomicOr(&flags[0], 1);
     } else {
-      status[q] = 2;
-      tau[q] = INFINITY;
-      atomicOr(&flags[0], 2);
+      // the next float up.  old > -inf here on finite scores: from -inf (no pass A) the k-th buffered score is finite and
+      // took the branch above.  From -0.0 the next key is +0.0, which admits the same rows: one wasted pass, then 1.4e-45.
+      tau[q] = key2f(f2key(old) + 1u);
+      status[q] = 3;
     }
   }
 }
@@ -1002,7 +1017,10 @@ int dann_search(dann_index_t *ix, int32_t nq, const float *queries, int32_t k, f
     int32_t m = std::min<int32_t>(MAX_NQ, nq - q0);
     int rc = search_chunk(ix, m, queries + (size_t)q0 * ix->d, k, out_dist + (size_t)q0 * k, out_ids + (size_t)q0 * k,
                           out_counts + q0);
-    if (rc) return rc;
+    if (rc) {  // no count a caller could take for an answer (chunks before this one have written theirs)
+      std::fill(out_counts, out_counts + nq, 0);
+      return rc;
+    }
     ta += ix->t_a;
     tb += ix->t_b;
     ts += ix->t_sel;
@@ -1152,8 +1170,9 @@ static int chunk_search_prepared(dann_index_t *ix, int32_t nq, int32_t k, float 
     DTRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
     *d2h += (int64_t)sizeof(int);
     DTRY(hipStreamSynchronize(st));
-    if (flags & 2) return fail(DANN_ELIMIT, "more than 8192 stored vectors tie at the k-th distance of a query");
-    if (round >= 16) return fail(DANN_ELIMIT, "threshold refinement did not converge");
+    if (flags & 2)
+      return fail(DANN_ELIMIT, "more than 8192 stored vectors score at or above a query's k-th best; the survivor buffer holds 8192");
+    if (round >= 16) return fail(DANN_ELIMIT, "threshold refinement did not converge in 16 passes (8192 survivors per query and pass)");
     if (flags & 1) {
       continue;
     }
