@@ -9,8 +9,8 @@
  *   thrift/com/twitter/ann/common/ann_common.thrift:41-56       FaissRuntimeParam: nprobe first
  *   thrift/com/twitter/ann/common/ann_common.thrift:16-19       enum DistanceMetric { L2, Cosine, InnerProduct }
  * Only the coarse quantizer, its training, the inverted lists and the probed scan are here.  Product quantisation
- * (codebooks, ADC tables, `ht`, `quantizer_kfactor_rf`) is not: it would replace the list payload and the scan's inner
- * product, nothing else.
+ * (codebooks, ADC tables) replaces the list payload and the scan's inner product, nothing else: that index is
+ * ivfpq_ann.h.  `ht` and `quantizer_kfactor_rf` are in neither.
  *
  * Arithmetic: as in dense_ann.h.  Rows, queries and centroids are rounded to fp16 (Cosine: L2-normalised first, the
  * index then behaves as InnerProduct), products accumulate in fp32 on the matrix cores.  Distances are those of

@@ -1,0 +1,274 @@
+// ivf_kernels.h -- what the two inverted-file indexes (ivf_ann.hip: flat lists; ivfpq_ann.hip: product-quantised lists)
+// share: row preparation, the small bookkeeping kernels of list construction and probe inversion, the survivor buffer's
+// arm / refine kernels with wg_kth_largest, and the device buffer Buf.  Moved here verbatim from ivf_ann.hip; a source
+// includes this once, after its hip_runtime / ivf_ann.h / sann_device.h includes.  Everything is file-local.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/ivf_ann.h"
+#include "ann_by_id_internal.h"
+
+namespace {
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float float16v __attribute__((ext_vector_type(16)));
+
+constexpr int CAP = 8192;  // survivors kept per query
+constexpr int MAX_K = 1024;
+constexpr int MAX_D = 512;
+constexpr int MAX_NLIST = 65536;
+constexpr int MAX_NPROBE = 1024;
+constexpr int CHUNK = ann_by_id::DANN_CHUNK;  // queries (or rows to assign) per coarse search
+constexpr int CELL_BITS = 17;                 // radix-sort key width of a cell number
+
+struct Survivor {
+  float score;
+  uint32_t slot;
+};
+struct Group {
+  uint32_t cell, p0, count;  // the queries of the group: pairs [p0, p0 + count) of the probe table sorted by cell
+};
+
+__device__ __forceinline__ uint32_t f2key(float f) {  // order-preserving float -> uint
+  uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key2f(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// rows (fp32, row-major) -> fp16 rows (row-major) and the sum of squares of the stored halves.  One wave per row; the
+// arithmetic of dense_ann.hip's prep_rows_kernel (Cosine: divide by the fp32 norm, then round).
+// ---------------------------------------------------------------------------------------------
+__global__ void store_rows_kernel(const float *__restrict__ src, int64_t n, int d, int normalise, _Float16 *__restrict__ flat,
+                                  float *__restrict__ sumsq) {
+  int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const float *x = src + row * d;
+  double ss = 0;
+  for (int k = lane; k < d; k += 64) ss += (double)x[k] * (double)x[k];
+  ss = wave_sum(ss);
+  float norm = 1.0f;
+  if (normalise) {
+    norm = (float)sqrt(ss);
+    if (!(norm > 0.0f)) norm = 1.0f;
+  }
+  double ss16 = 0;
+  for (int k = lane; k < d; k += 64) {
+    _Float16 hv = (_Float16)(x[k] / norm);
+    float back = (float)hv;
+    ss16 += (double)back * (double)back;
+    flat[row * d + k] = hv;
+  }
+  ss16 = wave_sum(ss16);
+  if (lane == 0) sumsq[row] = (float)ss16;
+}
+
+// fp16 rows -> the B-operand fragments of a query chunk: the coarse search's (S_c k-steps, zeroed by dann_chunk_open) and,
+// with own != NULL, the scan's (S = d / 16).  One thread per (row, 8-half piece).
+__global__ void frag_rows_kernel(const _Float16 *__restrict__ flat, const float *__restrict__ sumsq, int m, int d, int S_c,
+                                 _Float16 *__restrict__ qf_c, float *__restrict__ qsumsq, _Float16 *__restrict__ own) {
+  const int pieces = d >> 3;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)m * pieces) return;
+  const int row = (int)(e / pieces), c = (int)(e % pieces);
+  const half8 v = *(const half8 *)&flat[(size_t)row * d + c * 8];
+  const int g = row >> 5, r = row & 31, s = c >> 1, h = c & 1;
+  *(half8 *)&qf_c[((((size_t)g * S_c + s) * 64) + h * 32 + r) * 8] = v;
+  if (own) *(half8 *)&own[((((size_t)g * (d >> 4) + s) * 64) + h * 32 + r) * 8] = v;
+  if (c == 0) qsumsq[row] = sumsq[row];
+}
+
+__global__ void iota_kernel(uint32_t *__restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (uint32_t)i;
+}
+__global__ void iota64_kernel(int64_t *__restrict__ out, int64_t first, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = first + i;
+}
+// the coarse search's answer (k = 1) -> the cell of each row
+__global__ void cells_kernel(const int64_t *__restrict__ ids, int m, int32_t *__restrict__ cell) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) cell[i] = (int32_t)ids[i];
+}
+__global__ void gather_cells_kernel(const int32_t *__restrict__ cell, const uint32_t *__restrict__ perm, int64_t n,
+                                    uint32_t *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (uint32_t)cell[perm ? perm[i] : i];
+}
+__global__ void hist_kernel(const uint32_t *__restrict__ keys, int64_t n, uint32_t *__restrict__ hist) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) atomicAdd(&hist[keys[i]], 1u);
+}
+__global__ void blocks_of_kernel(const uint32_t *__restrict__ sizes, int n, uint32_t *__restrict__ nblk) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) nblk[i] = (sizes[i] + 31u) >> 5;
+}
+
+__global__ void fill_kernel(float *__restrict__ p, int64_t n, float v) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k-means
+// ---------------------------------------------------------------------------------------------
+__global__ void pick_rows_kernel(const _Float16 *__restrict__ flat, const int64_t *__restrict__ picks, int nlist, int d,
+                                 float *__restrict__ cent) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)nlist * d) return;
+  cent[e] = (float)flat[(size_t)picks[e / d] * d + e % d];
+}
+// InnerProduct: the initial picks scaled to unit length, as every later centroid is.  One wave per centroid.
+__global__ void unit_rows_kernel(float *__restrict__ cent, int nlist, int d) {
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nlist) return;
+  float *x = cent + (size_t)row * d;
+  double ss = 0;
+  for (int k = lane; k < d; k += 64) ss += (double)x[k] * (double)x[k];
+  ss = wave_sum(ss);
+  if (!(ss > 0)) return;
+  const double scale = 1.0 / sqrt(ss);
+  for (int k = lane; k < d; k += 64) x[k] = (float)((double)x[k] * scale);
+}
+
+// ---------------------------------------------------------------------------------------------
+// probe inversion
+// ---------------------------------------------------------------------------------------------
+// the coarse search's answer [m][nprobe] -> the probe export, the (cell, query) pairs and the number of queries per cell
+__global__ void probes_kernel(const int64_t *__restrict__ ids, int m, int nprobe, int32_t *__restrict__ probes,
+                              uint32_t *__restrict__ pair_cell, uint32_t *__restrict__ pair_q, uint32_t *__restrict__ per_cell) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)m * nprobe) return;
+  const uint32_t c = (uint32_t)ids[e];
+  probes[e] = (int32_t)c;
+  pair_cell[e] = c;
+  pair_q[e] = (uint32_t)(e / nprobe);
+  atomicAdd(&per_cell[c], 1u);
+}
+// one thread per cell: its groups of <= 32 queries, and its share of the rows scanned (integers: any order gives the sum)
+__global__ void groups_kernel(const uint32_t *__restrict__ per_cell, const uint32_t *__restrict__ pstart,
+                              const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ sizes, int nlist,
+                              Group *__restrict__ groups, unsigned long long *__restrict__ rows_scanned) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nlist) return;
+  const uint32_t cnt = per_cell[c];
+  if (cnt == 0) return;
+  for (uint32_t g = 0; g * 32 < cnt; ++g) groups[gstart[c] + g] = Group{(uint32_t)c, pstart[c] + g * 32, min(32u, cnt - g * 32)};
+  atomicAdd(rows_scanned, (unsigned long long)cnt * sizes[c]);
+}
+
+// k-th largest of n floats (stride in floats), one workgroup, 4 radix passes over an LDS histogram (as dense_ann.hip)
+__device__ float wg_kth_largest(const float *vals, int64_t n, int stride, int k, uint32_t *hist /*[258]*/) {
+  uint32_t prefix = 0, mask = 0;
+  uint32_t want = (uint32_t)k;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+      uint32_t key = f2key(vals[i * stride]);
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t acc = 0;
+      int dgt = 255;
+      for (; dgt > 0; --dgt) {
+        if (acc + hist[dgt] >= want) break;
+        acc += hist[dgt];
+      }
+      hist[256] = (uint32_t)dgt;
+      hist[257] = want - acc;
+    }
+    __syncthreads();
+    prefix |= hist[256] << shift;
+    mask |= 255u << shift;
+    want = hist[257];
+    __syncthreads();
+  }
+  return key2f(prefix);
+}
+
+// after a scan round: a query whose candidates fitted is finished (tau = +inf); one that overflowed is re-armed with the
+// k-th largest buffered score.  flags: 1 = another round, 2 = cannot tighten (more than CAP scores tie at the k-th).
+__global__ void refine_kernel(float *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ done_cnt,
+                              const Survivor *__restrict__ surv, int k, int *__restrict__ flags) {
+  __shared__ uint32_t hist[258];
+  const int q = blockIdx.x;
+  if (done_cnt[q] != 0xffffffffu) return;  // finished in an earlier round
+  const uint32_t c = cnt[q];
+  if (c <= (uint32_t)CAP) {
+    if (threadIdx.x == 0) {
+      done_cnt[q] = c;
+      tau[q] = INFINITY;
+    }
+    return;
+  }
+  const float old = tau[q];
+  const float nt = wg_kth_largest(&surv[(size_t)q * CAP].score, CAP, 2, k, hist);
+  if (threadIdx.x == 0) {
+    if (nt > old) {
+      tau[q] = nt;
+      cnt[q] = 0;
+      atomicOr(&flags[0], 1);
+    } else {
+      tau[q] = INFINITY;
+      atomicOr(&flags[0], 2);
+    }
+  }
+}
+__global__ void arm_kernel(float *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ done_cnt, int nq) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  tau[q] = -INFINITY;
+  cnt[q] = 0;
+  done_cnt[q] = 0xffffffffu;
+}
+
+struct Buf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  ~Buf() { if (p) (void)hipFree(p); }
+  hipError_t reserve(size_t n) {
+    if (n <= bytes) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    hipError_t e = hipMalloc(&p, n ? n : 8);
+    if (e == hipSuccess) bytes = n ? n : 8;
+    return e;
+  }
+  // growth that keeps the first `keep` bytes (device to device)
+  hipError_t grow_keep(size_t keep, size_t want) {
+    if (p && want <= bytes) return hipSuccess;
+    void *np = nullptr;
+    hipError_t e = hipMalloc(&np, want ? want : 8);
+    if (e != hipSuccess) return e;
+    if (keep && p) {
+      e = hipMemcpy(np, p, keep, hipMemcpyDeviceToDevice);
+      if (e != hipSuccess) {
+        (void)hipFree(np);
+        return e;
+      }
+    }
+    if (p) (void)hipFree(p);
+    p = np;
+    bytes = want ? want : 8;
+    return hipSuccess;
+  }
+  template <class T> T *as() const { return (T *)p; }
+};
+
+inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
+}  // namespace

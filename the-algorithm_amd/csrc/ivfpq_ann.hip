@@ -1,0 +1,911 @@
+// ivfpq_ann.hip -- inverted-file index with product-quantised lists (`IVF<nlist>,PQ<M>` in an id map) for gfx950.
+//
+// What it replaces: the reference's Faiss queryable as production configures it (ann_common.thrift:45: nprobe is "How many
+// cells to visit in IVFPQ"; FaissIndexer.scala:82-92 hands any factory string to index_factory).  The contract is
+// include/ivfpq_ann.h; the coarse half is that of ivf_ann.hip, whose kernels for it are shared through ivf_kernels.h.
+//
+// Shape of the computation.
+//   * The coarse quantizer is a dann_index over the centroids, used through the prepared-search seam exactly as
+//     ivf_ann.hip uses it.  ivfpq_index_train obtains the centroids from ivf_index_train, so the two index types train
+//     the same cells from the same arguments.
+//   * The rows are not kept.  An add prepares a slab of rows (fp16), assigns it, encodes it and keeps M code bytes, the id
+//     and the cell per row, in the order added.  The lists are laid out again from that: every list starts on a block of
+//     64 rows, a block is [M / 4][64] dwords -- lane r of a wave reads the four codes 4g .. 4g + 3 of row r with one
+//     coalesced 256-byte load -- in (cell, id) order, beside the slot's rank in id order.
+//   * encode_kernel: one workgroup per (64 rows, subspace).  The residuals r = fl32(x - centroid[cell]) of the tile go to
+//     LDS, the subspace's codebook is staged through LDS 64 codewords at a time; wave w evaluates codewords 16w .. 16w+15
+//     of the stage (the codeword is a broadcast LDS read), a lane owns a row.  Codebook training uses the same kernel
+//     for its assignment step, and pq_mean_kernel (one workgroup per codeword, members compacted in position order,
+//     summed in fp64 by one thread per component) for the means.
+//   * adc_scan_kernel, the hot path: one workgroup per (query, probed cell) pair, the pairs sorted by cell so that
+//     neighbouring workgroups read the same list from L2.  The workgroup builds the pair's table [M][256] in LDS
+//     (thread j owns codeword j of every subspace), then its four waves stride over the list's blocks; a lane owns a
+//     row and adds M table entries in ascending m, starting from 0 (L2) or <q, c> (InnerProduct / Cosine).  Survivors
+//     go to the per-query buffer of ivf_ann.hip (CAP = 8192, one integer atomic per wave and block), with its arm / refine
+//     rounds.
+//   * Select sorts a query's survivors by (score desc, rank in id order asc), as ivf_ann.hip's select does.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#include "../../include/dense_ann.h"
+#include "../../include/ivf_ann.h"
+#include "../../include/ivfpq_ann.h"
+#include "sann_device.h"  // mix64
+#include "abi_guard.h"
+#include "ann_by_id_internal.h"
+#include "ivf_kernels.h"
+#define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
+
+namespace {
+
+thread_local std::string g_err;
+int fail(int code, const std::string &m) {
+  g_err = m;
+  return code;
+}
+#define ITRY(expr)                                                                                \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) return fail(IVF_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+// a call into dense_ann.hip: its status codes carry the same numbers, its message is in dann_last_error()
+#define DCALL(expr)                                              \
+  do {                                                           \
+    int rc_ = (expr);                                            \
+    if (rc_) return fail(rc_, std::string("coarse quantizer: ") + dann_last_error()); \
+  } while (0)
+
+constexpr int KSUB = 256;    // codewords per sub-quantizer
+constexpr int MAX_M = 64;
+constexpr int LBLOCK = 64;   // rows per list block
+constexpr int ENC_ROWS = 64; // rows per encoder workgroup
+constexpr int ENC_STAGE = 64;  // codewords staged in LDS at a time
+
+// ---------------------------------------------------------------------------------------------
+// encoder: code[row][m] = argmin_j ||r_m - cb[m][j]||^2 in fp32, ties to the lower j.  grid (row tiles, M), 256 threads.
+// The code of (row, m) is written at codes[row * row_stride + m * m_stride]: [n][M] for an add, [M][n] for training.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void encode_kernel(const _Float16 *__restrict__ flat, const int32_t *__restrict__ cell,
+                                                     const float *__restrict__ cent, const float *__restrict__ cb, int64_t n,
+                                                     int d, int dsub, uint8_t *__restrict__ codes, int64_t row_stride,
+                                                     int64_t m_stride) {
+  extern __shared__ float enc_lds[];
+  float *s_r = enc_lds;                     // [dsub][ENC_ROWS]
+  float *s_cb = enc_lds + dsub * ENC_ROWS;  // [ENC_STAGE][dsub]
+  __shared__ float s_best[4][ENC_ROWS];
+  __shared__ int s_arg[4][ENC_ROWS];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, m = blockIdx.y;
+  const int64_t row0 = (int64_t)blockIdx.x * ENC_ROWS;
+  for (int e = t; e < dsub * ENC_ROWS; e += 256) {
+    const int r = e / dsub, i = e % dsub;
+    const int64_t row = row0 + r;
+    float v = 0.0f;
+    if (row < n) v = (float)flat[(size_t)row * d + m * dsub + i] - cent[(size_t)cell[row] * d + m * dsub + i];
+    s_r[i * ENC_ROWS + r] = v;
+  }
+  float best = INFINITY;
+  int arg = 0;
+  const float *cbm = cb + (size_t)m * KSUB * dsub;
+  for (int j0 = 0; j0 < KSUB; j0 += ENC_STAGE) {
+    __syncthreads();
+    for (int e = t; e < ENC_STAGE * dsub; e += 256) s_cb[e] = cbm[(size_t)j0 * dsub + e];
+    __syncthreads();
+    for (int jj = 0; jj < 16; jj += 4) {
+      const float *c0 = s_cb + (w * 16 + jj) * dsub;
+      float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+      for (int i = 0; i < dsub; ++i) {
+        const float r = s_r[i * ENC_ROWS + lane];
+        const float e0 = r - c0[i], e1 = r - c0[dsub + i], e2 = r - c0[2 * dsub + i], e3 = r - c0[3 * dsub + i];
+        a0 += e0 * e0;
+        a1 += e1 * e1;
+        a2 += e2 * e2;
+        a3 += e3 * e3;
+      }
+      const int j = j0 + w * 16 + jj;
+      if (a0 < best) { best = a0; arg = j; }
+      if (a1 < best) { best = a1; arg = j + 1; }
+      if (a2 < best) { best = a2; arg = j + 2; }
+      if (a3 < best) { best = a3; arg = j + 3; }
+    }
+  }
+  s_best[w][lane] = best;
+  s_arg[w][lane] = arg;
+  __syncthreads();
+  if (w == 0 && row0 + lane < n) {
+#pragma unroll
+    for (int u = 1; u < 4; ++u) {
+      const float b = s_best[u][lane];
+      const int a = s_arg[u][lane];
+      if (b < best || (b == best && a < arg)) {
+        best = b;
+        arg = a;
+      }
+    }
+    codes[(row0 + lane) * row_stride + m * m_stride] = (uint8_t)arg;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// codebook training
+// ---------------------------------------------------------------------------------------------
+// the initial codewords: cb[m][j] = the m-th piece of the residual of training row picks[m][j]
+__global__ void pq_pick_kernel(const _Float16 *__restrict__ flat, const int32_t *__restrict__ cell, const float *__restrict__ cent,
+                               const int64_t *__restrict__ picks, int M, int d, int dsub, float *__restrict__ cb) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)M * KSUB * dsub) return;
+  const int i = (int)(e % dsub), m = (int)(e / ((int64_t)KSUB * dsub));
+  const int64_t row = picks[e / dsub];
+  cb[e] = (float)flat[(size_t)row * d + m * dsub + i] - cent[(size_t)cell[row] * d + m * dsub + i];
+}
+
+// One workgroup per codeword (j, m): the rows that carry it are found 256 at a time and compacted in position order;
+// component i of the mean is then summed by thread i over them, in fp64 -- a fixed order, no floating-point atomics.
+// A codeword without members keeps its value.  codes are [M][n].
+__global__ __launch_bounds__(256) void pq_mean_kernel(const _Float16 *__restrict__ flat, const int32_t *__restrict__ cell,
+                                                      const float *__restrict__ cent, const uint8_t *__restrict__ codes, int64_t n,
+                                                      int d, int dsub, float *__restrict__ cb) {
+  __shared__ uint32_t s_rows[256];
+  __shared__ uint32_t s_wcnt[4];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, j = blockIdx.x, m = blockIdx.y;
+  const uint8_t *cm = codes + (size_t)m * n;
+  double acc = 0.0;
+  uint32_t members = 0;
+  for (int64_t r0 = 0; r0 < n; r0 += 256) {
+    const int64_t row = r0 + t;
+    const bool mine = row < n && cm[row] == (uint8_t)j;
+    const unsigned long long mask = __ballot(mine);
+    if (lane == 0) s_wcnt[w] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t base = 0;
+    for (int u = 0; u < w; ++u) base += s_wcnt[u];
+    const uint32_t total = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+    if (mine) s_rows[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)row;
+    __syncthreads();
+    if (t < dsub)
+      for (uint32_t u = 0; u < total; ++u) {
+        const uint32_t rr = s_rows[u];
+        const float r = (float)flat[(size_t)rr * d + m * dsub + t] - cent[(size_t)cell[rr] * d + m * dsub + t];
+        acc += (double)r;
+      }
+    members += total;
+    __syncthreads();
+  }
+  if (t < dsub && members > 0) cb[((size_t)m * KSUB + j) * dsub + t] = (float)(acc / (double)members);
+}
+
+// ---------------------------------------------------------------------------------------------
+// list construction: the codes of row j of the (cell, id) order go to its list's next slot.  One thread per (row, 4 codes).
+// ---------------------------------------------------------------------------------------------
+__global__ void scatter_codes_kernel(const uint32_t *__restrict__ codes4 /*[n][M/4]*/, int64_t n, int M4,
+                                     const uint32_t *__restrict__ cell_sorted, const uint32_t *__restrict__ ord,
+                                     const uint32_t *__restrict__ perm, const uint32_t *__restrict__ start,
+                                     const uint32_t *__restrict__ boff, uint32_t *__restrict__ lc, uint32_t *__restrict__ lrank) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * M4) return;
+  const int64_t j = e / M4;
+  const int g = (int)(e % M4);
+  const uint32_t c = cell_sorted[j], rank = ord[j], src = perm[rank];
+  const size_t slot = (size_t)boff[c] * LBLOCK + (size_t)(j - start[c]);
+  const size_t blk = slot / LBLOCK;
+  const int r = (int)(slot % LBLOCK);
+  lc[(blk * M4 + g) * LBLOCK + r] = codes4[(size_t)src * M4 + g];
+  if (g == 0) lrank[slot] = rank;
+}
+__global__ void blocks64_of_kernel(const uint32_t *__restrict__ sizes, int n, uint32_t *__restrict__ nblk) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) nblk[i] = (sizes[i] + (uint32_t)LBLOCK - 1u) / (uint32_t)LBLOCK;
+}
+// one thread per cell: its share of the rows scanned (integers: any order gives the sum)
+__global__ void rows_scanned_kernel(const uint32_t *__restrict__ per_cell, const uint32_t *__restrict__ sizes, int nlist,
+                                    unsigned long long *__restrict__ rows_scanned) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nlist) return;
+  const uint32_t cnt = per_cell[c];
+  if (cnt) atomicAdd(rows_scanned, (unsigned long long)cnt * sizes[c]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the ADC scan
+// ---------------------------------------------------------------------------------------------
+struct AdcArgs {
+  const uint32_t *lc;       // list codes [block][M/4][64]
+  const uint32_t *boff;     // first block of a cell's list
+  const uint32_t *sizes;    // its rows
+  const _Float16 *q16;      // prepared queries of the chunk, row-major [nq][d]
+  const float *cent;        // centroids, fp32 [nlist][d]
+  const float *cb;          // codebooks [M][256][dsub]
+  const uint32_t *pair_cell, *pair_q;  // the pairs sorted by cell
+  const float *tau;         // [nq]: emit scores >= tau; +inf = the query is finished
+  uint32_t *cnt;            // [nq]
+  Survivor *surv;           // [nq][CAP]
+  int d, M, dsub, metric;
+};
+
+__global__ __launch_bounds__(256) void adc_scan_kernel(AdcArgs a) {
+  extern __shared__ float adc_lds[];
+  float *s_tab = adc_lds;               // [M][256]
+  float *s_u = adc_lds + a.M * KSUB;    // [d]: q - centroid (L2) or q
+  __shared__ float s_qc;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int d = a.d, M = a.M, dsub = a.dsub;
+  const uint32_t cell = a.pair_cell[blockIdx.x], q = a.pair_q[blockIdx.x];
+  const uint32_t size = a.sizes[cell];
+  const float thr = a.tau[q];
+  if (size == 0 || !(thr < INFINITY)) return;  // an empty list, or a fallback round this query is not part of
+  const bool l2 = a.metric == IVF_METRIC_L2;
+  const _Float16 *qp = a.q16 + (size_t)q * d;
+  const float *cp = a.cent + (size_t)cell * d;
+  for (int i = t; i < d; i += 256) s_u[i] = l2 ? (float)qp[i] - cp[i] : (float)qp[i];
+  if (w == 0) {
+    // <q, c>: lane l sums the products of components l, l + 64, ... in ascending order, then a fixed shuffle tree
+    float p = 0.0f;
+    if (!l2)
+      for (int i = lane; i < d; i += 64) p += (float)qp[i] * cp[i];
+    for (int o = 32; o; o >>= 1) p += __shfl_xor(p, o, 64);
+    if (lane == 0) s_qc = p;
+  }
+  __syncthreads();
+  // the table: thread j owns codeword j of every subspace, components in ascending order
+  for (int m = 0; m < M; ++m) {
+    const float *cw = a.cb + ((size_t)m * KSUB + t) * dsub;
+    const float *u = s_u + m * dsub;
+    float acc = 0.0f;
+    if ((dsub & 3) == 0) {
+      for (int i = 0; i < dsub; i += 4) {
+        const float4 c4 = *(const float4 *)(cw + i);
+        if (l2) {
+          const float e0 = u[i] - c4.x, e1 = u[i + 1] - c4.y, e2 = u[i + 2] - c4.z, e3 = u[i + 3] - c4.w;
+          acc += e0 * e0;
+          acc += e1 * e1;
+          acc += e2 * e2;
+          acc += e3 * e3;
+        } else {
+          acc += u[i] * c4.x;
+          acc += u[i + 1] * c4.y;
+          acc += u[i + 2] * c4.z;
+          acc += u[i + 3] * c4.w;
+        }
+      }
+    } else {
+      for (int i = 0; i < dsub; ++i) {
+        if (l2) {
+          const float e = u[i] - cw[i];
+          acc += e * e;
+        } else {
+          acc += u[i] * cw[i];
+        }
+      }
+    }
+    s_tab[m * KSUB + t] = acc;
+  }
+  __syncthreads();
+  const float acc0 = l2 ? 0.0f : s_qc;
+  const int M4 = M >> 2;
+  const uint32_t b0 = a.boff[cell], nb = (size + (uint32_t)LBLOCK - 1u) / (uint32_t)LBLOCK;
+  for (uint32_t blk = w; blk < nb; blk += 4) {
+    const size_t gb = (size_t)b0 + blk;
+    const uint32_t *cp4 = a.lc + gb * M4 * LBLOCK + lane;
+    float acc = acc0;
+    for (int g = 0; g < M4; ++g) {
+      const uint32_t c4 = cp4[(size_t)g * LBLOCK];
+      const float *tb = s_tab + (g * 4) * KSUB;
+      acc += tb[c4 & 255u];
+      acc += tb[KSUB + ((c4 >> 8) & 255u)];
+      acc += tb[2 * KSUB + ((c4 >> 16) & 255u)];
+      acc += tb[3 * KSUB + (c4 >> 24)];
+    }
+    const float score = l2 ? -acc : acc;
+    // the wave's survivors take consecutive slots, reserved by one integer atomic of its first surviving lane
+    const bool pass = blk * (uint32_t)LBLOCK + (uint32_t)lane < size && score >= thr;
+    const unsigned long long mask = __ballot(pass);
+    if (mask == 0) continue;
+    const int leader = __ffsll((long long)mask) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(&a.cnt[q], (uint32_t)__popcll(mask));
+    base = __shfl(base, leader, 64);
+    const uint32_t pos = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (pass && pos < (uint32_t)CAP) a.surv[(size_t)q * CAP + pos] = Survivor{score, (uint32_t)(gb * LBLOCK) + (uint32_t)lane};
+  }
+}
+
+// per query: sort survivors by (score desc, rank in id order asc), emit the k nearest as distances (ivf_ann.hip's select
+// with this index's scores: -s for L2, the similarity otherwise)
+__global__ __launch_bounds__(512) void pq_select_kernel(const Survivor *__restrict__ surv, const uint32_t *__restrict__ done_cnt,
+                                                        const uint32_t *__restrict__ lrank, const int64_t *__restrict__ ids_sorted,
+                                                        int metric, int k, float *__restrict__ out_dist,
+                                                        int64_t *__restrict__ out_ids, int32_t *__restrict__ out_counts) {
+  extern __shared__ unsigned long long keys[];
+  const int q = blockIdx.x;
+  const uint32_t c = min(done_cnt[q], (uint32_t)CAP);
+  uint32_t n2 = 64;
+  while (n2 < c) n2 <<= 1;
+  for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
+    unsigned long long key = 0;
+    if (i < c) {
+      Survivor s = surv[(size_t)q * CAP + i];
+      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - lrank[s.slot]);
+    }
+    keys[i] = key;
+  }
+  __syncthreads();
+  for (uint32_t size = 2; size <= n2; size <<= 1)
+    for (uint32_t str = size >> 1; str > 0; str >>= 1) {
+      for (uint32_t i = threadIdx.x; i < n2 / 2; i += blockDim.x) {
+        uint32_t lo = 2 * i - (i & (str - 1));
+        uint32_t hi = lo + str;
+        bool desc = (lo & size) == 0;
+        unsigned long long x = keys[lo], y = keys[hi];
+        if ((x < y) == desc) {
+          keys[lo] = y;
+          keys[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  const uint32_t m = min(c, (uint32_t)k);
+  for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
+    float dist = 0.0f;
+    int64_t id = 0;
+    if (i < m) {
+      unsigned long long key = keys[i];
+      float sc = key2f((uint32_t)(key >> 32));
+      id = ids_sorted[0xffffffffu - (uint32_t)key];
+      if (metric == IVF_METRIC_L2) dist = sqrtf(fmaxf(0.0f, -sc));
+      else dist = 1.0f - sc;
+    }
+    out_dist[(size_t)q * k + i] = dist;
+    out_ids[(size_t)q * k + i] = id;
+  }
+  if (threadIdx.x == 0) out_counts[q] = (int32_t)m;
+}
+
+}  // namespace
+
+struct ivfpq_index {
+  int device = 0, metric = 0, d = 0, nlist = 0, M = 0, dsub = 0;
+  int64_t n = 0;
+  int ids_mode = -1;  // -1: no add yet; 0: ids are positions; 1: ids given
+  dann_index *coarse = nullptr;
+  Buf cent, cb;  // centroids fp32 [nlist][d] (the stored fp16 values), codebooks fp32 [M][256][dsub]
+  // per row, in the order added
+  Buf codes, cell, ids;
+  // the lists
+  Buf ids_sorted, perm, cell_r, cell_sorted, ord, iota, sizes, start, nblk, boff, lc, lrank, sort_tmp;
+  std::vector<int64_t> h_sizes;
+  int64_t total_blocks = 0;
+  // per-call scratch
+  Buf stage, flat, sumsq, c_dist, c_ids, c_cnt, q16, qsumsq;
+  Buf pair_cell, pair_q, pair_cell_s, pair_q_s, per_cell, rows_acc;
+  Buf tau, cnt, done_cnt, surv, flags, o_dist, o_ids, o_cnt;
+  // the last search
+  Buf probes;
+  int32_t last_nq = 0, last_nprobe = 0, last_rounds = 0;
+  int64_t last_rows = 0;
+  float t_coarse = 0, t_scan = 0, t_sel = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~ivfpq_index() {
+    if (coarse) (void)dann_index_destroy(coarse);
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+namespace {
+
+int check_shape(int32_t metric, int32_t d, int32_t nlist, int32_t M) {
+  if (metric < IVF_METRIC_L2 || metric > IVF_METRIC_INNER_PRODUCT) return fail(IVF_EINVAL, "unknown metric");
+  if (d < 16 || d > MAX_D || d % 16) return fail(IVF_EINVAL, "dimension must be a multiple of 16 in 16..512");
+  if (nlist < 1 || nlist > MAX_NLIST) return fail(IVF_EINVAL, "nlist must be in 1..65536");
+  if (M < 4 || M > MAX_M || M % 4) return fail(IVF_EINVAL, "M must be a multiple of 4 in 4..64");
+  if (d % M) return fail(IVF_EINVAL, "M must divide the dimension");
+  return IVF_OK;
+}
+
+size_t encode_lds_bytes(int dsub) { return (size_t)(ENC_ROWS + ENC_STAGE) * dsub * sizeof(float); }
+size_t adc_lds_bytes(int M, int d) { return ((size_t)M * KSUB + d) * sizeof(float); }
+
+int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, std::unique_ptr<ivfpq_index> &ix) {
+  ITRY(hipSetDevice(device));
+  ix.reset(new ivfpq_index);
+  ix->device = device;
+  ix->metric = metric;
+  ix->d = d;
+  ix->nlist = nlist;
+  ix->M = M;
+  ix->dsub = d / M;
+  ix->h_sizes.assign((size_t)nlist, 0);
+  for (auto &e : ix->ev) ITRY(hipEventCreate(&e));
+  for (Buf *b : {&ix->sizes, &ix->start, &ix->nblk, &ix->boff}) {
+    ITRY(b->reserve((size_t)nlist * 4));
+    ITRY(hipMemset(b->p, 0, (size_t)nlist * 4));
+  }
+  ITRY(ix->cent.reserve((size_t)nlist * d * sizeof(float)));
+  ITRY(ix->cb.reserve((size_t)M * KSUB * ix->dsub * sizeof(float)));
+  // both kernels size their LDS by the shape: up to 64 KiB (encoder, dsub = 128) and 66 KiB (scan, M = 64, d = 512)
+  ITRY(hipFuncSetAttribute((const void *)encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)encode_lds_bytes(MAX_D / 4)));
+  ITRY(hipFuncSetAttribute((const void *)adc_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)adc_lds_bytes(MAX_M, MAX_D)));
+  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
+  return IVF_OK;
+}
+
+// the coarse quantizer over the given centroids (host, fp32 [nlist][d]); the index keeps the values it stores as fp32
+int set_centroids(ivfpq_index *ix, const float *centroids) {
+  const size_t bytes = (size_t)ix->nlist * ix->d * sizeof(float);
+  ITRY(hipMemcpy(ix->cent.p, centroids, bytes, hipMemcpyHostToDevice));
+  dann_index *c = nullptr;
+  DCALL(ann_by_id::dann_build_device(ix->device, ix->metric, ix->nlist, ix->d, ix->cent.as<float>(), &c));
+  if (ix->coarse) (void)dann_index_destroy(ix->coarse);
+  ix->coarse = c;
+  std::vector<float> stored((size_t)ix->nlist * ix->d);
+  DCALL(dann_index_get_vectors(ix->coarse, 0, ix->nlist, stored.data()));
+  ITRY(hipMemcpy(ix->cent.p, stored.data(), bytes, hipMemcpyHostToDevice));
+  return IVF_OK;
+}
+
+// stable sort of n (cell number, value) pairs by cell
+int sort_by_cell(ivfpq_index *ix, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out, int64_t n) {
+  size_t tb = 0;
+  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
+  ITRY(ix->sort_tmp.reserve(tb));
+  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
+  return IVF_OK;
+}
+int exclusive_sum(ivfpq_index *ix, const uint32_t *in, uint32_t *out, int n) {
+  size_t tb = 0;
+  ITRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, (hipStream_t)0));
+  ITRY(ix->sort_tmp.reserve(tb));
+  ITRY(hipcub::DeviceScan::ExclusiveSum(ix->sort_tmp.p, tb, in, out, n, (hipStream_t)0));
+  return IVF_OK;
+}
+
+// the nearest centroid of each of n fp16 rows (the coarse search with k = 1, CHUNK rows at a time) -> cell[0 .. n)
+int assign_rows(ivfpq_index *ix, const _Float16 *flat, const float *sumsq, int64_t n, int32_t *cell) {
+  ann_by_id::DannTarget tgt;
+  DCALL(ann_by_id::dann_open(ix->coarse, 1, false, &tgt));
+  ITRY(ix->c_dist.reserve((size_t)CHUNK * sizeof(float)));
+  ITRY(ix->c_ids.reserve((size_t)CHUNK * sizeof(int64_t)));
+  ITRY(ix->c_cnt.reserve((size_t)CHUNK * sizeof(int32_t)));
+  const int d = ix->d;
+  for (int64_t r0 = 0; r0 < n; r0 += CHUNK) {
+    const int m = (int)std::min<int64_t>(CHUNK, n - r0);
+    ann_by_id::DannChunk ch;
+    DCALL(ann_by_id::dann_chunk_open(ix->coarse, m, 1, &ch));
+    hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)m * (d >> 3))), dim3(256), 0, 0, flat + (size_t)r0 * d,
+                       sumsq + r0, m, d, tgt.S, ch.qf, ch.qsumsq, (_Float16 *)nullptr);
+    ITRY(hipGetLastError());
+    int64_t d2h = 0;
+    DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, m, 1, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
+                                                ix->c_cnt.as<int32_t>(), &d2h));
+    hipLaunchKernelGGL(cells_kernel, dim3(blocks_for(m)), dim3(256), 0, 0, ix->c_ids.as<int64_t>(), m, cell + r0);
+    ITRY(hipGetLastError());
+  }
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+}
+
+int encode_rows(ivfpq_index *ix, const _Float16 *flat, const int32_t *cell, int64_t n, uint8_t *codes, int64_t row_stride,
+                int64_t m_stride) {
+  if (n == 0) return IVF_OK;
+  hipLaunchKernelGGL(encode_kernel, dim3(blocks_for(n, ENC_ROWS), ix->M), dim3(256), encode_lds_bytes(ix->dsub), 0, flat, cell,
+                     ix->cent.as<float>(), ix->cb.as<float>(), n, ix->d, ix->dsub, codes, row_stride, m_stride);
+  ITRY(hipGetLastError());
+  return IVF_OK;
+}
+
+// host rows [r0, r0 + m) -> fp16 rows and their sums of squares at the front of `flat` / `sumsq`
+int prepare_slab(ivfpq_index *ix, const float *rows, int64_t m, Buf &flat, Buf &sumsq, int64_t at) {
+  const int d = ix->d;
+  ITRY(ix->stage.reserve((size_t)m * d * sizeof(float)));
+  ITRY(hipMemcpy(ix->stage.p, rows, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, ix->stage.as<float>(), m, d,
+                     ix->metric == IVF_METRIC_COSINE ? 1 : 0, flat.as<_Float16>() + (size_t)at * d, sumsq.as<float>() + at);
+  ITRY(hipGetLastError());
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+}
+int64_t slab_rows(int d) { return std::max<int64_t>(1, (int64_t)(64 << 20) / (d * 4)); }
+
+// all lists again from the codes in the order added: (cell, id) order, every list on a block boundary
+int layout_lists(ivfpq_index *ix) {
+  const int64_t n = ix->n;
+  const int nlist = ix->nlist, M4 = ix->M >> 2;
+  // rank in (id, position) order: ids_sorted[rank], perm[rank] = position
+  ITRY(ix->ids_sorted.reserve((size_t)n * 8));
+  ITRY(ix->perm.reserve((size_t)n * 4));
+  ITRY(ix->iota.reserve((size_t)n * 4));
+  hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->iota.as<uint32_t>(), n);
+  ITRY(hipGetLastError());
+  size_t tb = 0;
+  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const uint32_t *)nullptr,
+                                          (uint32_t *)nullptr, (int)n, 0, 64, (hipStream_t)0));
+  ITRY(ix->sort_tmp.reserve(tb));
+  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, ix->ids.as<int64_t>(), ix->ids_sorted.as<int64_t>(),
+                                          ix->iota.as<uint32_t>(), ix->perm.as<uint32_t>(), (int)n, 0, 64, (hipStream_t)0));
+  ITRY(hipDeviceSynchronize());  // (the sorts below may replace sort_tmp)
+  // ranks by (cell, rank)
+  ITRY(ix->cell_r.reserve((size_t)n * 4));
+  ITRY(ix->cell_sorted.reserve((size_t)n * 4));
+  ITRY(ix->ord.reserve((size_t)n * 4));
+  ITRY(hipMemset(ix->sizes.p, 0, (size_t)nlist * 4));
+  hipLaunchKernelGGL(gather_cells_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell.as<int32_t>(), ix->perm.as<uint32_t>(), n,
+                     ix->cell_r.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = sort_by_cell(ix, ix->cell_r.as<uint32_t>(), ix->cell_sorted.as<uint32_t>(), ix->iota.as<uint32_t>(),
+                            ix->ord.as<uint32_t>(), n))
+    return rc;
+  hipLaunchKernelGGL(hist_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell_r.as<uint32_t>(), n, ix->sizes.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = exclusive_sum(ix, ix->sizes.as<uint32_t>(), ix->start.as<uint32_t>(), nlist)) return rc;
+  hipLaunchKernelGGL(blocks64_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, 0, ix->sizes.as<uint32_t>(), nlist, ix->nblk.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = exclusive_sum(ix, ix->nblk.as<uint32_t>(), ix->boff.as<uint32_t>(), nlist)) return rc;
+  std::vector<uint32_t> hs((size_t)nlist);
+  ITRY(hipMemcpy(hs.data(), ix->sizes.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
+  int64_t blocks = 0;
+  for (int c = 0; c < nlist; ++c) {
+    ix->h_sizes[(size_t)c] = hs[(size_t)c];
+    blocks += (hs[(size_t)c] + LBLOCK - 1) / LBLOCK;
+  }
+  if (blocks * LBLOCK >= (int64_t)0xffffff00u) return fail(IVF_ELIMIT, "the lists would hold 2^32 slots or more");
+  ix->total_blocks = blocks;
+  const size_t slots = (size_t)blocks * LBLOCK;
+  ITRY(ix->lc.reserve(slots * M4 * sizeof(uint32_t)));
+  ITRY(ix->lrank.reserve(slots * sizeof(uint32_t)));
+  ITRY(hipMemset(ix->lc.p, 0, slots * M4 * sizeof(uint32_t)));
+  ITRY(hipMemset(ix->lrank.p, 0, slots * sizeof(uint32_t)));
+  hipLaunchKernelGGL(scatter_codes_kernel, dim3(blocks_for(n * M4)), dim3(256), 0, 0, ix->codes.as<uint32_t>(), n, M4,
+                     ix->cell_sorted.as<uint32_t>(), ix->ord.as<uint32_t>(), ix->perm.as<uint32_t>(), ix->start.as<uint32_t>(),
+                     ix->boff.as<uint32_t>(), ix->lc.as<uint32_t>(), ix->lrank.as<uint32_t>());
+  ITRY(hipGetLastError());
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+}
+
+// the M codebooks on the residuals of the n prepared training rows
+int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq, int64_t n, int rounds, uint64_t seed) {
+  const int M = ix->M, d = ix->d, dsub = ix->dsub;
+  Buf tcell, tcodes, picks_d;
+  ITRY(tcell.reserve((size_t)n * 4));
+  ITRY(tcodes.reserve((size_t)n * M));
+  if (int rc = assign_rows(ix, tflat, tsumsq, n, tcell.as<int32_t>())) return rc;
+  std::vector<int64_t> picks;
+  picks.reserve((size_t)M * KSUB);
+  for (int m = 0; m < M; ++m) {
+    std::unordered_set<int64_t> seen;
+    const uint64_t base = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(m + 1);
+    for (uint64_t t = 0; (int)seen.size() < KSUB; ++t) {
+      const int64_t r = (int64_t)(sann::mix64(base + t) % (uint64_t)n);
+      if (seen.insert(r).second) picks.push_back(r);
+    }
+  }
+  ITRY(picks_d.reserve(picks.size() * 8));
+  ITRY(hipMemcpy(picks_d.p, picks.data(), picks.size() * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pq_pick_kernel, dim3(blocks_for((int64_t)M * KSUB * dsub)), dim3(256), 0, 0, tflat, tcell.as<int32_t>(),
+                     ix->cent.as<float>(), picks_d.as<int64_t>(), M, d, dsub, ix->cb.as<float>());
+  ITRY(hipGetLastError());
+  for (int it = 0; it < rounds; ++it) {
+    if (int rc = encode_rows(ix, tflat, tcell.as<int32_t>(), n, tcodes.as<uint8_t>(), 1, n)) return rc;
+    hipLaunchKernelGGL(pq_mean_kernel, dim3(KSUB, M), dim3(256), 0, 0, tflat, tcell.as<int32_t>(), ix->cent.as<float>(),
+                       tcodes.as<uint8_t>(), n, d, dsub, ix->cb.as<float>());
+    ITRY(hipGetLastError());
+  }
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+}
+
+int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
+                 int64_t *out_ids, int32_t *out_counts) {
+  const int d = ix->d, nlist = ix->nlist;
+  const int64_t np = (int64_t)nq * nprobe;
+  hipStream_t st = 0;
+  ann_by_id::DannTarget tgt;
+  DCALL(ann_by_id::dann_open(ix->coarse, nprobe, false, &tgt));
+  ann_by_id::DannChunk ch;
+  DCALL(ann_by_id::dann_chunk_open(ix->coarse, nq, nprobe, &ch));
+  ITRY(ix->stage.reserve((size_t)nq * d * sizeof(float)));
+  ITRY(ix->q16.reserve((size_t)nq * d * sizeof(_Float16)));
+  ITRY(ix->qsumsq.reserve((size_t)nq * sizeof(float)));
+  ITRY(ix->c_dist.reserve((size_t)np * sizeof(float)));
+  ITRY(ix->c_ids.reserve((size_t)np * sizeof(int64_t)));
+  ITRY(ix->c_cnt.reserve((size_t)std::max(nq, CHUNK) * sizeof(int32_t)));
+  ITRY(ix->pair_cell.reserve((size_t)np * 4));
+  ITRY(ix->pair_q.reserve((size_t)np * 4));
+  ITRY(ix->pair_cell_s.reserve((size_t)np * 4));
+  ITRY(ix->pair_q_s.reserve((size_t)np * 4));
+  ITRY(ix->per_cell.reserve((size_t)nlist * 4));
+  ITRY(ix->rows_acc.reserve(8));
+  ITRY(ix->tau.reserve((size_t)nq * 4));
+  ITRY(ix->cnt.reserve((size_t)nq * 4));
+  ITRY(ix->done_cnt.reserve((size_t)nq * 4));
+  ITRY(ix->flags.reserve(sizeof(int)));
+  ITRY(ix->surv.reserve((size_t)nq * CAP * sizeof(Survivor)));
+  ITRY(ix->o_dist.reserve((size_t)nq * k * sizeof(float)));
+  ITRY(ix->o_ids.reserve((size_t)nq * k * sizeof(int64_t)));
+  ITRY(ix->o_cnt.reserve((size_t)nq * sizeof(int32_t)));
+
+  // coarse: the nprobe nearest centroids of every query
+  ITRY(hipEventRecord(ix->ev[0], st));
+  ITRY(hipMemcpyAsync(ix->stage.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, ix->stage.as<float>(), (int64_t)nq, d,
+                     ix->metric == IVF_METRIC_COSINE ? 1 : 0, ix->q16.as<_Float16>(), ix->qsumsq.as<float>());
+  ITRY(hipGetLastError());
+  hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, ix->q16.as<_Float16>(),
+                     ix->qsumsq.as<float>(), nq, d, tgt.S, ch.qf, ch.qsumsq, (_Float16 *)nullptr);
+  ITRY(hipGetLastError());
+  int64_t d2h = 0;
+  DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, nq, nprobe, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
+                                              ix->c_cnt.as<int32_t>(), &d2h));
+
+  // inversion: (cell, query) pairs sorted by cell, one workgroup each
+  ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
+  ITRY(hipMemsetAsync(ix->rows_acc.p, 0, 8, st));
+  hipLaunchKernelGGL(probes_kernel, dim3(blocks_for(np)), dim3(256), 0, st, ix->c_ids.as<int64_t>(), nq, nprobe,
+                     ix->probes.as<int32_t>() + (size_t)q0 * nprobe, ix->pair_cell.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
+                     ix->per_cell.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = sort_by_cell(ix, ix->pair_cell.as<uint32_t>(), ix->pair_cell_s.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
+                            ix->pair_q_s.as<uint32_t>(), np))
+    return rc;
+  hipLaunchKernelGGL(rows_scanned_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(),
+                     ix->sizes.as<uint32_t>(), nlist, ix->rows_acc.as<unsigned long long>());
+  ITRY(hipGetLastError());
+  hipLaunchKernelGGL(arm_kernel, dim3(blocks_for(nq)), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
+                     ix->done_cnt.as<uint32_t>(), nq);
+  ITRY(hipGetLastError());
+  ITRY(hipEventRecord(ix->ev[1], st));
+
+  // scan rounds
+  AdcArgs a;
+  a.lc = ix->lc.as<uint32_t>();
+  a.boff = ix->boff.as<uint32_t>();
+  a.sizes = ix->sizes.as<uint32_t>();
+  a.q16 = ix->q16.as<_Float16>();
+  a.cent = ix->cent.as<float>();
+  a.cb = ix->cb.as<float>();
+  a.pair_cell = ix->pair_cell_s.as<uint32_t>();
+  a.pair_q = ix->pair_q_s.as<uint32_t>();
+  a.tau = ix->tau.as<float>();
+  a.cnt = ix->cnt.as<uint32_t>();
+  a.surv = ix->surv.as<Survivor>();
+  a.d = d;
+  a.M = ix->M;
+  a.dsub = ix->dsub;
+  a.metric = ix->metric;
+  int rounds = 0;
+  for (;; ++rounds) {
+    if (ix->n > 0) {
+      hipLaunchKernelGGL(adc_scan_kernel, dim3((unsigned)np), dim3(256), adc_lds_bytes(ix->M, d), st, a);
+      ITRY(hipGetLastError());
+    }
+    int flags = 0;
+    ITRY(hipMemsetAsync(ix->flags.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(refine_kernel, dim3(nq), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
+                       ix->done_cnt.as<uint32_t>(), ix->surv.as<Survivor>(), k, ix->flags.as<int>());
+    ITRY(hipGetLastError());
+    ITRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    ITRY(hipStreamSynchronize(st));
+    if (flags & 2) return fail(IVF_ELIMIT, "more than 8192 rows of the probed lists tie at the k-th distance of a query");
+    if (rounds >= 16) return fail(IVF_ELIMIT, "threshold refinement did not converge");
+    if (!(flags & 1)) break;
+  }
+  ITRY(hipEventRecord(ix->ev[2], st));
+
+  hipLaunchKernelGGL(pq_select_kernel, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
+                     ix->done_cnt.as<uint32_t>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
+                     ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
+  ITRY(hipGetLastError());
+  ITRY(hipEventRecord(ix->ev[3], st));
+  ITRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  ITRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  ITRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  unsigned long long rows = 0;
+  ITRY(hipMemcpyAsync(&rows, ix->rows_acc.p, 8, hipMemcpyDeviceToHost, st));
+  ITRY(hipStreamSynchronize(st));
+  float tc = 0, ts = 0, tl = 0;
+  (void)hipEventElapsedTime(&tc, ix->ev[0], ix->ev[1]);
+  (void)hipEventElapsedTime(&ts, ix->ev[1], ix->ev[2]);
+  (void)hipEventElapsedTime(&tl, ix->ev[2], ix->ev[3]);
+  ix->t_coarse += tc;
+  ix->t_scan += ts;
+  ix->t_sel += tl;
+  ix->last_rows += (int64_t)rows;
+  ix->last_rounds = std::max(ix->last_rounds, rounds + 1);
+  return IVF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *ivfpq_last_error(void) { return g_err.c_str(); }
+
+int ivfpq_index_load(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, const float *centroids,
+                     const float *codebooks, ivfpq_index_t **out) try {
+  if (!centroids || !codebooks || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist, M)) return rc;
+  std::unique_ptr<ivfpq_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, M, ix)) return rc;
+  if (int rc = set_centroids(ix.get(), centroids)) return rc;
+  ITRY(hipMemcpy(ix->cb.p, codebooks, (size_t)M * KSUB * ix->dsub * sizeof(float), hipMemcpyHostToDevice));
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
+                      const float *train_vectors, int32_t niter, uint64_t seed, ivfpq_index_t **out) try {
+  if (!train_vectors || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist, M)) return rc;
+  if (n_train < std::max<int64_t>(nlist, KSUB)) return fail(IVF_EINVAL, "n_train must be at least max(nlist, 256)");
+  if (n_train >= ((int64_t)1 << 31)) return fail(IVF_EINVAL, "n_train out of range");
+  if (niter < -1) return fail(IVF_EINVAL, "niter must be -1 (initial picks), 0 (20 rounds) or a number of rounds");
+  const int rounds = niter == 0 ? 20 : niter == -1 ? 0 : niter;
+  // the coarse quantizer, trained as an IVF-Flat index trains it
+  std::vector<float> centroids((size_t)nlist * d);
+  {
+    ivf_index_t *flat = nullptr;
+    if (int rc = ivf_index_train(device, metric, d, nlist, n_train, train_vectors, niter, seed, &flat))
+      return fail(rc, std::string("coarse training: ") + ivf_last_error());
+    const int rc = ivf_index_get_centroids(flat, centroids.data());
+    const std::string msg = rc ? ivf_last_error() : "";
+    (void)ivf_index_destroy(flat);
+    if (rc) return fail(rc, "coarse training: " + msg);
+  }
+  std::unique_ptr<ivfpq_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, M, ix)) return rc;
+  if (int rc = set_centroids(ix.get(), centroids.data())) return rc;
+  // the training rows, prepared as stored rows are; they go with this call
+  Buf tflat, tsumsq;
+  ITRY(tflat.reserve((size_t)n_train * d * sizeof(_Float16)));
+  ITRY(tsumsq.reserve((size_t)n_train * sizeof(float)));
+  const int64_t slab = slab_rows(d);
+  for (int64_t r0 = 0; r0 < n_train; r0 += slab)
+    if (int rc = prepare_slab(ix.get(), train_vectors + r0 * d, std::min(slab, n_train - r0), tflat, tsumsq, r0)) return rc;
+  if (int rc = train_codebooks(ix.get(), tflat.as<_Float16>(), tsumsq.as<float>(), n_train, rounds, seed)) return rc;
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_add(ivfpq_index_t *ix, int64_t n, const float *vectors, const int64_t *ids) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (n < 0) return fail(IVF_EINVAL, "n must not be negative");
+  if (ix->ids_mode == 1 && !ids) return fail(IVF_EINVAL, "the index holds rows added with ids: an add must give ids");
+  if (ix->ids_mode == 0 && ids) return fail(IVF_EINVAL, "the index holds rows added without ids (its ids are positions): ids must be NULL");
+  if (n == 0) return IVF_OK;
+  if (!vectors) return fail(IVF_EINVAL, "null vectors");
+  const int64_t n_old = ix->n, total = n_old + n;
+  if (total >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
+  ITRY(hipSetDevice(ix->device));
+  const int d = ix->d, M = ix->M;
+  ITRY(ix->codes.grow_keep((size_t)n_old * M, (size_t)total * M));
+  ITRY(ix->cell.grow_keep((size_t)n_old * 4, (size_t)total * 4));
+  ITRY(ix->ids.grow_keep((size_t)n_old * 8, (size_t)total * 8));
+  // a slab of rows at a time: prepare, assign, encode; the fp16 rows are scratch
+  const int64_t slab = slab_rows(d);
+  ITRY(ix->flat.reserve((size_t)std::min(slab, n) * d * sizeof(_Float16)));
+  ITRY(ix->sumsq.reserve((size_t)std::min(slab, n) * sizeof(float)));
+  for (int64_t r0 = 0; r0 < n; r0 += slab) {
+    const int64_t m = std::min(slab, n - r0);
+    if (int rc = prepare_slab(ix, vectors + r0 * d, m, ix->flat, ix->sumsq, 0)) return rc;
+    int32_t *cell = ix->cell.as<int32_t>() + n_old + r0;
+    if (int rc = assign_rows(ix, ix->flat.as<_Float16>(), ix->sumsq.as<float>(), m, cell)) return rc;
+    if (int rc = encode_rows(ix, ix->flat.as<_Float16>(), cell, m, ix->codes.as<uint8_t>() + (size_t)(n_old + r0) * M, M, 1)) return rc;
+    ITRY(hipDeviceSynchronize());
+  }
+  if (ids) {
+    ITRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  } else {
+    hipLaunchKernelGGL(iota64_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->ids.as<int64_t>() + n_old, n_old, n);
+    ITRY(hipGetLastError());
+  }
+  ix->n = total;
+  ix->ids_mode = ids ? 1 : 0;
+  return layout_lists(ix);
+} ABI_CATCH
+
+int ivfpq_search(ivfpq_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
+                 int64_t *out_ids, int32_t *out_counts) try {
+  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
+  if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
+  if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
+  nprobe = std::min(nprobe, ix->nlist);
+  ITRY(hipSetDevice(ix->device));
+  ITRY(ix->probes.reserve((size_t)nq * nprobe * sizeof(int32_t)));
+  ix->last_nq = 0;
+  ix->last_nprobe = nprobe;
+  ix->last_rows = 0;
+  ix->last_rounds = 0;
+  ix->t_coarse = ix->t_scan = ix->t_sel = 0;
+  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
+    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
+    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, k, nprobe, out_dist + (size_t)q0 * k,
+                              out_ids + (size_t)q0 * k, out_counts + q0))
+      return rc;
+  }
+  ix->last_nq = nq;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_info(const ivfpq_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist, int32_t *M) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (n) *n = ix->n;
+  if (d) *d = ix->d;
+  if (metric) *metric = ix->metric;
+  if (nlist) *nlist = ix->nlist;
+  if (M) *M = ix->M;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_get_centroids(const ivfpq_index_t *ix, float *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  DCALL(dann_index_get_vectors(ix->coarse, 0, ix->nlist, out));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_get_codebooks(const ivfpq_index_t *ix, float *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  ITRY(hipSetDevice(ix->device));
+  ITRY(hipMemcpy(out, ix->cb.p, (size_t)ix->M * KSUB * ix->dsub * sizeof(float), hipMemcpyDeviceToHost));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_get_codes(const ivfpq_index_t *ix, uint8_t *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  if (ix->n == 0) return IVF_OK;
+  ITRY(hipSetDevice(ix->device));
+  ITRY(hipMemcpy(out, ix->codes.p, (size_t)ix->n * ix->M, hipMemcpyDeviceToHost));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_list_sizes(const ivfpq_index_t *ix, int64_t *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  std::copy(ix->h_sizes.begin(), ix->h_sizes.end(), out);
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_get_assignment(const ivfpq_index_t *ix, int64_t *out_ids, int32_t *out_cells) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (ix->n == 0) return IVF_OK;
+  ITRY(hipSetDevice(ix->device));
+  if (out_ids) ITRY(hipMemcpy(out_ids, ix->ids.p, (size_t)ix->n * 8, hipMemcpyDeviceToHost));
+  if (out_cells) ITRY(hipMemcpy(out_cells, ix->cell.p, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_last_probes(const ivfpq_index_t *ix, int32_t *nq, int32_t *nprobe, int32_t *out_cells) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (nq) *nq = ix->last_nq;
+  if (nprobe) *nprobe = ix->last_nprobe;
+  if (out_cells && ix->last_nq > 0) {
+    ITRY(hipSetDevice(ix->device));
+    ITRY(hipMemcpy(out_cells, ix->probes.p, (size_t)ix->last_nq * ix->last_nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_last_stats(const ivfpq_index_t *ix, int64_t *rows_scanned, int32_t *rounds, float *coarse_ms, float *scan_ms,
+                     float *select_ms) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (rows_scanned) *rows_scanned = ix->last_rows;
+  if (rounds) *rounds = ix->last_rounds;
+  if (coarse_ms) *coarse_ms = ix->t_coarse;
+  if (scan_ms) *scan_ms = ix->t_scan;
+  if (select_ms) *select_ms = ix->t_sel;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_index_destroy(ivfpq_index_t *ix) try {
+  delete ix;
+  return IVF_OK;
+} ABI_CATCH
+
+}  // extern "C"
