@@ -43,6 +43,7 @@
 #include "sann_device.h"  // mix64
 #include "abi_guard.h"
 #include "ann_by_id_internal.h"
+#include "ivf_device_rows.h"
 #include "ivf_kernels.h"
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
@@ -310,9 +311,17 @@ int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, std::uni
   return IVF_OK;
 }
 
-// host rows -> fp16 rows at flat[row0 ..) and their sums of squares, through a staging buffer
-int upload_rows(ivf_index *ix, const float *rows, int64_t n, Buf &flat, Buf &sumsq, int64_t row0) {
+// host rows -> fp16 rows at flat[row0 ..) and their sums of squares, through a staging buffer; rows that are on the
+// device already (ivf_device_rows.h) are prepared where they lie
+int upload_rows(ivf_index *ix, const float *rows, bool on_device, int64_t n, Buf &flat, Buf &sumsq, int64_t row0) {
   const int d = ix->d;
+  if (on_device) {
+    hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, 0, rows, n, d,
+                       ix->metric == IVF_METRIC_COSINE ? 1 : 0, flat.as<_Float16>() + (size_t)row0 * d, sumsq.as<float>() + row0);
+    ITRY(hipGetLastError());
+    ITRY(hipDeviceSynchronize());
+    return IVF_OK;
+  }
   const int64_t slab = std::max<int64_t>(1, (int64_t)(64 << 20) / (d * 4));
   ITRY(ix->stage.reserve((size_t)std::min(slab, n) * d * sizeof(float)));
   for (int64_t r0 = 0; r0 < n; r0 += slab) {
@@ -578,27 +587,9 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, in
   return IVF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char *ivf_last_error(void) { return g_err.c_str(); }
-
-int ivf_index_load(int32_t device, int32_t metric, int32_t d, int32_t nlist, const float *centroids, ivf_index_t **out) try {
-  if (!centroids || !out) return fail(IVF_EINVAL, "null argument");
-  if (int rc = check_shape(metric, d, nlist)) return rc;
-  std::unique_ptr<ivf_index> ix;
-  if (int rc = new_index(device, metric, d, nlist, ix)) return rc;
-  Buf cent;
-  ITRY(cent.reserve((size_t)nlist * d * sizeof(float)));
-  ITRY(hipMemcpy(cent.p, centroids, (size_t)nlist * d * sizeof(float), hipMemcpyHostToDevice));
-  if (int rc = build_coarse(ix.get(), cent.as<float>())) return rc;
-  *out = ix.release();
-  return IVF_OK;
-} ABI_CATCH
-
-int ivf_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t n_train, const float *train_vectors,
-                    int32_t niter, uint64_t seed, ivf_index_t **out) try {
+// ivf_index_train, over host rows or over rows that are on the device
+int train_rows(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t n_train, const float *train_vectors,
+               bool on_device, int32_t niter, uint64_t seed, ivf_index_t **out) {
   if (!train_vectors || !out) return fail(IVF_EINVAL, "null argument");
   if (int rc = check_shape(metric, d, nlist)) return rc;
   if (n_train < nlist) return fail(IVF_EINVAL, "n_train must be at least nlist");
@@ -611,7 +602,7 @@ int ivf_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, in
   Buf tflat, tsumsq, picks_d, cent;
   ITRY(tflat.reserve((size_t)n_train * d * sizeof(_Float16)));
   ITRY(tsumsq.reserve((size_t)n_train * sizeof(float)));
-  if (int rc = upload_rows(ix.get(), train_vectors, n_train, tflat, tsumsq, 0)) return rc;
+  if (int rc = upload_rows(ix.get(), train_vectors, on_device, n_train, tflat, tsumsq, 0)) return rc;
   // initial centroids: rows mix64(seed + t) mod n_train, t = 0, 1, ..., without repetition
   std::vector<int64_t> picks;
   picks.reserve((size_t)nlist);
@@ -647,6 +638,35 @@ int ivf_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, in
   ITRY(hipMemset(ix->start.p, 0, (size_t)nlist * 4));
   *out = ix.release();
   return IVF_OK;
+}
+
+}  // namespace
+
+int ivf_internal::train_device(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t n_train, const float *d_rows,
+                               int32_t niter, uint64_t seed, ivf_index **out) try {
+  return train_rows(device, metric, d, nlist, n_train, d_rows, true, niter, seed, out);
+} ABI_CATCH
+
+extern "C" {
+
+const char *ivf_last_error(void) { return g_err.c_str(); }
+
+int ivf_index_load(int32_t device, int32_t metric, int32_t d, int32_t nlist, const float *centroids, ivf_index_t **out) try {
+  if (!centroids || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist)) return rc;
+  std::unique_ptr<ivf_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, ix)) return rc;
+  Buf cent;
+  ITRY(cent.reserve((size_t)nlist * d * sizeof(float)));
+  ITRY(hipMemcpy(cent.p, centroids, (size_t)nlist * d * sizeof(float), hipMemcpyHostToDevice));
+  if (int rc = build_coarse(ix.get(), cent.as<float>())) return rc;
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t n_train, const float *train_vectors,
+                    int32_t niter, uint64_t seed, ivf_index_t **out) try {
+  return train_rows(device, metric, d, nlist, n_train, train_vectors, false, niter, seed, out);
 } ABI_CATCH
 
 int ivf_index_add(ivf_index_t *ix, int64_t n, const float *vectors, const int64_t *ids) try {
@@ -664,7 +684,7 @@ int ivf_index_add(ivf_index_t *ix, int64_t n, const float *vectors, const int64_
   ITRY(ix->sumsq.grow_keep((size_t)n_old * 4, (size_t)total * 4));
   ITRY(ix->cell.grow_keep((size_t)n_old * 4, (size_t)total * 4));
   ITRY(ix->ids.grow_keep((size_t)n_old * 8, (size_t)total * 8));
-  if (int rc = upload_rows(ix, vectors, n, ix->flat, ix->sumsq, n_old)) return rc;
+  if (int rc = upload_rows(ix, vectors, false, n, ix->flat, ix->sumsq, n_old)) return rc;
   if (ids) {
     ITRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
   } else {

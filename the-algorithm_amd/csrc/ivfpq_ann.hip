@@ -42,6 +42,7 @@
 #include "sann_device.h"  // mix64
 #include "abi_guard.h"
 #include "ann_by_id_internal.h"
+#include "ivf_device_rows.h"
 #include "ivf_kernels.h"
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
@@ -501,18 +502,22 @@ int encode_rows(ivfpq_index *ix, const _Float16 *flat, const int32_t *cell, int6
   return IVF_OK;
 }
 
-// host rows [r0, r0 + m) -> fp16 rows and their sums of squares at the front of `flat` / `sumsq`
-int prepare_slab(ivfpq_index *ix, const float *rows, int64_t m, Buf &flat, Buf &sumsq, int64_t at) {
+// m device rows -> fp16 rows and their sums of squares at row `at` of `flat` / `sumsq`
+int prepare_slab(ivfpq_index *ix, const float *d_rows, int64_t m, Buf &flat, Buf &sumsq, int64_t at) {
   const int d = ix->d;
-  ITRY(ix->stage.reserve((size_t)m * d * sizeof(float)));
-  ITRY(hipMemcpy(ix->stage.p, rows, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, ix->stage.as<float>(), m, d,
+  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, d_rows, m, d,
                      ix->metric == IVF_METRIC_COSINE ? 1 : 0, flat.as<_Float16>() + (size_t)at * d, sumsq.as<float>() + at);
   ITRY(hipGetLastError());
   ITRY(hipDeviceSynchronize());
   return IVF_OK;
 }
-int64_t slab_rows(int d) { return std::max<int64_t>(1, (int64_t)(64 << 20) / (d * 4)); }
+using ivfpq_internal::slab_rows;
+// host rows -> the staging buffer of the index
+int stage_rows(ivfpq_index *ix, const float *rows, int64_t m) {
+  ITRY(ix->stage.reserve((size_t)m * ix->d * sizeof(float)));
+  ITRY(hipMemcpy(ix->stage.p, rows, (size_t)m * ix->d * sizeof(float), hipMemcpyHostToDevice));
+  return IVF_OK;
+}
 
 // all lists again from the codes in the order added: (cell, id) order, every list on a block boundary
 int layout_lists(ivfpq_index *ix) {
@@ -570,13 +575,8 @@ int layout_lists(ivfpq_index *ix) {
   return IVF_OK;
 }
 
-// the M codebooks on the residuals of the n prepared training rows
-int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq, int64_t n, int rounds, uint64_t seed) {
-  const int M = ix->M, d = ix->d, dsub = ix->dsub;
-  Buf tcell, tcodes, picks_d;
-  ITRY(tcell.reserve((size_t)n * 4));
-  ITRY(tcodes.reserve((size_t)n * M));
-  if (int rc = assign_rows(ix, tflat, tsumsq, n, tcell.as<int32_t>())) return rc;
+// the rows whose residuals are the initial codewords: picks[m][j], by the rule of ivfpq_ann.h
+std::vector<int64_t> initial_picks(int M, int64_t n, uint64_t seed) {
   std::vector<int64_t> picks;
   picks.reserve((size_t)M * KSUB);
   for (int m = 0; m < M; ++m) {
@@ -587,6 +587,17 @@ int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq,
       if (seen.insert(r).second) picks.push_back(r);
     }
   }
+  return picks;
+}
+
+// the M codebooks on the residuals of the n prepared training rows
+int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq, int64_t n, int rounds, uint64_t seed) {
+  const int M = ix->M, d = ix->d, dsub = ix->dsub;
+  Buf tcell, tcodes, picks_d;
+  ITRY(tcell.reserve((size_t)n * 4));
+  ITRY(tcodes.reserve((size_t)n * M));
+  if (int rc = assign_rows(ix, tflat, tsumsq, n, tcell.as<int32_t>())) return rc;
+  const std::vector<int64_t> picks = initial_picks(M, n, seed);
   ITRY(picks_d.reserve(picks.size() * 8));
   ITRY(hipMemcpy(picks_d.p, picks.data(), picks.size() * 8, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(pq_pick_kernel, dim3(blocks_for((int64_t)M * KSUB * dsub)), dim3(256), 0, 0, tflat, tcell.as<int32_t>(),
@@ -602,8 +613,8 @@ int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq,
   return IVF_OK;
 }
 
-int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
-                 int64_t *out_ids, int32_t *out_counts) {
+int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
+                 float *out_dist, int64_t *out_ids, int32_t *out_counts) {
   const int d = ix->d, nlist = ix->nlist;
   const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
@@ -611,7 +622,7 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
   DCALL(ann_by_id::dann_open(ix->coarse, nprobe, false, &tgt));
   ann_by_id::DannChunk ch;
   DCALL(ann_by_id::dann_chunk_open(ix->coarse, nq, nprobe, &ch));
-  ITRY(ix->stage.reserve((size_t)nq * d * sizeof(float)));
+  if (!on_device) ITRY(ix->stage.reserve((size_t)nq * d * sizeof(float)));
   ITRY(ix->q16.reserve((size_t)nq * d * sizeof(_Float16)));
   ITRY(ix->qsumsq.reserve((size_t)nq * sizeof(float)));
   ITRY(ix->c_dist.reserve((size_t)np * sizeof(float)));
@@ -634,8 +645,8 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
 
   // coarse: the nprobe nearest centroids of every query
   ITRY(hipEventRecord(ix->ev[0], st));
-  ITRY(hipMemcpyAsync(ix->stage.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, ix->stage.as<float>(), (int64_t)nq, d,
+  if (!on_device) ITRY(hipMemcpyAsync(ix->stage.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, on_device ? queries : ix->stage.as<float>(), (int64_t)nq, d,
                      ix->metric == IVF_METRIC_COSINE ? 1 : 0, ix->q16.as<_Float16>(), ix->qsumsq.as<float>());
   ITRY(hipGetLastError());
   hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, ix->q16.as<_Float16>(),
@@ -722,7 +733,174 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
   return IVF_OK;
 }
 
+// ivfpq_index_train, over host rows or over rows that are on the device
+int train_rows(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train, const float *train_vectors,
+               bool on_device, int32_t niter, uint64_t seed, ivfpq_index_t **out) {
+  if (!train_vectors || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist, M)) return rc;
+  if (n_train < std::max<int64_t>(nlist, KSUB)) return fail(IVF_EINVAL, "n_train must be at least max(nlist, 256)");
+  if (n_train >= ((int64_t)1 << 31)) return fail(IVF_EINVAL, "n_train out of range");
+  if (niter < -1) return fail(IVF_EINVAL, "niter must be -1 (initial picks), 0 (20 rounds) or a number of rounds");
+  const int rounds = niter == 0 ? 20 : niter == -1 ? 0 : niter;
+  // the coarse quantizer, trained as an IVF-Flat index trains it
+  std::vector<float> centroids((size_t)nlist * d);
+  {
+    ivf_index_t *flat = nullptr;
+    if (int rc = on_device ? ivf_internal::train_device(device, metric, d, nlist, n_train, train_vectors, niter, seed, &flat)
+                           : ivf_index_train(device, metric, d, nlist, n_train, train_vectors, niter, seed, &flat))
+      return fail(rc, std::string("coarse training: ") + ivf_last_error());
+    const int rc = ivf_index_get_centroids(flat, centroids.data());
+    const std::string msg = rc ? ivf_last_error() : "";
+    (void)ivf_index_destroy(flat);
+    if (rc) return fail(rc, "coarse training: " + msg);
+  }
+  std::unique_ptr<ivfpq_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, M, ix)) return rc;
+  if (int rc = set_centroids(ix.get(), centroids.data())) return rc;
+  // the training rows, prepared as stored rows are; they go with this call
+  Buf tflat, tsumsq;
+  ITRY(tflat.reserve((size_t)n_train * d * sizeof(_Float16)));
+  ITRY(tsumsq.reserve((size_t)n_train * sizeof(float)));
+  const int64_t slab = slab_rows(d);
+  for (int64_t r0 = 0; r0 < n_train; r0 += slab) {
+    const int64_t m = std::min(slab, n_train - r0);
+    const float *src = train_vectors + r0 * d;
+    if (!on_device) {
+      if (int rc = stage_rows(ix.get(), src, m)) return rc;
+      src = ix->stage.as<float>();
+    }
+    if (int rc = prepare_slab(ix.get(), src, m, tflat, tsumsq, r0)) return rc;
+  }
+  if (int rc = train_codebooks(ix.get(), tflat.as<_Float16>(), tsumsq.as<float>(), n_train, rounds, seed)) return rc;
+  *out = ix.release();
+  return IVF_OK;
+}
+
+int check_ids_rule(const ivfpq_index *ix, bool with_ids) {
+  if (ix->ids_mode == 1 && !with_ids) return fail(IVF_EINVAL, "the index holds rows added with ids: an add must give ids");
+  if (ix->ids_mode == 0 && with_ids) return fail(IVF_EINVAL, "the index holds rows added without ids (its ids are positions): ids must be NULL");
+  return IVF_OK;
+}
+
+// ivfpq_search, over host queries or over queries that are on the device
+int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe, float *out_dist,
+                int64_t *out_ids, int32_t *out_counts) {
+  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
+  if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
+  if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
+  nprobe = std::min(nprobe, ix->nlist);
+  ITRY(hipSetDevice(ix->device));
+  ITRY(ix->probes.reserve((size_t)nq * nprobe * sizeof(int32_t)));
+  ix->last_nq = 0;
+  ix->last_nprobe = nprobe;
+  ix->last_rows = 0;
+  ix->last_rounds = 0;
+  ix->t_coarse = ix->t_scan = ix->t_sel = 0;
+  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
+    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
+    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, out_dist + (size_t)q0 * k,
+                              out_ids + (size_t)q0 * k, out_counts + q0))
+      return rc;
+  }
+  ix->last_nq = nq;
+  return IVF_OK;
+}
+
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// the device-rows seam (ivf_device_rows.h)
+// ---------------------------------------------------------------------------------------------
+int64_t ivfpq_internal::slab_rows(int d) { return std::max<int64_t>(1, (int64_t)(64 << 20) / (d * 4)); }
+
+int ivfpq_internal::train_device(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
+                                 const float *d_rows, int32_t niter, uint64_t seed, ivfpq_index **out) try {
+  return train_rows(device, metric, d, nlist, M, n_train, d_rows, true, niter, seed, out);
+} ABI_CATCH
+
+int ivfpq_internal::add_begin(ivfpq_index *ix, int64_t n, bool with_ids) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (n < 1) return fail(IVF_EINVAL, "n must be positive");
+  if (int rc = check_ids_rule(ix, with_ids)) return rc;
+  const int64_t n_old = ix->n, total = n_old + n;
+  if (total >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
+  ITRY(hipSetDevice(ix->device));
+  const int d = ix->d, M = ix->M;
+  ITRY(ix->codes.grow_keep((size_t)n_old * M, (size_t)total * M));
+  ITRY(ix->cell.grow_keep((size_t)n_old * 4, (size_t)total * 4));
+  ITRY(ix->ids.grow_keep((size_t)n_old * 8, (size_t)total * 8));
+  // a slab of rows at a time: prepare, assign, encode; the fp16 rows are scratch
+  const int64_t slab = slab_rows(d);
+  ITRY(ix->flat.reserve((size_t)std::min(slab, n) * d * sizeof(_Float16)));
+  ITRY(ix->sumsq.reserve((size_t)std::min(slab, n) * sizeof(float)));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::add_slab(ivfpq_index *ix, int64_t r0, int64_t m, const float *d_rows) try {
+  const int64_t at = ix->n + r0;
+  const int M = ix->M;
+  if (int rc = prepare_slab(ix, d_rows, m, ix->flat, ix->sumsq, 0)) return rc;
+  int32_t *cell = ix->cell.as<int32_t>() + at;
+  if (int rc = assign_rows(ix, ix->flat.as<_Float16>(), ix->sumsq.as<float>(), m, cell)) return rc;
+  if (int rc = encode_rows(ix, ix->flat.as<_Float16>(), cell, m, ix->codes.as<uint8_t>() + (size_t)at * M, M, 1)) return rc;
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::add_end(ivfpq_index *ix, int64_t n, const int64_t *ids) try {
+  const int64_t n_old = ix->n;
+  if (ids) {
+    ITRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+  } else {
+    hipLaunchKernelGGL(iota64_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->ids.as<int64_t>() + n_old, n_old, n);
+    ITRY(hipGetLastError());
+  }
+  ix->n = n_old + n;
+  ix->ids_mode = ids ? 1 : 0;
+  return layout_lists(ix);
+} ABI_CATCH
+
+int ivfpq_internal::search_device(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *out_dist,
+                                  int64_t *out_ids, int32_t *out_counts) try {
+  return search_rows(ix, nq, d_queries, true, k, nprobe, out_dist, out_ids, out_counts);
+} ABI_CATCH
+
+int ivfpq_internal::pq_train_plain(int32_t device, const _Float16 *d_rows16, int64_t n, int32_t d, int32_t M, bool init,
+                                   int32_t rounds, uint64_t seed, float *d_cb, uint8_t *d_codes) try {
+  if (!d_rows16 || !d_cb || !d_codes) return fail(IVF_EINVAL, "null argument");
+  if (n < KSUB || n >= ((int64_t)1 << 31)) return fail(IVF_EINVAL, "a product quantiser needs 256 .. 2^31 - 1 rows");
+  ITRY(hipSetDevice(device));
+  const int dsub = d / M;
+  Buf cell0, cent0, tcodes, picks_d;
+  ITRY(cell0.reserve((size_t)n * 4));
+  ITRY(cent0.reserve((size_t)d * sizeof(float)));
+  ITRY(tcodes.reserve((size_t)n * M));
+  ITRY(hipMemset(cell0.p, 0, (size_t)n * 4));
+  ITRY(hipMemset(cent0.p, 0, (size_t)d * sizeof(float)));
+  ITRY(hipFuncSetAttribute((const void *)encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)encode_lds_bytes(MAX_D / 4)));
+  if (init) {
+    const std::vector<int64_t> picks = initial_picks(M, n, seed);
+    ITRY(picks_d.reserve(picks.size() * 8));
+    ITRY(hipMemcpy(picks_d.p, picks.data(), picks.size() * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(pq_pick_kernel, dim3(blocks_for((int64_t)M * KSUB * dsub)), dim3(256), 0, 0, d_rows16, cell0.as<int32_t>(),
+                       cent0.as<float>(), picks_d.as<int64_t>(), M, d, dsub, d_cb);
+    ITRY(hipGetLastError());
+  }
+  for (int it = 0; it <= rounds; ++it) {
+    const bool last = it == rounds;  // the final encoding, [n][M]
+    hipLaunchKernelGGL(encode_kernel, dim3(blocks_for(n, ENC_ROWS), M), dim3(256), encode_lds_bytes(dsub), 0, d_rows16,
+                       cell0.as<int32_t>(), cent0.as<float>(), d_cb, n, d, dsub, last ? d_codes : tcodes.as<uint8_t>(),
+                       last ? (int64_t)M : (int64_t)1, last ? (int64_t)1 : n);
+    ITRY(hipGetLastError());
+    if (last) break;
+    hipLaunchKernelGGL(pq_mean_kernel, dim3(KSUB, M), dim3(256), 0, 0, d_rows16, cell0.as<int32_t>(), cent0.as<float>(),
+                       tcodes.as<uint8_t>(), n, d, dsub, d_cb);
+    ITRY(hipGetLastError());
+  }
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+} ABI_CATCH
 
 extern "C" {
 
@@ -742,97 +920,28 @@ int ivfpq_index_load(int32_t device, int32_t metric, int32_t d, int32_t nlist, i
 
 int ivfpq_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
                       const float *train_vectors, int32_t niter, uint64_t seed, ivfpq_index_t **out) try {
-  if (!train_vectors || !out) return fail(IVF_EINVAL, "null argument");
-  if (int rc = check_shape(metric, d, nlist, M)) return rc;
-  if (n_train < std::max<int64_t>(nlist, KSUB)) return fail(IVF_EINVAL, "n_train must be at least max(nlist, 256)");
-  if (n_train >= ((int64_t)1 << 31)) return fail(IVF_EINVAL, "n_train out of range");
-  if (niter < -1) return fail(IVF_EINVAL, "niter must be -1 (initial picks), 0 (20 rounds) or a number of rounds");
-  const int rounds = niter == 0 ? 20 : niter == -1 ? 0 : niter;
-  // the coarse quantizer, trained as an IVF-Flat index trains it
-  std::vector<float> centroids((size_t)nlist * d);
-  {
-    ivf_index_t *flat = nullptr;
-    if (int rc = ivf_index_train(device, metric, d, nlist, n_train, train_vectors, niter, seed, &flat))
-      return fail(rc, std::string("coarse training: ") + ivf_last_error());
-    const int rc = ivf_index_get_centroids(flat, centroids.data());
-    const std::string msg = rc ? ivf_last_error() : "";
-    (void)ivf_index_destroy(flat);
-    if (rc) return fail(rc, "coarse training: " + msg);
-  }
-  std::unique_ptr<ivfpq_index> ix;
-  if (int rc = new_index(device, metric, d, nlist, M, ix)) return rc;
-  if (int rc = set_centroids(ix.get(), centroids.data())) return rc;
-  // the training rows, prepared as stored rows are; they go with this call
-  Buf tflat, tsumsq;
-  ITRY(tflat.reserve((size_t)n_train * d * sizeof(_Float16)));
-  ITRY(tsumsq.reserve((size_t)n_train * sizeof(float)));
-  const int64_t slab = slab_rows(d);
-  for (int64_t r0 = 0; r0 < n_train; r0 += slab)
-    if (int rc = prepare_slab(ix.get(), train_vectors + r0 * d, std::min(slab, n_train - r0), tflat, tsumsq, r0)) return rc;
-  if (int rc = train_codebooks(ix.get(), tflat.as<_Float16>(), tsumsq.as<float>(), n_train, rounds, seed)) return rc;
-  *out = ix.release();
-  return IVF_OK;
+  return train_rows(device, metric, d, nlist, M, n_train, train_vectors, false, niter, seed, out);
 } ABI_CATCH
 
 int ivfpq_index_add(ivfpq_index_t *ix, int64_t n, const float *vectors, const int64_t *ids) try {
   if (!ix) return fail(IVF_EINVAL, "null index");
   if (n < 0) return fail(IVF_EINVAL, "n must not be negative");
-  if (ix->ids_mode == 1 && !ids) return fail(IVF_EINVAL, "the index holds rows added with ids: an add must give ids");
-  if (ix->ids_mode == 0 && ids) return fail(IVF_EINVAL, "the index holds rows added without ids (its ids are positions): ids must be NULL");
+  if (int rc = check_ids_rule(ix, ids != nullptr)) return rc;
   if (n == 0) return IVF_OK;
   if (!vectors) return fail(IVF_EINVAL, "null vectors");
-  const int64_t n_old = ix->n, total = n_old + n;
-  if (total >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
-  ITRY(hipSetDevice(ix->device));
-  const int d = ix->d, M = ix->M;
-  ITRY(ix->codes.grow_keep((size_t)n_old * M, (size_t)total * M));
-  ITRY(ix->cell.grow_keep((size_t)n_old * 4, (size_t)total * 4));
-  ITRY(ix->ids.grow_keep((size_t)n_old * 8, (size_t)total * 8));
-  // a slab of rows at a time: prepare, assign, encode; the fp16 rows are scratch
-  const int64_t slab = slab_rows(d);
-  ITRY(ix->flat.reserve((size_t)std::min(slab, n) * d * sizeof(_Float16)));
-  ITRY(ix->sumsq.reserve((size_t)std::min(slab, n) * sizeof(float)));
+  if (int rc = ivfpq_internal::add_begin(ix, n, ids != nullptr)) return rc;
+  const int64_t slab = slab_rows(ix->d);
   for (int64_t r0 = 0; r0 < n; r0 += slab) {
     const int64_t m = std::min(slab, n - r0);
-    if (int rc = prepare_slab(ix, vectors + r0 * d, m, ix->flat, ix->sumsq, 0)) return rc;
-    int32_t *cell = ix->cell.as<int32_t>() + n_old + r0;
-    if (int rc = assign_rows(ix, ix->flat.as<_Float16>(), ix->sumsq.as<float>(), m, cell)) return rc;
-    if (int rc = encode_rows(ix, ix->flat.as<_Float16>(), cell, m, ix->codes.as<uint8_t>() + (size_t)(n_old + r0) * M, M, 1)) return rc;
-    ITRY(hipDeviceSynchronize());
+    if (int rc = stage_rows(ix, vectors + r0 * ix->d, m)) return rc;
+    if (int rc = ivfpq_internal::add_slab(ix, r0, m, ix->stage.as<float>())) return rc;
   }
-  if (ids) {
-    ITRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
-  } else {
-    hipLaunchKernelGGL(iota64_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->ids.as<int64_t>() + n_old, n_old, n);
-    ITRY(hipGetLastError());
-  }
-  ix->n = total;
-  ix->ids_mode = ids ? 1 : 0;
-  return layout_lists(ix);
+  return ivfpq_internal::add_end(ix, n, ids);
 } ABI_CATCH
 
 int ivfpq_search(ivfpq_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
                  int64_t *out_ids, int32_t *out_counts) try {
-  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
-  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
-  if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
-  if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
-  nprobe = std::min(nprobe, ix->nlist);
-  ITRY(hipSetDevice(ix->device));
-  ITRY(ix->probes.reserve((size_t)nq * nprobe * sizeof(int32_t)));
-  ix->last_nq = 0;
-  ix->last_nprobe = nprobe;
-  ix->last_rows = 0;
-  ix->last_rounds = 0;
-  ix->t_coarse = ix->t_scan = ix->t_sel = 0;
-  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
-    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
-    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, k, nprobe, out_dist + (size_t)q0 * k,
-                              out_ids + (size_t)q0 * k, out_counts + q0))
-      return rc;
-  }
-  ix->last_nq = nq;
-  return IVF_OK;
+  return search_rows(ix, nq, queries, false, k, nprobe, out_dist, out_ids, out_counts);
 } ABI_CATCH
 
 int ivfpq_index_info(const ivfpq_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist, int32_t *M) try {
