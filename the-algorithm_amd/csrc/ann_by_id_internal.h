@@ -63,6 +63,9 @@ int dann_chunk_search_prepared(dann_index *ix, int32_t nq, int32_t k, float *o_d
 std::shared_ptr<void> &dann_scratch(dann_index *ix);
 // dann_index_build without ids from rows that are on the device already (row-major fp32 [n][d]): the coarse quantizer of
 // ivf_ann.hip rebuilds its centroid index this way in every k-means round.  Free with dann_index_destroy.
-int dann_build_device(int32_t device, int32_t metric, int64_t n, int32_t d, const float *d_rows, dann_index **out);
+// stored: the rows are values an index stored before (fp16 values, Cosine rows normalised already); they are kept as they
+// are -- a Cosine index does not normalise them again, which could move a rounded value by an ulp.
+int dann_build_device(int32_t device, int32_t metric, int64_t n, int32_t d, const float *d_rows, dann_index **out,
+                      bool stored = false);
 
 }  // namespace ann_by_id

@@ -1450,7 +1450,7 @@ int dann_chunk_search_prepared(dann_index *ix, int32_t nq, int32_t k, float *o_d
 
 std::shared_ptr<void> &dann_scratch(dann_index *ix) { return ix->by_id; }
 
-int dann_build_device(int32_t device, int32_t metric, int64_t n, int32_t d, const float *d_rows, dann_index **out) {
+int dann_build_device(int32_t device, int32_t metric, int64_t n, int32_t d, const float *d_rows, dann_index **out, bool stored) {
   if (!d_rows || !out) return fail(DANN_EINVAL, "null argument");
   std::unique_ptr<dann_index> ix(new dann_index);
   if (int rc = alloc_index(ix.get(), device, metric, n, d)) return rc;
@@ -1458,7 +1458,7 @@ int dann_build_device(int32_t device, int32_t metric, int64_t n, int32_t d, cons
   for (int64_t r0 = 0; r0 < n; r0 += slab) {
     const int64_t m = std::min(slab, n - r0);
     hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_rows + r0 * d, m, d, ix->S,
-                       metric == DANN_METRIC_COSINE ? 1 : 0, r0, ix->xf.as<_Float16>(), ix->bias.as<float>());
+                       metric == DANN_METRIC_COSINE && !stored ? 1 : 0, r0, ix->xf.as<_Float16>(), ix->bias.as<float>());
     DTRY(hipGetLastError());
   }
   hipLaunchKernelGGL(bias_kernel, dim3((unsigned)((ix->n_pad + 255) / 256)), dim3(256), 0, 0, ix->bias.as<float>(), n,

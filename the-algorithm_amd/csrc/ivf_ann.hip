@@ -44,7 +44,9 @@
 #include "abi_guard.h"
 #include "ann_by_id_internal.h"
 #include "ivf_device_rows.h"
+#include "faiss_restore.h"
 #include "ivf_kernels.h"
+#include "ivf_restore.h"
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
 namespace {
@@ -89,6 +91,21 @@ __global__ void scatter_rows_kernel(const _Float16 *__restrict__ flat, const flo
     lbias[slot] = metric == IVF_METRIC_L2 ? -0.5f * sumsq[src] : 0.0f;
     lrank[slot] = rank;
   }
+}
+// Restoring a saved index: the sum of squares of stored fp16 rows, by the second half of store_rows_kernel exactly -- one
+// wave per row, lane l sums components l, l + 64, ... in fp64, then the same shuffle tree -- so that a restored row carries
+// the bits it carried when it was added.
+__global__ void stored_sumsq_kernel(const _Float16 *__restrict__ flat, int64_t n, int d, float *__restrict__ sumsq) {
+  const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  double ss16 = 0;
+  for (int k = lane; k < d; k += 64) {
+    const float back = (float)flat[row * d + k];
+    ss16 += (double)back * (double)back;
+  }
+  ss16 = wave_sum(ss16);
+  if (lane == 0) sumsq[row] = (float)ss16;
 }
 // One workgroup per cell: component k of the mean is summed by one thread over the cell's rows in position order, in
 // fp64 -- a fixed order, no floating-point atomics.  InnerProduct / Cosine: the mean is scaled to unit length, its
@@ -275,6 +292,7 @@ struct ivf_index {
   int64_t last_rows = 0;
   float t_coarse = 0, t_scan = 0, t_sel = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  RestoreState rs;  // faiss_restore.h
   ~ivf_index() {
     if (coarse) (void)dann_index_destroy(coarse);
     for (auto &e : ev)
@@ -447,9 +465,9 @@ int layout_lists(ivf_index *ix) {
   return IVF_OK;
 }
 
-int build_coarse(ivf_index *ix, const float *d_cent) {
+int build_coarse(ivf_index *ix, const float *d_cent, bool stored = false) {
   dann_index *c = nullptr;
-  DCALL(ann_by_id::dann_build_device(ix->device, ix->metric, ix->nlist, ix->d, d_cent, &c));
+  DCALL(ann_by_id::dann_build_device(ix->device, ix->metric, ix->nlist, ix->d, d_cent, &c, stored));
   if (ix->coarse) (void)dann_index_destroy(ix->coarse);
   ix->coarse = c;
   return IVF_OK;
@@ -646,6 +664,88 @@ int ivf_internal::train_device(int32_t device, int32_t metric, int32_t d, int32_
                                int32_t niter, uint64_t seed, ivf_index **out) try {
   return train_rows(device, metric, d, nlist, n_train, d_rows, true, niter, seed, out);
 } ABI_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// restoring a saved index (faiss_restore.h)
+// ---------------------------------------------------------------------------------------------
+int64_t ivf_internal::restore_slab_rows(int32_t d) { return std::max<int64_t>(1, (int64_t)(32 << 20) / (d * 2 + 12)); }
+
+int ivf_internal::restore_begin(int32_t device, int32_t metric, int32_t d, int32_t nlist, const float *centroids, int32_t ids_mode,
+                                int64_t n, ivf_index **out) try {
+  if (!centroids || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist)) return rc;
+  if (n < 0 || n >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
+  if (ids_mode < -1 || ids_mode > 1 || (n == 0) != (ids_mode == -1)) return fail(IVF_EINVAL, "ids mode does not fit the row count");
+  std::unique_ptr<ivf_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, ix)) return rc;
+  Buf cent;
+  ITRY(cent.reserve((size_t)nlist * d * sizeof(float)));
+  ITRY(hipMemcpy(cent.p, centroids, (size_t)nlist * d * sizeof(float), hipMemcpyHostToDevice));
+  if (int rc = build_coarse(ix.get(), cent.as<float>(), true)) return rc;
+  ITRY(ix->flat.reserve((size_t)n * d * sizeof(_Float16)));
+  ITRY(ix->sumsq.reserve((size_t)n * 4));
+  ITRY(ix->cell.reserve((size_t)n * 4));
+  ITRY(ix->ids.reserve((size_t)n * 8));
+  ix->rs.n = n;
+  ix->rs.ids_mode = ids_mode;
+  ix->rs.open = true;
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_internal::restore_stage(ivf_index *ix, int64_t m, int64_t **ids, int32_t **cells, uint16_t **rows16) try {
+  if (!ix || !ix->rs.open || !ids || !cells || !rows16) return fail(IVF_EINVAL, "no restore in progress");
+  if (m < 1 || m > restore_slab_rows(ix->d)) return fail(IVF_EINVAL, "slab size out of range");
+  ITRY(hipSetDevice(ix->device));
+  ITRY(ix->rs.stage(m, (size_t)ix->d * sizeof(_Float16)));
+  *ids = ix->rs.ids();
+  *cells = ix->rs.cells();
+  *rows16 = (uint16_t *)ix->rs.payload();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_internal::restore_slab(ivf_index *ix, int64_t r0, int64_t m) try {
+  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
+  RestoreState &rs = ix->rs;
+  if (m < 1 || m > rs.slab || r0 != rs.done || m > rs.n - r0) return fail(IVF_EINVAL, "slab outside the rows announced");
+  ITRY(hipSetDevice(ix->device));
+  uint32_t bad[2] = {0, 0};
+  ITRY(restore_upload(rs, r0, m, ix->nlist, ix->ids.as<int64_t>(), ix->cell.as<int32_t>(), ix->flat.p, bad));
+  if (bad[0] != 0xffffffffu)
+    return fail(IVF_EINVAL, "row " + std::to_string(bad[0]) + ": its cell is outside [0, nlist = " + std::to_string(ix->nlist) + ")");
+  if (bad[1] != 0xffffffffu)
+    return fail(IVF_EINVAL, "row " + std::to_string(bad[1]) + ": the ids of this index are positions, and its id is not its position");
+  hipLaunchKernelGGL(stored_sumsq_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, ix->flat.as<_Float16>() + (size_t)r0 * ix->d, m,
+                     ix->d, ix->sumsq.as<float>() + r0);
+  ITRY(hipGetLastError());
+  ITRY(hipDeviceSynchronize());
+  rs.done = r0 + m;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_internal::restore_end(ivf_index *ix) try {
+  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
+  if (ix->rs.done != ix->rs.n) return fail(IVF_EINVAL, "rows are missing");
+  ITRY(hipSetDevice(ix->device));
+  ix->n = ix->rs.n;
+  ix->ids_mode = ix->rs.ids_mode;
+  ix->rs.close();
+  return ix->n > 0 ? layout_lists(ix) : IVF_OK;
+} ABI_CATCH
+
+int ivf_internal::export_rows(const ivf_index *ix, int64_t r0, int64_t m, int64_t *ids, int32_t *cells, uint16_t *rows16) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (r0 < 0 || m < 0 || r0 > ix->n || m > ix->n - r0) return fail(IVF_EINVAL, "rows outside the index");
+  if (m == 0) return IVF_OK;
+  ITRY(hipSetDevice(ix->device));
+  if (ids) ITRY(hipMemcpy(ids, ix->ids.as<int64_t>() + r0, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (cells) ITRY(hipMemcpy(cells, ix->cell.as<int32_t>() + r0, (size_t)m * 4, hipMemcpyDeviceToHost));
+  if (rows16)
+    ITRY(hipMemcpy(rows16, ix->flat.as<_Float16>() + (size_t)r0 * ix->d, (size_t)m * ix->d * sizeof(_Float16), hipMemcpyDeviceToHost));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivf_internal::ids_mode(const ivf_index *ix) { return ix->ids_mode; }
 
 extern "C" {
 

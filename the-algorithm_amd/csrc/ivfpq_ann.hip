@@ -43,7 +43,9 @@
 #include "abi_guard.h"
 #include "ann_by_id_internal.h"
 #include "ivf_device_rows.h"
+#include "faiss_restore.h"
 #include "ivf_kernels.h"
+#include "ivf_restore.h"
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
 namespace {
@@ -393,6 +395,7 @@ struct ivfpq_index {
   int64_t last_rows = 0;
   float t_coarse = 0, t_scan = 0, t_sel = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  RestoreState rs;  // faiss_restore.h
   ~ivfpq_index() {
     if (coarse) (void)dann_index_destroy(coarse);
     for (auto &e : ev)
@@ -901,6 +904,82 @@ int ivfpq_internal::pq_train_plain(int32_t device, const _Float16 *d_rows16, int
   ITRY(hipDeviceSynchronize());
   return IVF_OK;
 } ABI_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// restoring a saved index (faiss_restore.h)
+// ---------------------------------------------------------------------------------------------
+int64_t ivfpq_internal::restore_slab_rows(int32_t M) { return std::max<int64_t>(1, (int64_t)(32 << 20) / (M + 12)); }
+
+int ivfpq_internal::restore_begin(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, const float *centroids,
+                                  const float *codebooks, int32_t ids_mode, int64_t n, ivfpq_index **out) try {
+  if (!centroids || !codebooks || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d, nlist, M)) return rc;
+  if (n < 0 || n >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
+  if (ids_mode < -1 || ids_mode > 1 || (n == 0) != (ids_mode == -1)) return fail(IVF_EINVAL, "ids mode does not fit the row count");
+  std::unique_ptr<ivfpq_index> ix;
+  if (int rc = new_index(device, metric, d, nlist, M, ix)) return rc;
+  // the stored centroids are what the index keeps and what its coarse quantizer holds: neither is rounded or normalised again
+  ITRY(hipMemcpy(ix->cent.p, centroids, (size_t)nlist * d * sizeof(float), hipMemcpyHostToDevice));
+  DCALL(ann_by_id::dann_build_device(device, metric, nlist, d, ix->cent.as<float>(), &ix->coarse, true));
+  ITRY(hipMemcpy(ix->cb.p, codebooks, (size_t)M * KSUB * ix->dsub * sizeof(float), hipMemcpyHostToDevice));
+  ITRY(ix->codes.reserve((size_t)n * M));
+  ITRY(ix->cell.reserve((size_t)n * 4));
+  ITRY(ix->ids.reserve((size_t)n * 8));
+  ix->rs.n = n;
+  ix->rs.ids_mode = ids_mode;
+  ix->rs.open = true;
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::restore_stage(ivfpq_index *ix, int64_t m, int64_t **ids, int32_t **cells, uint8_t **codes) try {
+  if (!ix || !ix->rs.open || !ids || !cells || !codes) return fail(IVF_EINVAL, "no restore in progress");
+  if (m < 1 || m > restore_slab_rows(ix->M)) return fail(IVF_EINVAL, "slab size out of range");
+  ITRY(hipSetDevice(ix->device));
+  ITRY(ix->rs.stage(m, (size_t)ix->M));
+  *ids = ix->rs.ids();
+  *cells = ix->rs.cells();
+  *codes = (uint8_t *)ix->rs.payload();
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::restore_slab(ivfpq_index *ix, int64_t r0, int64_t m) try {
+  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
+  RestoreState &rs = ix->rs;
+  if (m < 1 || m > rs.slab || r0 != rs.done || m > rs.n - r0) return fail(IVF_EINVAL, "slab outside the rows announced");
+  ITRY(hipSetDevice(ix->device));
+  uint32_t bad[2] = {0, 0};
+  ITRY(restore_upload(rs, r0, m, ix->nlist, ix->ids.as<int64_t>(), ix->cell.as<int32_t>(), ix->codes.p, bad));
+  if (bad[0] != 0xffffffffu)
+    return fail(IVF_EINVAL, "row " + std::to_string(bad[0]) + ": its cell is outside [0, nlist = " + std::to_string(ix->nlist) + ")");
+  if (bad[1] != 0xffffffffu)
+    return fail(IVF_EINVAL, "row " + std::to_string(bad[1]) + ": the ids of this index are positions, and its id is not its position");
+  rs.done = r0 + m;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::restore_end(ivfpq_index *ix) try {
+  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
+  if (ix->rs.done != ix->rs.n) return fail(IVF_EINVAL, "rows are missing");
+  ITRY(hipSetDevice(ix->device));
+  ix->n = ix->rs.n;
+  ix->ids_mode = ix->rs.ids_mode;
+  ix->rs.close();
+  return ix->n > 0 ? layout_lists(ix) : IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::export_rows(const ivfpq_index *ix, int64_t r0, int64_t m, int64_t *ids, int32_t *cells, uint8_t *codes) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (r0 < 0 || m < 0 || r0 > ix->n || m > ix->n - r0) return fail(IVF_EINVAL, "rows outside the index");
+  if (m == 0) return IVF_OK;
+  ITRY(hipSetDevice(ix->device));
+  if (ids) ITRY(hipMemcpy(ids, ix->ids.as<int64_t>() + r0, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (cells) ITRY(hipMemcpy(cells, ix->cell.as<int32_t>() + r0, (size_t)m * 4, hipMemcpyDeviceToHost));
+  if (codes) ITRY(hipMemcpy(codes, ix->codes.as<uint8_t>() + (size_t)r0 * ix->M, (size_t)m * ix->M, hipMemcpyDeviceToHost));
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::ids_mode(const ivfpq_index *ix) { return ix->ids_mode; }
 
 extern "C" {
 

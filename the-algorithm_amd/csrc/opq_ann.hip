@@ -35,6 +35,7 @@
 #include "sann_device.h"  // mix64
 #include "abi_guard.h"
 #include "ivf_device_rows.h"
+#include "faiss_restore.h"
 #include "ivf_kernels.h"
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
@@ -493,6 +494,23 @@ int stage_and_transform(opq_index *ix, const float *rows, int64_t m, bool timed)
 int64_t in_slab_rows(const opq_index *ix) { return ivfpq_internal::slab_rows(ix->d_in); }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// restoring a saved index (faiss_restore.h): the matrix as given, the inner index begun with its stored values
+// ---------------------------------------------------------------------------------------------
+int opq_internal::restore_begin(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, int32_t nlist, int32_t M, const float *A,
+                                const float *centroids, const float *codebooks, int32_t ids_mode, int64_t n, opq_index **out) try {
+  if (!A || !centroids || !codebooks || !out) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_shape(metric, d_in, d_out, nlist, M)) return rc;
+  std::unique_ptr<opq_index> ix;
+  if (int rc = new_index(device, metric, d_in, d_out, nlist, M, ix)) return rc;
+  if (int rc = set_matrix(ix.get(), A)) return rc;
+  PCALL(ivfpq_internal::restore_begin(device, inner_metric(metric), d_out, nlist, M, centroids, codebooks, ids_mode, n, &ix->inner));
+  *out = ix.release();
+  return IVF_OK;
+} ABI_CATCH
+
+ivfpq_index *opq_internal::inner(const opq_index *ix) { return ix->inner; }
 
 extern "C" {
 
