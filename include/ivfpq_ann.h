@@ -6,8 +6,9 @@
  * What it replaces (paths relative to the reference's ann/src/main/):
  *   scala/com/twitter/ann/faiss/FaissIndexer.scala:82-92        index_factory(any factory string) -> train -> add_with_ids
  *   thrift/com/twitter/ann/common/ann_common.thrift:45          nprobe: "How many cells to visit in IVFPQ"
- * Not here: the decomposed "precomputed table" form, polysemous codes (`ht`), refinement (`quantizer_kfactor_rf`), an HNSW
- * coarse quantizer, by-id queries over this index.  The OPQ pre-transform is a layer in front of this index: opq_ann.h.
+ * Not here: the decomposed "precomputed table" form, polysemous codes (`ht`), a refine index as the coarse quantizer
+ * (`quantizer_kfactor_rf`), an HNSW coarse quantizer, by-id queries over this index.  The OPQ pre-transform is a layer in
+ * front of this index: opq_ann.h.  Re-ranking of the answers by stored rows (`,RFlat`) is a layer around it: refine_ann.h.
  *
  * Status codes, metric numbers, the preparation of rows, queries and centroids (fp16, Cosine L2-normalised first), the
  * distances (L2 = ||q - x||, Cosine = 1 - cos, InnerProduct = 1 - <q, x>), the tie rules, the ids rule and the clamping of
@@ -33,7 +34,7 @@
  *     InnerProduct / Cosine:  sim = <q, centroid[c]> + sum_m <q_m, cb[m][code_m]>; the distance is 1 - sim.
  *     A row's value comes from a fixed sequence of operations that depends neither on scheduling nor on the other
  *     queries of the batch; rows with equal codes in one cell tie exactly and come out in id order.
- *   Memory: the index keeps no copy of the rows.  Per row: M code bytes in the order added, its id and its cell, and the
+ *   Memory: the index keeps no copy of the rows (refine_ann.h adds one and re-ranks by it).  Per row: M code bytes in the order added, its id and its cell, and the
  *     lists, which every add lays out again device to device in (cell, id) order.
  *
  * No function throws or aborts; every function returns a status (IVF_OK, IVF_EINVAL, ... of ivf_ann.h), the message is in

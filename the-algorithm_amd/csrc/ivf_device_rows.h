@@ -40,6 +40,16 @@ int64_t slab_rows(int d);  // rows of dimension d in a 64-MiB fp32 slab
 int search_device(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *out_dist,
                   int64_t *out_ids, int32_t *out_counts);
 
+// search_device with the select step writing, instead of the answer, what the re-rank of refine_ann.hip needs: for query q
+// its candidates best first by (distance, id) as add-order positions d_pos[q * k ..] (-1 past the count), their ranks in
+// (id, position) order d_rank[q * k ..] and their number d_counts[q].  All three are device buffers; nothing but the scan's
+// round flags leaves the device.  The last-search exports of the index (probes, stats) describe this search.
+int search_positions(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t *d_pos,
+                     uint32_t *d_rank, int32_t *d_counts);
+// The ids in (id, position) order on the device, [n]: ids_sorted[rank] is the id of the candidate of that rank.
+const int64_t *device_ids_sorted(const ivfpq_index *ix);
+int device_of(const ivfpq_index *ix);  // the device the index lives on
+
 // A product quantiser on the rows themselves (no coarse quantizer, no residuals): M sub-quantizers of 256 codewords over
 // n fp16 device rows [n][d], by the encoder and the mean kernel of the index with one all-zero centroid and every row in
 // cell 0.  init: the initial codewords are picked by the rule of ivfpq_ann.h with this seed; otherwise d_cb holds them.
@@ -48,3 +58,18 @@ int pq_train_plain(int32_t device, const _Float16 *d_rows16, int64_t n, int32_t 
                    uint64_t seed, float *d_cb, uint8_t *d_codes);
 
 }  // namespace ivfpq_internal
+
+struct opq_index;
+
+namespace opq_internal __attribute__((visibility("hidden"))) {
+
+// opq_index_add over rows that are on the device (row-major fp32 [m][d_in], not yet prepared): add_begin and add_end are
+// those of the inner index (faiss_restore.h's inner()); add_slab transforms rows [r0, r0 + m) of the add, m at most
+// slab_rows(), and hands them to the inner add_slab.
+int add_slab(opq_index *ix, int64_t r0, int64_t m, const float *d_rows);
+int64_t slab_rows(const opq_index *ix);
+// ivfpq_internal::search_positions over device queries [nq][d_in], which are prepared and transformed first.
+int search_positions(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t *d_pos,
+                     uint32_t *d_rank, int32_t *d_counts);
+
+}  // namespace opq_internal

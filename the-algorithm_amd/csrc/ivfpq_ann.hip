@@ -321,11 +321,15 @@ __global__ __launch_bounds__(256) void adc_scan_kernel(AdcArgs a) {
 }
 
 // per query: sort survivors by (score desc, rank in id order asc), emit the k nearest as distances (ivf_ann.hip's select
-// with this index's scores: -s for L2, the similarity otherwise)
+// with this index's scores: -s for L2, the similarity otherwise).  POSITIONS: emit instead, for the re-rank of
+// refine_ann.hip, the k nearest as add-order positions perm[rank] (-1 past the count) beside their ranks.
+template <bool POSITIONS>
 __global__ __launch_bounds__(512) void pq_select_kernel(const Survivor *__restrict__ surv, const uint32_t *__restrict__ done_cnt,
                                                         const uint32_t *__restrict__ lrank, const int64_t *__restrict__ ids_sorted,
                                                         int metric, int k, float *__restrict__ out_dist,
-                                                        int64_t *__restrict__ out_ids, int32_t *__restrict__ out_counts) {
+                                                        int64_t *__restrict__ out_ids, int32_t *__restrict__ out_counts,
+                                                        const uint32_t *__restrict__ perm, int32_t *__restrict__ out_pos,
+                                                        uint32_t *__restrict__ out_rank) {
   extern __shared__ unsigned long long keys[];
   const int q = blockIdx.x;
   const uint32_t c = min(done_cnt[q], (uint32_t)CAP);
@@ -355,21 +359,41 @@ __global__ __launch_bounds__(512) void pq_select_kernel(const Survivor *__restri
       __syncthreads();
     }
   const uint32_t m = min(c, (uint32_t)k);
-  for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
-    float dist = 0.0f;
-    int64_t id = 0;
-    if (i < m) {
-      unsigned long long key = keys[i];
-      float sc = key2f((uint32_t)(key >> 32));
-      id = ids_sorted[0xffffffffu - (uint32_t)key];
-      if (metric == IVF_METRIC_L2) dist = sqrtf(fmaxf(0.0f, -sc));
-      else dist = 1.0f - sc;
+  if constexpr (POSITIONS) {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
+      int32_t pos = -1;
+      uint32_t rank = 0;
+      if (i < m) {
+        rank = 0xffffffffu - (uint32_t)keys[i];
+        pos = (int32_t)perm[rank];
+      }
+      out_pos[(size_t)q * k + i] = pos;
+      out_rank[(size_t)q * k + i] = rank;
     }
-    out_dist[(size_t)q * k + i] = dist;
-    out_ids[(size_t)q * k + i] = id;
+  } else {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
+      float dist = 0.0f;
+      int64_t id = 0;
+      if (i < m) {
+        unsigned long long key = keys[i];
+        float sc = key2f((uint32_t)(key >> 32));
+        id = ids_sorted[0xffffffffu - (uint32_t)key];
+        if (metric == IVF_METRIC_L2) dist = sqrtf(fmaxf(0.0f, -sc));
+        else dist = 1.0f - sc;
+      }
+      out_dist[(size_t)q * k + i] = dist;
+      out_ids[(size_t)q * k + i] = id;
+    }
   }
   if (threadIdx.x == 0) out_counts[q] = (int32_t)m;
 }
+
+// where the select step of a search writes when it serves ivfpq_internal::search_positions (device buffers)
+struct PosOut {
+  int32_t *pos;
+  uint32_t *rank;
+  int32_t *cnt;
+};
 
 }  // namespace
 
@@ -437,7 +461,8 @@ int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t 
   // both kernels size their LDS by the shape: up to 64 KiB (encoder, dsub = 128) and 66 KiB (scan, M = 64, d = 512)
   ITRY(hipFuncSetAttribute((const void *)encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)encode_lds_bytes(MAX_D / 4)));
   ITRY(hipFuncSetAttribute((const void *)adc_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)adc_lds_bytes(MAX_M, MAX_D)));
-  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
+  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
+  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
   return IVF_OK;
 }
 
@@ -617,7 +642,7 @@ int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq,
 }
 
 int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
-                 float *out_dist, int64_t *out_ids, int32_t *out_counts) {
+                 float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po) {
   const int d = ix->d, nlist = ix->nlist;
   const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
@@ -713,14 +738,24 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
   }
   ITRY(hipEventRecord(ix->ev[2], st));
 
-  hipLaunchKernelGGL(pq_select_kernel, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
-                     ix->done_cnt.as<uint32_t>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
-                     ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
-  ITRY(hipGetLastError());
-  ITRY(hipEventRecord(ix->ev[3], st));
-  ITRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-  ITRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  ITRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (po) {
+    hipLaunchKernelGGL(pq_select_kernel<true>, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
+                       ix->done_cnt.as<uint32_t>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
+                       (float *)nullptr, (int64_t *)nullptr, po->cnt + q0, ix->perm.as<uint32_t>(), po->pos + (size_t)q0 * k,
+                       po->rank + (size_t)q0 * k);
+    ITRY(hipGetLastError());
+    ITRY(hipEventRecord(ix->ev[3], st));
+  } else {
+    hipLaunchKernelGGL(pq_select_kernel<false>, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
+                       ix->done_cnt.as<uint32_t>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
+                       ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>(), (const uint32_t *)nullptr,
+                       (int32_t *)nullptr, (uint32_t *)nullptr);
+    ITRY(hipGetLastError());
+    ITRY(hipEventRecord(ix->ev[3], st));
+    ITRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    ITRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ITRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
   unsigned long long rows = 0;
   ITRY(hipMemcpyAsync(&rows, ix->rows_acc.p, 8, hipMemcpyDeviceToHost, st));
   ITRY(hipStreamSynchronize(st));
@@ -787,8 +822,9 @@ int check_ids_rule(const ivfpq_index *ix, bool with_ids) {
 
 // ivfpq_search, over host queries or over queries that are on the device
 int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe, float *out_dist,
-                int64_t *out_ids, int32_t *out_counts) {
-  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+                int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr) {
+  if (!ix || !queries) return fail(IVF_EINVAL, "null argument");
+  if (po ? !po->pos || !po->rank || !po->cnt : !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
   if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
   if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
   if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
@@ -802,8 +838,8 @@ int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_dev
   ix->t_coarse = ix->t_scan = ix->t_sel = 0;
   for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
     const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
-    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, out_dist + (size_t)q0 * k,
-                              out_ids + (size_t)q0 * k, out_counts + q0))
+    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, po ? nullptr : out_dist + (size_t)q0 * k,
+                              po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po))
       return rc;
   }
   ix->last_nq = nq;
@@ -868,6 +904,15 @@ int ivfpq_internal::search_device(ivfpq_index *ix, int32_t nq, const float *d_qu
                                   int64_t *out_ids, int32_t *out_counts) try {
   return search_rows(ix, nq, d_queries, true, k, nprobe, out_dist, out_ids, out_counts);
 } ABI_CATCH
+
+int ivfpq_internal::search_positions(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t *d_pos,
+                                     uint32_t *d_rank, int32_t *d_counts) try {
+  const PosOut po{d_pos, d_rank, d_counts};
+  return search_rows(ix, nq, d_queries, true, k, nprobe, nullptr, nullptr, nullptr, &po);
+} ABI_CATCH
+
+const int64_t *ivfpq_internal::device_ids_sorted(const ivfpq_index *ix) { return ix->ids_sorted.as<int64_t>(); }
+int ivfpq_internal::device_of(const ivfpq_index *ix) { return ix->device; }
 
 int ivfpq_internal::pq_train_plain(int32_t device, const _Float16 *d_rows16, int64_t n, int32_t d, int32_t M, bool init,
                                    int32_t rounds, uint64_t seed, float *d_cb, uint8_t *d_codes) try {

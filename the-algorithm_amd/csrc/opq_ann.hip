@@ -512,6 +512,40 @@ int opq_internal::restore_begin(int32_t device, int32_t metric, int32_t d_in, in
 
 ivfpq_index *opq_internal::inner(const opq_index *ix) { return ix->inner; }
 
+// ---------------------------------------------------------------------------------------------
+// the device-rows seam (ivf_device_rows.h): what refine_ann.hip shares with opq_index_add and opq_search
+// ---------------------------------------------------------------------------------------------
+int64_t opq_internal::slab_rows(const opq_index *ix) { return std::min(in_slab_rows(ix), ivfpq_internal::slab_rows(ix->d_out)); }
+
+int opq_internal::add_slab(opq_index *ix, int64_t r0, int64_t m, const float *d_rows) try {
+  if (!ix || !d_rows) return fail(IVF_EINVAL, "null argument");
+  if (m < 1 || m > slab_rows(ix)) return fail(IVF_EINVAL, "slab size out of range");
+  ITRY(hipSetDevice(ix->device));
+  ITRY(ix->y.reserve((size_t)m * ix->d_out * sizeof(float)));
+  if (int rc = transform(ix, d_rows, m, ix->metric == IVF_METRIC_COSINE, ix->y.as<float>())) return rc;
+  ITRY(hipDeviceSynchronize());
+  PCALL(ivfpq_internal::add_slab(ix->inner, r0, m, ix->y.as<float>()));
+  return IVF_OK;
+} ABI_CATCH
+
+int opq_internal::search_positions(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t *d_pos,
+                                   uint32_t *d_rank, int32_t *d_counts) try {
+  if (!ix || !d_queries) return fail(IVF_EINVAL, "null argument");
+  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
+  ITRY(hipSetDevice(ix->device));
+  ix->t_transform = 0;
+  ITRY(ix->y.reserve((size_t)nq * ix->d_out * sizeof(float)));
+  ITRY(hipEventRecord(ix->ev[0], 0));
+  if (int rc = transform(ix, d_queries, nq, ix->metric == IVF_METRIC_COSINE, ix->y.as<float>())) return rc;
+  ITRY(hipEventRecord(ix->ev[1], 0));
+  ITRY(hipDeviceSynchronize());
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, ix->ev[0], ix->ev[1]);
+  ix->t_transform += ms;
+  PCALL(ivfpq_internal::search_positions(ix->inner, nq, ix->y.as<float>(), k, nprobe, d_pos, d_rank, d_counts));
+  return IVF_OK;
+} ABI_CATCH
+
 extern "C" {
 
 const char *opq_last_error(void) { return g_err.c_str(); }
