@@ -10,8 +10,9 @@
  *   thrift/com/twitter/ann/common/ann_common.thrift:16-19       enum DistanceMetric { L2, Cosine, InnerProduct }
  * Only the coarse quantizer, its training, the inverted lists and the probed scan are here.  Product quantisation
  * (codebooks, ADC tables) replaces the list payload and the scan's inner product, nothing else: that index is
- * ivfpq_ann.h.  `ht` and `quantizer_kfactor_rf` (a refine index as the coarse quantizer) are in neither; top-level
- * refinement of the product-quantised answers by stored rows is refine_ann.h.
+ * ivfpq_ann.h.  `quantizer_kfactor_rf` (a refine index as the coarse quantizer) is in neither; `ht` (polysemous codes over
+ * the product-quantised lists) is polysemous_ann.h; top-level refinement of the product-quantised answers by stored rows
+ * is refine_ann.h.
  *
  * Arithmetic: as in dense_ann.h.  Rows, queries and centroids are rounded to fp16 (Cosine: L2-normalised first, the
  * index then behaves as InnerProduct), products accumulate in fp32 on the matrix cores.  Distances are those of

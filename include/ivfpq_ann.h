@@ -6,9 +6,10 @@
  * What it replaces (paths relative to the reference's ann/src/main/):
  *   scala/com/twitter/ann/faiss/FaissIndexer.scala:82-92        index_factory(any factory string) -> train -> add_with_ids
  *   thrift/com/twitter/ann/common/ann_common.thrift:45          nprobe: "How many cells to visit in IVFPQ"
- * Not here: the decomposed "precomputed table" form, polysemous codes (`ht`), a refine index as the coarse quantizer
- * (`quantizer_kfactor_rf`), an HNSW coarse quantizer, by-id queries over this index.  The OPQ pre-transform is a layer in
- * front of this index: opq_ann.h.  Re-ranking of the answers by stored rows (`,RFlat`) is a layer around it: refine_ann.h.
+ * Not here: the decomposed "precomputed table" form, a refine index as the coarse quantizer (`quantizer_kfactor_rf`), an
+ * HNSW coarse quantizer, by-id queries over this index.  The OPQ pre-transform is a layer in front of this index:
+ * opq_ann.h.  Re-ranking of the answers by stored rows (`,RFlat`) is a layer around it: refine_ann.h.  Polysemous codes and
+ * the search they filter (`ht`) are declared in polysemous_ann.h, over the handles of this header.
  *
  * Status codes, metric numbers, the preparation of rows, queries and centroids (fp16, Cosine L2-normalised first), the
  * distances (L2 = ||q - x||, Cosine = 1 - cos, InnerProduct = 1 - <q, x>), the tie rules, the ids rule and the clamping of

@@ -9,9 +9,10 @@
  *                                                               dout = (d / M) M, nlist = N / 20
  *   scala/com/twitter/ann/faiss/FaissIndexer.scala:82-92        index_factory(any factory string) -> train -> add_with_ids
  *   scala/com/twitter/ann/faiss/QueryableIndexAdapter.scala:43-65   Cosine: normalise, search by inner product, 1 - sim
- * Not here: `ht`, a refine index as the coarse quantizer (`quantizer_kfactor_rf`), an HNSW coarse quantizer, by-id queries
+ * Not here: a refine index as the coarse quantizer (`quantizer_kfactor_rf`), an HNSW coarse quantizer, by-id queries
  * over this index, OPQ with a number of sub-quantizers other than the index's M.  Top-level refinement (`,RFlat`: the
- * answers re-ranked by the stored rows, before the transform) is refine_ann.h.
+ * answers re-ranked by the stored rows, before the transform) is refine_ann.h; polysemous codes and `ht` are
+ * polysemous_ann.h, over the handles of this header.
  *
  * Status codes and metric numbers are those of ivf_ann.h; M, nlist, k, nprobe, the ids rule and everything behind the
  * transform are those of ivfpq_ann.h.

@@ -27,6 +27,10 @@ namespace ivfpq_internal __attribute__((visibility("hidden"))) {
 int train_device(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train, const float *d_rows,
                  int32_t niter, uint64_t seed, ivfpq_index **out);
 
+// ivfpq_index_train_polysemous (polysemous_ann.h) over training rows that are on the device.
+int train_device_polysemous(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train, const float *d_rows,
+                            int32_t niter, uint64_t seed, int64_t anneal_iters, ivfpq_index **out);
+
 // ivfpq_index_add in three steps.  add_begin refuses what ivfpq_index_add refuses (n > 0) and makes room for n rows;
 // add_slab prepares, assigns and encodes rows [r0, r0 + m) of the add from device rows (row-major fp32 [m][d]; m at most
 // slab_rows()); add_end takes the ids (host, or NULL), counts the rows in and lays the lists out again.  The index is
@@ -39,6 +43,13 @@ int64_t slab_rows(int d);  // rows of dimension d in a 64-MiB fp32 slab
 // ivfpq_search over queries that are on the device (row-major fp32 [nq][d]); the outputs are host buffers.
 int search_device(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *out_dist,
                   int64_t *out_ids, int32_t *out_counts);
+
+// ivfpq_search_ht (polysemous_ann.h) over queries that are on the device; ht <= 0 is search_device.
+int search_device_ht(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht, float *out_dist,
+                     int64_t *out_ids, int32_t *out_counts);
+
+// After a search_device that stood in for a search with ht <= 0: every scanned row counts as scored (ivfpq_last_ht_stats).
+int search_stats_unfiltered(ivfpq_index *ix);
 
 // search_device with the select step writing, instead of the answer, what the re-rank of refine_ann.hip needs: for query q
 // its candidates best first by (distance, id) as add-order positions d_pos[q * k ..] (-1 past the count), their ranks in

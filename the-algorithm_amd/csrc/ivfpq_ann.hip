@@ -33,12 +33,14 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <thread>
 #include <unordered_set>
 #include <vector>
 
 #include "../../include/dense_ann.h"
 #include "../../include/ivf_ann.h"
 #include "../../include/ivfpq_ann.h"
+#include "../../include/polysemous_ann.h"
 #include "sann_device.h"  // mix64
 #include "abi_guard.h"
 #include "ann_by_id_internal.h"
@@ -233,20 +235,73 @@ struct AdcArgs {
   int d, M, dsub, metric;
 };
 
-__global__ __launch_bounds__(256) void adc_scan_kernel(AdcArgs a) {
+// what the Hamming-filtered scan (include/polysemous_ann.h) is given beside AdcArgs
+struct HtArgs {
+  const int32_t *probes;       // the chunk's rows of the probe export, [nq][nprobe]
+  uint8_t *qcodes;             // the chunk's rows of the query-code export, [nq][nprobe][M]
+  unsigned long long *scored;  // the rows that pass the filter are counted here in the first round, NULL in a later one
+  int nprobe, ht;
+};
+
+// s_code[m] = argmin_j tab[m][j], ties to the lower j: wave w takes subspaces w, w + 4, ...; a lane looks at entries lane,
+// lane + 64, ... in ascending order, then a fixed xor tree over (value, j)
+__device__ __forceinline__ void query_code(const float *__restrict__ tab, int M, int lane, int w, uint8_t *__restrict__ s_code) {
+  for (int m = w; m < M; m += 4) {
+    const float *tb = tab + m * KSUB;
+    float best = tb[lane];
+    int arg = lane;
+#pragma unroll
+    for (int u = 1; u < 4; ++u) {
+      const float v = tb[lane + 64 * u];
+      if (v < best) {
+        best = v;
+        arg = lane + 64 * u;
+      }
+    }
+    for (int o = 32; o; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oa = __shfl_xor(arg, o, 64);
+      if (ov < best || (ov == best && oa < arg)) {
+        best = ov;
+        arg = oa;
+      }
+    }
+    if (lane == 0) s_code[m] = (uint8_t)arg;
+  }
+}
+
+// HT = false is ivfpq_search's scan, statement for statement what it was before the filter existed.  HT = true: the pair's
+// query code (the encoding of fl32(q - centroid) by the encoder rule: for L2 an arg-min over the table, which holds exactly
+// those distances; otherwise a pass over the codebook that borrows the table's LDS before the table is built) goes to M
+// bytes of LDS behind s_u and to the export; a lane XORs its row's code dwords against it (a broadcast read) and only a
+// row at Hamming distance < ht adds its table entries -- the same additions in the same order.
+template <bool HT>
+__device__ __forceinline__ void adc_scan_body(const AdcArgs &a, const HtArgs &h) {
   extern __shared__ float adc_lds[];
   float *s_tab = adc_lds;               // [M][256]
   float *s_u = adc_lds + a.M * KSUB;    // [d]: q - centroid (L2) or q
   __shared__ float s_qc;
+  __shared__ int s_slot;  // HT: where the pair's cell stands in the query's row of probes (-1: nowhere)
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int d = a.d, M = a.M, dsub = a.dsub;
   const uint32_t cell = a.pair_cell[blockIdx.x], q = a.pair_q[blockIdx.x];
   const uint32_t size = a.sizes[cell];
   const float thr = a.tau[q];
-  if (size == 0 || !(thr < INFINITY)) return;  // an empty list, or a fallback round this query is not part of
+  if constexpr (HT) {
+    if (!(thr < INFINITY)) return;  // a fallback round this query is not part of (an empty list still has a query code)
+  } else {
+    if (size == 0 || !(thr < INFINITY)) return;  // an empty list, or a fallback round this query is not part of
+  }
   const bool l2 = a.metric == IVF_METRIC_L2;
   const _Float16 *qp = a.q16 + (size_t)q * d;
   const float *cp = a.cent + (size_t)cell * d;
+  uint8_t *s_code = (uint8_t *)(s_u + d);  // HT: [M], read back as M / 4 dwords
+  if constexpr (HT) {
+    if (t == 0) s_slot = -1;
+    __syncthreads();
+    for (int j = t; j < h.nprobe; j += 256)
+      if ((uint32_t)h.probes[(size_t)q * h.nprobe + j] == cell) s_slot = j;
+  }
   for (int i = t; i < d; i += 256) s_u[i] = l2 ? (float)qp[i] - cp[i] : (float)qp[i];
   if (w == 0) {
     // <q, c>: lane l sums the products of components l, l + 64, ... in ascending order, then a fixed shuffle tree
@@ -257,6 +312,25 @@ __global__ __launch_bounds__(256) void adc_scan_kernel(AdcArgs a) {
     if (lane == 0) s_qc = p;
   }
   __syncthreads();
+  if constexpr (HT) {
+    if (!l2) {
+      // ||fl32(q - c)_m - cb[m][j]||^2 as the encoder sums it, thread j owning codeword j; the table's LDS holds them for now
+      for (int m = 0; m < M; ++m) {
+        const float *cw = a.cb + ((size_t)m * KSUB + t) * dsub;
+        const float *u = s_u + m * dsub, *c = cp + m * dsub;
+        float acc = 0.0f;
+        for (int i = 0; i < dsub; ++i) {
+          const float r = u[i] - c[i];
+          const float e = r - cw[i];
+          acc += e * e;
+        }
+        s_tab[m * KSUB + t] = acc;
+      }
+      __syncthreads();
+      query_code(s_tab, M, lane, w, s_code);
+      __syncthreads();
+    }
+  }
   // the table: thread j owns codeword j of every subspace, components in ascending order
   for (int m = 0; m < M; ++m) {
     const float *cw = a.cb + ((size_t)m * KSUB + t) * dsub;
@@ -291,24 +365,42 @@ __global__ __launch_bounds__(256) void adc_scan_kernel(AdcArgs a) {
     s_tab[m * KSUB + t] = acc;
   }
   __syncthreads();
+  if constexpr (HT) {
+    if (l2) {
+      query_code(s_tab, M, lane, w, s_code);
+      __syncthreads();
+    }
+    if (t < M && s_slot >= 0) h.qcodes[((size_t)q * h.nprobe + s_slot) * M + t] = s_code[t];
+  }
   const float acc0 = l2 ? 0.0f : s_qc;
   const int M4 = M >> 2;
   const uint32_t b0 = a.boff[cell], nb = (size + (uint32_t)LBLOCK - 1u) / (uint32_t)LBLOCK;
+  unsigned long long scored = 0;  // HT: the wave's rows that passed the filter (the same in every lane)
   for (uint32_t blk = w; blk < nb; blk += 4) {
     const size_t gb = (size_t)b0 + blk;
     const uint32_t *cp4 = a.lc + gb * M4 * LBLOCK + lane;
+    bool keep = true;
+    if constexpr (HT) {
+      const uint32_t *qc4 = (const uint32_t *)s_code;
+      int ham = 0;
+      for (int g = 0; g < M4; ++g) ham += __popc(cp4[(size_t)g * LBLOCK] ^ qc4[g]);
+      keep = blk * (uint32_t)LBLOCK + (uint32_t)lane < size && ham < h.ht;
+      scored += (unsigned long long)__popcll(__ballot(keep));
+    }
     float acc = acc0;
-    for (int g = 0; g < M4; ++g) {
-      const uint32_t c4 = cp4[(size_t)g * LBLOCK];
-      const float *tb = s_tab + (g * 4) * KSUB;
-      acc += tb[c4 & 255u];
-      acc += tb[KSUB + ((c4 >> 8) & 255u)];
-      acc += tb[2 * KSUB + ((c4 >> 16) & 255u)];
-      acc += tb[3 * KSUB + (c4 >> 24)];
+    if (keep) {
+      for (int g = 0; g < M4; ++g) {
+        const uint32_t c4 = cp4[(size_t)g * LBLOCK];
+        const float *tb = s_tab + (g * 4) * KSUB;
+        acc += tb[c4 & 255u];
+        acc += tb[KSUB + ((c4 >> 8) & 255u)];
+        acc += tb[2 * KSUB + ((c4 >> 16) & 255u)];
+        acc += tb[3 * KSUB + (c4 >> 24)];
+      }
     }
     const float score = l2 ? -acc : acc;
     // the wave's survivors take consecutive slots, reserved by one integer atomic of its first surviving lane
-    const bool pass = blk * (uint32_t)LBLOCK + (uint32_t)lane < size && score >= thr;
+    const bool pass = keep && blk * (uint32_t)LBLOCK + (uint32_t)lane < size && score >= thr;
     const unsigned long long mask = __ballot(pass);
     if (mask == 0) continue;
     const int leader = __ffsll((long long)mask) - 1;
@@ -318,7 +410,13 @@ __global__ __launch_bounds__(256) void adc_scan_kernel(AdcArgs a) {
     const uint32_t pos = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
     if (pass && pos < (uint32_t)CAP) a.surv[(size_t)q * CAP + pos] = Survivor{score, (uint32_t)(gb * LBLOCK) + (uint32_t)lane};
   }
+  if constexpr (HT) {
+    if (h.scored && lane == 0 && scored) atomicAdd(h.scored, scored);  // one integer atomic per wave
+  }
 }
+
+__global__ __launch_bounds__(256) void adc_scan_kernel(AdcArgs a) { adc_scan_body<false>(a, HtArgs{}); }
+__global__ __launch_bounds__(256) void adc_scan_ht_kernel(AdcArgs a, HtArgs h) { adc_scan_body<true>(a, h); }
 
 // per query: sort survivors by (score desc, rank in id order asc), emit the k nearest as distances (ivf_ann.hip's select
 // with this index's scores: -s for L2, the similarity otherwise).  POSITIONS: emit instead, for the re-rank of
@@ -418,6 +516,11 @@ struct ivfpq_index {
   int32_t last_nq = 0, last_nprobe = 0, last_rounds = 0;
   int64_t last_rows = 0;
   float t_coarse = 0, t_scan = 0, t_sel = 0;
+  // polysemous_ann.h: the flag of the training, and the last search with ht > 0
+  bool polysemous = false;
+  Buf qcodes, scored_acc;
+  int32_t qc_nq = 0, qc_nprobe = 0;
+  int64_t last_scored = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   RestoreState rs;  // faiss_restore.h
   ~ivfpq_index() {
@@ -440,6 +543,7 @@ int check_shape(int32_t metric, int32_t d, int32_t nlist, int32_t M) {
 
 size_t encode_lds_bytes(int dsub) { return (size_t)(ENC_ROWS + ENC_STAGE) * dsub * sizeof(float); }
 size_t adc_lds_bytes(int M, int d) { return ((size_t)M * KSUB + d) * sizeof(float); }
+size_t adc_ht_lds_bytes(int M, int d) { return adc_lds_bytes(M, d) + (size_t)M; }  // + the query code
 
 int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, std::unique_ptr<ivfpq_index> &ix) {
   ITRY(hipSetDevice(device));
@@ -461,6 +565,7 @@ int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t 
   // both kernels size their LDS by the shape: up to 64 KiB (encoder, dsub = 128) and 66 KiB (scan, M = 64, d = 512)
   ITRY(hipFuncSetAttribute((const void *)encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)encode_lds_bytes(MAX_D / 4)));
   ITRY(hipFuncSetAttribute((const void *)adc_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)adc_lds_bytes(MAX_M, MAX_D)));
+  ITRY(hipFuncSetAttribute((const void *)adc_scan_ht_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)adc_ht_lds_bytes(MAX_M, MAX_D)));
   ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
   ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
   return IVF_OK;
@@ -642,7 +747,7 @@ int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq,
 }
 
 int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
-                 float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po) {
+                 float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po, int32_t ht) {
   const int d = ix->d, nlist = ix->nlist;
   const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
@@ -719,9 +824,20 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
   a.M = ix->M;
   a.dsub = ix->dsub;
   a.metric = ix->metric;
+  HtArgs h{};
+  if (ht > 0) {  // the Hamming-filtered scan of polysemous_ann.h (ix->qcodes and ix->scored_acc are the caller's)
+    h.probes = ix->probes.as<int32_t>() + (size_t)q0 * nprobe;
+    h.qcodes = ix->qcodes.as<uint8_t>() + (size_t)q0 * nprobe * ix->M;
+    h.nprobe = nprobe;
+    h.ht = ht;
+  }
   int rounds = 0;
   for (;; ++rounds) {
-    if (ix->n > 0) {
+    if (ht > 0) {
+      h.scored = rounds == 0 ? ix->scored_acc.as<unsigned long long>() : nullptr;
+      hipLaunchKernelGGL(adc_scan_ht_kernel, dim3((unsigned)np), dim3(256), adc_ht_lds_bytes(ix->M, d), st, a, h);
+      ITRY(hipGetLastError());
+    } else if (ix->n > 0) {
       hipLaunchKernelGGL(adc_scan_kernel, dim3((unsigned)np), dim3(256), adc_lds_bytes(ix->M, d), st, a);
       ITRY(hipGetLastError());
     }
@@ -814,6 +930,69 @@ int train_rows(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t
   return IVF_OK;
 }
 
+// new[m][perm[m][j]] = old[m][j].  One thread per component.
+__global__ void renumber_codebooks_kernel(const float *__restrict__ old_cb, const uint8_t *__restrict__ perm, int M, int dsub,
+                                          float *__restrict__ new_cb) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)M * KSUB * dsub) return;
+  const int i = (int)(e % dsub), j = (int)((e / dsub) % KSUB), m = (int)(e / ((int64_t)KSUB * dsub));
+  new_cb[((size_t)m * KSUB + perm[m * KSUB + j]) * dsub + i] = old_cb[e];
+}
+
+// the polysemous step of a training (polysemous_ann.h): one renumbering per subspace on at most 16 host threads, which
+// share nothing but the read-only codebooks; then the codebooks are renumbered on the device.  The index holds no rows.
+int make_polysemous(ivfpq_index *ix, uint64_t seed, int64_t anneal_iters) {
+  const int M = ix->M, dsub = ix->dsub;
+  const size_t count = (size_t)M * KSUB * dsub;
+  std::vector<float> cb(count);
+  ITRY(hipSetDevice(ix->device));
+  ITRY(hipMemcpy(cb.data(), ix->cb.p, count * sizeof(float), hipMemcpyDeviceToHost));
+  std::vector<uint8_t> perm((size_t)M * KSUB);
+  std::vector<int> status((size_t)M, IVF_OK);
+  std::vector<std::string> message((size_t)M);
+  const int threads = std::min(M, 16);
+  auto work = [&](int first) {
+    for (int m = first; m < M; m += threads) {
+      double before = 0, after = 0;
+      status[(size_t)m] = polysemous_optimize_codebook(dsub, cb.data() + (size_t)m * KSUB * dsub, anneal_iters,
+                                                       sann::mix64(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(m + 1)),
+                                                       perm.data() + (size_t)m * KSUB, &before, &after);
+      if (status[(size_t)m]) message[(size_t)m] = polysemous_last_error();  // (thread-local: read where it was written)
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int u = 1; u < threads; ++u) pool.emplace_back(work, u);
+  work(0);
+  for (auto &th : pool) th.join();
+  for (int m = 0; m < M; ++m)
+    if (status[(size_t)m]) return fail(status[(size_t)m], "polysemous training, subspace " + std::to_string(m) + ": " + message[(size_t)m]);
+  Buf old_cb, perm_d;
+  ITRY(old_cb.reserve(count * sizeof(float)));
+  ITRY(perm_d.reserve(perm.size()));
+  ITRY(hipMemcpy(old_cb.p, ix->cb.p, count * sizeof(float), hipMemcpyDeviceToDevice));
+  ITRY(hipMemcpy(perm_d.p, perm.data(), perm.size(), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(renumber_codebooks_kernel, dim3(blocks_for((int64_t)count)), dim3(256), 0, 0, old_cb.as<float>(),
+                     perm_d.as<uint8_t>(), M, dsub, ix->cb.as<float>());
+  ITRY(hipGetLastError());
+  ITRY(hipDeviceSynchronize());
+  ix->polysemous = true;
+  return IVF_OK;
+}
+
+// train_rows, then the polysemous step
+int train_rows_polysemous(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
+                          const float *train_vectors, bool on_device, int32_t niter, uint64_t seed, int64_t anneal_iters,
+                          ivfpq_index_t **out) {
+  if (anneal_iters < 0) return fail(IVF_EINVAL, "anneal_iters must be 0 (500000 steps) or a number of steps");
+  if (!out) return fail(IVF_EINVAL, "null argument");
+  ivfpq_index_t *ix = nullptr;
+  if (int rc = train_rows(device, metric, d, nlist, M, n_train, train_vectors, on_device, niter, seed, &ix)) return rc;
+  std::unique_ptr<ivfpq_index> hold(ix);
+  if (int rc = make_polysemous(ix, seed, anneal_iters)) return rc;
+  *out = hold.release();
+  return IVF_OK;
+}
+
 int check_ids_rule(const ivfpq_index *ix, bool with_ids) {
   if (ix->ids_mode == 1 && !with_ids) return fail(IVF_EINVAL, "the index holds rows added with ids: an add must give ids");
   if (ix->ids_mode == 0 && with_ids) return fail(IVF_EINVAL, "the index holds rows added without ids (its ids are positions): ids must be NULL");
@@ -822,7 +1001,7 @@ int check_ids_rule(const ivfpq_index *ix, bool with_ids) {
 
 // ivfpq_search, over host queries or over queries that are on the device
 int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe, float *out_dist,
-                int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr) {
+                int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr, int32_t ht = 0) {
   if (!ix || !queries) return fail(IVF_EINVAL, "null argument");
   if (po ? !po->pos || !po->rank || !po->cnt : !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
   if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
@@ -836,13 +1015,27 @@ int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_dev
   ix->last_rows = 0;
   ix->last_rounds = 0;
   ix->t_coarse = ix->t_scan = ix->t_sel = 0;
+  if (ht > 0) {
+    ix->qc_nq = 0;  // (a failure below leaves no query codes to ask for)
+    ITRY(ix->qcodes.reserve((size_t)nq * nprobe * ix->M));
+    ITRY(ix->scored_acc.reserve(8));
+    ITRY(hipMemset(ix->qcodes.p, 0, (size_t)nq * nprobe * ix->M));
+    ITRY(hipMemset(ix->scored_acc.p, 0, 8));
+  }
   for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
     const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
     if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, po ? nullptr : out_dist + (size_t)q0 * k,
-                              po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po))
+                              po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po, ht))
       return rc;
   }
   ix->last_nq = nq;
+  if (ht > 0) {
+    unsigned long long scored = 0;
+    ITRY(hipMemcpy(&scored, ix->scored_acc.p, 8, hipMemcpyDeviceToHost));
+    ix->last_scored = (int64_t)scored;
+    ix->qc_nq = nq;
+    ix->qc_nprobe = nprobe;
+  }
   return IVF_OK;
 }
 
@@ -910,6 +1103,25 @@ int ivfpq_internal::search_positions(ivfpq_index *ix, int32_t nq, const float *d
   const PosOut po{d_pos, d_rank, d_counts};
   return search_rows(ix, nq, d_queries, true, k, nprobe, nullptr, nullptr, nullptr, &po);
 } ABI_CATCH
+
+int ivfpq_internal::train_device_polysemous(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
+                                            const float *d_rows, int32_t niter, uint64_t seed, int64_t anneal_iters,
+                                            ivfpq_index **out) try {
+  return train_rows_polysemous(device, metric, d, nlist, M, n_train, d_rows, true, niter, seed, anneal_iters, out);
+} ABI_CATCH
+
+int ivfpq_internal::search_device_ht(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht,
+                                     float *out_dist, int64_t *out_ids, int32_t *out_counts) try {
+  if (int rc = search_rows(ix, nq, d_queries, true, k, nprobe, out_dist, out_ids, out_counts, nullptr, std::max(ht, 0))) return rc;
+  if (ht <= 0) ix->last_scored = ix->last_rows;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_internal::search_stats_unfiltered(ivfpq_index *ix) {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  ix->last_scored = ix->last_rows;
+  return IVF_OK;
+}
 
 const int64_t *ivfpq_internal::device_ids_sorted(const ivfpq_index *ix) { return ix->ids_sorted.as<int64_t>(); }
 int ivfpq_internal::device_of(const ivfpq_index *ix) { return ix->device; }
@@ -1066,6 +1278,46 @@ int ivfpq_index_add(ivfpq_index_t *ix, int64_t n, const float *vectors, const in
 int ivfpq_search(ivfpq_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
                  int64_t *out_ids, int32_t *out_counts) try {
   return search_rows(ix, nq, queries, false, k, nprobe, out_dist, out_ids, out_counts);
+} ABI_CATCH
+
+int ivfpq_index_train_polysemous(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
+                                 const float *train_vectors, int32_t niter, uint64_t seed, int64_t anneal_iters,
+                                 ivfpq_index_t **out) try {
+  return train_rows_polysemous(device, metric, d, nlist, M, n_train, train_vectors, false, niter, seed, anneal_iters, out);
+} ABI_CATCH
+
+int ivfpq_index_is_polysemous(const ivfpq_index_t *ix, int32_t *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  *out = ix->polysemous ? 1 : 0;
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_search_ht(ivfpq_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, int32_t ht, float *out_dist,
+                    int64_t *out_ids, int32_t *out_counts) try {
+  if (ht <= 0) {  // the filter is off: ivfpq_search itself
+    if (int rc = ivfpq_search(ix, nq, queries, k, nprobe, out_dist, out_ids, out_counts)) return rc;
+    ix->last_scored = ix->last_rows;
+    return IVF_OK;
+  }
+  return search_rows(ix, nq, queries, false, k, nprobe, out_dist, out_ids, out_counts, nullptr, ht);
+} ABI_CATCH
+
+int ivfpq_last_query_codes(const ivfpq_index_t *ix, int32_t *nq, int32_t *nprobe, uint8_t *out) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (ix->qc_nq == 0) return fail(IVF_EINVAL, "no search with ht > 0 has run on this index: there are no query codes");
+  if (nq) *nq = ix->qc_nq;
+  if (nprobe) *nprobe = ix->qc_nprobe;
+  if (out) {
+    ITRY(hipSetDevice(ix->device));
+    ITRY(hipMemcpy(out, ix->qcodes.p, (size_t)ix->qc_nq * ix->qc_nprobe * ix->M, hipMemcpyDeviceToHost));
+  }
+  return IVF_OK;
+} ABI_CATCH
+
+int ivfpq_last_ht_stats(const ivfpq_index_t *ix, int64_t *rows_scored) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  if (rows_scored) *rows_scored = ix->last_scored;
+  return IVF_OK;
 } ABI_CATCH
 
 int ivfpq_index_info(const ivfpq_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist, int32_t *M) try {

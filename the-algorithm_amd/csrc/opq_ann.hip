@@ -32,6 +32,7 @@
 #include "../../include/ivf_ann.h"
 #include "../../include/ivfpq_ann.h"
 #include "../../include/opq_ann.h"
+#include "../../include/polysemous_ann.h"
 #include "sann_device.h"  // mix64
 #include "abi_guard.h"
 #include "ivf_device_rows.h"
@@ -546,6 +547,12 @@ int opq_internal::search_positions(opq_index *ix, int32_t nq, const float *d_que
   return IVF_OK;
 } ABI_CATCH
 
+namespace {
+int train_index(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, int32_t nlist, int32_t M, int64_t n_train,
+                const float *train_vectors, int32_t niter, int32_t niter_opq, uint64_t seed, bool polysemous, int64_t anneal_iters,
+                opq_index_t **out);
+}
+
 extern "C" {
 
 const char *opq_last_error(void) { return g_err.c_str(); }
@@ -573,6 +580,60 @@ int opq_index_load(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, 
 
 int opq_index_train(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, int32_t nlist, int32_t M, int64_t n_train,
                     const float *train_vectors, int32_t niter, int32_t niter_opq, uint64_t seed, opq_index_t **out) try {
+  return train_index(device, metric, d_in, d_out, nlist, M, n_train, train_vectors, niter, niter_opq, seed, false, 0, out);
+} ABI_CATCH
+
+int opq_index_train_polysemous(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, int32_t nlist, int32_t M,
+                               int64_t n_train, const float *train_vectors, int32_t niter, int32_t niter_opq, uint64_t seed,
+                               int64_t anneal_iters, opq_index_t **out) try {
+  if (anneal_iters < 0) return fail(IVF_EINVAL, "anneal_iters must be 0 (500000 steps) or a number of steps");
+  return train_index(device, metric, d_in, d_out, nlist, M, n_train, train_vectors, niter, niter_opq, seed, true, anneal_iters, out);
+} ABI_CATCH
+
+int opq_index_is_polysemous(const opq_index_t *ix, int32_t *out) try {
+  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
+  PCALL(ivfpq_index_is_polysemous(ix->inner, out));
+  return IVF_OK;
+} ABI_CATCH
+
+int opq_search_ht(opq_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, int32_t ht, float *out_dist,
+                  int64_t *out_ids, int32_t *out_counts) try {
+  if (ht <= 0) {  // the filter is off: opq_search itself
+    if (int rc = opq_search(ix, nq, queries, k, nprobe, out_dist, out_ids, out_counts)) return rc;
+    PCALL(ivfpq_internal::search_stats_unfiltered(ix->inner));
+    return IVF_OK;
+  }
+  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
+  if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
+  if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
+  ITRY(hipSetDevice(ix->device));
+  ix->t_transform = 0;
+  if (int rc = stage_and_transform(ix, queries, nq, true)) return rc;
+  PCALL(ivfpq_internal::search_device_ht(ix->inner, nq, ix->y.as<float>(), k, nprobe, ht, out_dist, out_ids, out_counts));
+  return IVF_OK;
+} ABI_CATCH
+
+int opq_last_query_codes(const opq_index_t *ix, int32_t *nq, int32_t *nprobe, uint8_t *out) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  PCALL(ivfpq_last_query_codes(ix->inner, nq, nprobe, out));
+  return IVF_OK;
+} ABI_CATCH
+
+int opq_last_ht_stats(const opq_index_t *ix, int64_t *rows_scored) try {
+  if (!ix) return fail(IVF_EINVAL, "null index");
+  PCALL(ivfpq_last_ht_stats(ix->inner, rows_scored));
+  return IVF_OK;
+} ABI_CATCH
+
+}  // extern "C"
+
+namespace {
+
+// opq_index_train; with polysemous, the final inner index is trained as ivfpq_index_train_polysemous trains
+int train_index(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, int32_t nlist, int32_t M, int64_t n_train,
+                const float *train_vectors, int32_t niter, int32_t niter_opq, uint64_t seed, bool polysemous, int64_t anneal_iters,
+                opq_index_t **out) {
   if (!train_vectors || !out) return fail(IVF_EINVAL, "null argument");
   if (int rc = check_shape(metric, d_in, d_out, nlist, M)) return rc;
   if (n_train < std::max<int64_t>(nlist, KSUB)) return fail(IVF_EINVAL, "n_train must be at least max(nlist, 256)");
@@ -609,12 +670,20 @@ int opq_index_train(int32_t device, int32_t metric, int32_t d_in, int32_t d_out,
     ITRY(hipDeviceSynchronize());
   }
   ix->tr_transform += (float)ms_since(t0);
-  PCALL(ivfpq_internal::train_device(device, inner_metric(metric), d_out, nlist, M, n_train, ytrain.as<float>(), niter, seed,
-                                     &ix->inner));
+  if (polysemous)
+    PCALL(ivfpq_internal::train_device_polysemous(device, inner_metric(metric), d_out, nlist, M, n_train, ytrain.as<float>(), niter,
+                                                  seed, anneal_iters, &ix->inner));
+  else
+    PCALL(ivfpq_internal::train_device(device, inner_metric(metric), d_out, nlist, M, n_train, ytrain.as<float>(), niter, seed,
+                                       &ix->inner));
   ix->tr_inner += (float)ms_since(t0);
   *out = ix.release();
   return IVF_OK;
-} ABI_CATCH
+}
+
+}  // namespace
+
+extern "C" {
 
 int opq_index_add(opq_index_t *ix, int64_t n, const float *vectors, const int64_t *ids) try {
   if (!ix) return fail(IVF_EINVAL, "null index");
