@@ -2,6 +2,9 @@
 exports (centroids, assignment, probes) -- never with the device's own answers.  Tolerance: the project's 1e-5 / 1e-5 on
 distances (tests/test_dense_gpu.py); ids and cells must agree wherever the restatement's distances are further apart than
 that.  PARITY UNPINNED against Faiss (not vendored in the reference), as the header says."""
+import importlib.util
+import os
+
 import numpy as np
 import pytest
 
@@ -9,6 +12,7 @@ import _ivf_ref as ref
 
 pytestmark = pytest.mark.gpu
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTOL, ATOL = ref.RTOL, ref.ATOL
 METRICS = ["L2", "Cosine", "InnerProduct"]
 
@@ -312,3 +316,20 @@ def test_recall_grows_with_nprobe_and_is_complete_at_nlist(pkg, metric):
     assert recalls[-1] >= 1.0 - (1.0 / k), "complete up to swaps at unclear positions"
     ix.close()
     dense.close()
+
+
+def test_flat_index_answers_as_before_the_shared_core(pkg):
+    """FaissIvfFlat over two adds with ids: both searches with their probes, list_sizes() and assignment(), byte for byte
+    against what the library gave before ivf_ann.hip and ivfpq_ann.hip shared csrc/ivf_core.h
+    (tests/golden/ivf_family_baseline.npz, written by make_ivf_family_baseline.py)."""
+    path = os.path.join(ROOT, "tests", "golden", "make_ivf_family_baseline.py")
+    spec = importlib.util.spec_from_file_location("make_ivf_family_baseline", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    base = np.load(os.path.join(ROOT, "tests", "golden", "ivf_family_baseline.npz"))
+    want = {n: base[n] for n in base.files if n.startswith("flat_")}
+    got = gen.flat_answers(pkg)
+    assert sorted(got) == sorted(want) and len(got) == len(gen.METRICS) * (4 * len(gen.SEARCHES) + 3)
+    for name in sorted(got):
+        assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
+    assert any(want[n].any() for n in want if n.endswith("_dist"))

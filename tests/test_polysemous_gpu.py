@@ -337,3 +337,20 @@ def test_plain_searches_answer_as_before_the_filter(pkg, kind):
     assert sorted(got) == sorted(want.files) and len(got) == 3 * len(gen.METRICS) * len(gen.SEARCHES)
     for name in sorted(got):
         assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
+
+
+def test_filtered_search_answers_as_before_the_shared_core(pkg):
+    """search(q, 10, 4, ht) of an adopted ivfpq index at a threshold where the filter both drops and keeps rows, with
+    last_query_codes() and the rows scored and scanned, byte for byte against what the library gave before ivf_ann.hip and
+    ivfpq_ann.hip shared csrc/ivf_core.h (tests/golden/ivf_family_baseline.npz, written by make_ivf_family_baseline.py)."""
+    path = os.path.join(ROOT, "tests", "golden", "make_ivf_family_baseline.py")
+    spec = importlib.util.spec_from_file_location("make_ivf_family_baseline", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    base = np.load(os.path.join(ROOT, "tests", "golden", "ivf_family_baseline.npz"))
+    want = {n: base[n] for n in base.files if n.startswith("ht_")}
+    got = gen.ht_answers(pkg)
+    assert sorted(got) == sorted(want) and len(got) == 6 * len(gen.METRICS) + 1
+    for name in sorted(got):
+        assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
+    assert any(want[n].any() for n in want if n.endswith("_dist"))

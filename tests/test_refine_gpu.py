@@ -353,3 +353,20 @@ def test_build_over_the_factory(pkg):
     ix = rf.build_faiss_index(x[:, :64], ids, 0.5, "IVF16,PQ8,Refine(Flat)", m, k_factor=2, niter=2)
     assert ix.base_kind == rf.BASE_IVFPQ and ix.n == 2000
     ix.close()
+
+
+def test_refined_search_answers_as_before_the_shared_core(pkg):
+    """search(q, 10, 4) of a refined ivfpq index (k_factor 4, two adds with ids) and last_candidates(), which pins
+    ivfpq_internal::search_positions, byte for byte against what the library gave before ivf_ann.hip and ivfpq_ann.hip
+    shared csrc/ivf_core.h (tests/golden/ivf_family_baseline.npz, written by make_ivf_family_baseline.py)."""
+    path = os.path.join(ROOT, "tests", "golden", "make_ivf_family_baseline.py")
+    spec = importlib.util.spec_from_file_location("make_ivf_family_baseline", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    base = np.load(os.path.join(ROOT, "tests", "golden", "ivf_family_baseline.npz"))
+    want = {n: base[n] for n in base.files if n.startswith("refine_")}
+    got = gen.refine_answers(pkg)
+    assert sorted(got) == sorted(want) and len(got) == 5 * len(gen.METRICS)
+    for name in sorted(got):
+        assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
+    assert any(want[n].any() for n in want if n.endswith("_dist"))

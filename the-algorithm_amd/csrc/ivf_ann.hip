@@ -27,7 +27,6 @@
 //     emitted then, so the k best are among the survivors whatever order the workgroups appended in.
 //   * Select sorts a query's survivors by (score desc, rank in id order asc): the order of dense_ann.hip's select.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -41,32 +40,11 @@
 #include "../../include/dense_ann.h"
 #include "../../include/ivf_ann.h"
 #include "sann_device.h"  // mix64
-#include "abi_guard.h"
-#include "ann_by_id_internal.h"
 #include "ivf_device_rows.h"
 #include "faiss_restore.h"
-#include "ivf_kernels.h"
-#include "ivf_restore.h"
-#define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
+#include "ivf_core.h"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(int code, const std::string &m) {
-  g_err = m;
-  return code;
-}
-#define ITRY(expr)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(IVF_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-// a call into dense_ann.hip: its status codes carry the same numbers, its message is in dann_last_error()
-#define DCALL(expr)                                              \
-  do {                                                           \
-    int rc_ = (expr);                                            \
-    if (rc_) return fail(rc_, std::string("coarse quantizer: ") + dann_last_error()); \
-  } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // list construction: row j of the (cell, id) order goes to its list's next slot, as an A fragment.  One wave per row.
@@ -226,32 +204,7 @@ __global__ __launch_bounds__(512) void select_kernel(const Survivor *__restrict_
                                                      int32_t *__restrict__ out_counts) {
   extern __shared__ unsigned long long keys[];
   const int q = blockIdx.x;
-  const uint32_t c = min(done_cnt[q], (uint32_t)CAP);
-  uint32_t n2 = 64;
-  while (n2 < c) n2 <<= 1;
-  for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
-    unsigned long long key = 0;
-    if (i < c) {
-      Survivor s = surv[(size_t)q * CAP + i];
-      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - lrank[s.slot]);
-    }
-    keys[i] = key;
-  }
-  __syncthreads();
-  for (uint32_t size = 2; size <= n2; size <<= 1)
-    for (uint32_t str = size >> 1; str > 0; str >>= 1) {
-      for (uint32_t i = threadIdx.x; i < n2 / 2; i += blockDim.x) {
-        uint32_t lo = 2 * i - (i & (str - 1));
-        uint32_t hi = lo + str;
-        bool desc = (lo & size) == 0;
-        unsigned long long x = keys[lo], y = keys[hi];
-        if ((x < y) == desc) {
-          keys[lo] = y;
-          keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  const uint32_t c = select_sorted(surv, done_cnt, lrank, q, keys);
   const uint32_t m = min(c, (uint32_t)k);
   for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
     float dist = 0.0f;
@@ -271,198 +224,41 @@ __global__ __launch_bounds__(512) void select_kernel(const Survivor *__restrict_
 
 }  // namespace
 
-struct ivf_index {
-  int device = 0, metric = 0, d = 0, nlist = 0;
-  int64_t n = 0;
-  int ids_mode = -1;  // -1: no add yet; 0: ids are positions; 1: ids given
-  dann_index *coarse = nullptr;
-  // the rows in the order they were added
-  Buf flat, sumsq, cell, ids;
-  // the lists
-  Buf ids_sorted, perm, cell_r, cell_sorted, ord, iota, sizes, start, nblk, boff, lf, lbias, lrank, sort_tmp, ids_tmp;
-  std::vector<int64_t> h_sizes;
-  int64_t total_blocks = 0;
-  // per-call scratch
-  Buf stage, c_dist, c_ids, c_cnt, qf, qsumsq;
-  Buf pair_cell, pair_q, pair_cell_s, pair_q_s, per_cell, pstart, ngrp, gstart, groups, rows_acc;
-  Buf tau, cnt, done_cnt, surv, flags, o_dist, o_ids, o_cnt;
-  // the last search
-  Buf probes;
-  int32_t last_nq = 0, last_nprobe = 0, last_rounds = 0;
-  int64_t last_rows = 0;
-  float t_coarse = 0, t_scan = 0, t_sel = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  RestoreState rs;  // faiss_restore.h
-  ~ivf_index() {
-    if (coarse) (void)dann_index_destroy(coarse);
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+struct ivf_index : IvfBase {
+  // the rows in the order added
+  Buf flat, sumsq;
+  // the lists' payload
+  Buf lf, lbias;
+  // per-call scratch: the queries, and the groups of a search
+  Buf qf, pstart, ngrp, gstart, groups;
 };
 
 namespace {
 
-int check_shape(int32_t metric, int32_t d, int32_t nlist) {
-  if (metric < IVF_METRIC_L2 || metric > IVF_METRIC_INNER_PRODUCT) return fail(IVF_EINVAL, "unknown metric");
-  if (d < 16 || d > MAX_D || d % 16) return fail(IVF_EINVAL, "dimension must be a multiple of 16 in 16..512");
-  if (nlist < 1 || nlist > MAX_NLIST) return fail(IVF_EINVAL, "nlist must be in 1..65536");
-  return IVF_OK;
-}
-
 int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, std::unique_ptr<ivf_index> &ix) {
   ITRY(hipSetDevice(device));
   ix.reset(new ivf_index);
-  ix->device = device;
-  ix->metric = metric;
-  ix->d = d;
-  ix->nlist = nlist;
-  ix->h_sizes.assign((size_t)nlist, 0);
-  for (auto &e : ix->ev) ITRY(hipEventCreate(&e));
-  ITRY(ix->sizes.reserve((size_t)nlist * 4));
-  ITRY(ix->start.reserve((size_t)nlist * 4));
-  ITRY(ix->nblk.reserve((size_t)nlist * 4));
-  ITRY(ix->boff.reserve((size_t)nlist * 4));
-  ITRY(hipMemset(ix->sizes.p, 0, (size_t)nlist * 4));
-  ITRY(hipMemset(ix->start.p, 0, (size_t)nlist * 4));
-  ITRY(hipMemset(ix->nblk.p, 0, (size_t)nlist * 4));
-  ITRY(hipMemset(ix->boff.p, 0, (size_t)nlist * 4));
+  if (int rc = init_base(ix.get(), device, metric, d, nlist)) return rc;
+  ITRY(hipFuncSetAttribute((const void *)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SELECT_LDS));
   return IVF_OK;
 }
 
-// host rows -> fp16 rows at flat[row0 ..) and their sums of squares, through a staging buffer; rows that are on the
-// device already (ivf_device_rows.h) are prepared where they lie
-int upload_rows(ivf_index *ix, const float *rows, bool on_device, int64_t n, Buf &flat, Buf &sumsq, int64_t row0) {
-  const int d = ix->d;
-  if (on_device) {
-    hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, 0, rows, n, d,
-                       ix->metric == IVF_METRIC_COSINE ? 1 : 0, flat.as<_Float16>() + (size_t)row0 * d, sumsq.as<float>() + row0);
-    ITRY(hipGetLastError());
-    ITRY(hipDeviceSynchronize());
-    return IVF_OK;
-  }
-  const int64_t slab = std::max<int64_t>(1, (int64_t)(64 << 20) / (d * 4));
-  ITRY(ix->stage.reserve((size_t)std::min(slab, n) * d * sizeof(float)));
-  for (int64_t r0 = 0; r0 < n; r0 += slab) {
-    const int64_t m = std::min(slab, n - r0);
-    ITRY(hipMemcpy(ix->stage.p, rows + r0 * d, (size_t)m * d * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, ix->stage.as<float>(), m, d,
-                       ix->metric == IVF_METRIC_COSINE ? 1 : 0, flat.as<_Float16>() + (size_t)(row0 + r0) * d,
-                       sumsq.as<float>() + row0 + r0);
-    ITRY(hipGetLastError());
-    ITRY(hipDeviceSynchronize());
-  }
-  return IVF_OK;
-}
-
-// stable sort of n (cell number, value) pairs by cell
-int sort_by_cell(ivf_index *ix, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out, int64_t n) {
-  size_t tb = 0;
-  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
-  ITRY(ix->sort_tmp.reserve(tb));
-  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
-  return IVF_OK;
-}
-int exclusive_sum(ivf_index *ix, const uint32_t *in, uint32_t *out, int n) {
-  size_t tb = 0;
-  ITRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, (hipStream_t)0));
-  ITRY(ix->sort_tmp.reserve(tb));
-  ITRY(hipcub::DeviceScan::ExclusiveSum(ix->sort_tmp.p, tb, in, out, n, (hipStream_t)0));
-  return IVF_OK;
-}
-
-// the nearest centroid of each of n fp16 rows (the coarse search with k = 1, CHUNK rows at a time) -> cell[0 .. n)
-int assign_rows(ivf_index *ix, dann_index *coarse, const _Float16 *flat, const float *sumsq, int64_t n, int32_t *cell) {
-  ann_by_id::DannTarget tgt;
-  DCALL(ann_by_id::dann_open(coarse, 1, false, &tgt));
-  ITRY(ix->c_dist.reserve((size_t)CHUNK * sizeof(float)));
-  ITRY(ix->c_ids.reserve((size_t)CHUNK * sizeof(int64_t)));
-  ITRY(ix->c_cnt.reserve((size_t)CHUNK * sizeof(int32_t)));
-  const int d = ix->d;
-  for (int64_t r0 = 0; r0 < n; r0 += CHUNK) {
-    const int m = (int)std::min<int64_t>(CHUNK, n - r0);
-    ann_by_id::DannChunk ch;
-    DCALL(ann_by_id::dann_chunk_open(coarse, m, 1, &ch));
-    hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)m * (d >> 3))), dim3(256), 0, 0, flat + (size_t)r0 * d,
-                       sumsq + r0, m, d, tgt.S, ch.qf, ch.qsumsq, (_Float16 *)nullptr);
-    ITRY(hipGetLastError());
-    int64_t d2h = 0;
-    DCALL(ann_by_id::dann_chunk_search_prepared(coarse, m, 1, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
-                                                ix->c_cnt.as<int32_t>(), &d2h));
-    hipLaunchKernelGGL(cells_kernel, dim3(blocks_for(m)), dim3(256), 0, 0, ix->c_ids.as<int64_t>(), m, cell + r0);
-    ITRY(hipGetLastError());
-  }
-  ITRY(hipDeviceSynchronize());
-  return IVF_OK;
-}
-
-// cells of n rows -> their order by (cell, position): ord, and per cell its size and first place in that order
-int segment_by_cell(ivf_index *ix, const uint32_t *perm, int64_t n) {
-  ITRY(ix->cell_r.reserve((size_t)n * 4));
-  ITRY(ix->cell_sorted.reserve((size_t)n * 4));
-  ITRY(ix->ord.reserve((size_t)n * 4));
-  ITRY(ix->iota.reserve((size_t)n * 4));
-  ITRY(hipMemset(ix->sizes.p, 0, (size_t)ix->nlist * 4));
-  if (n > 0) {
-    hipLaunchKernelGGL(gather_cells_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell.as<int32_t>(), perm, n,
-                       ix->cell_r.as<uint32_t>());
-    ITRY(hipGetLastError());
-    hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->iota.as<uint32_t>(), n);
-    ITRY(hipGetLastError());
-    if (int rc = sort_by_cell(ix, ix->cell_r.as<uint32_t>(), ix->cell_sorted.as<uint32_t>(), ix->iota.as<uint32_t>(),
-                              ix->ord.as<uint32_t>(), n))
-      return rc;
-    hipLaunchKernelGGL(hist_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell_r.as<uint32_t>(), n, ix->sizes.as<uint32_t>());
-    ITRY(hipGetLastError());
-  }
-  return exclusive_sum(ix, ix->sizes.as<uint32_t>(), ix->start.as<uint32_t>(), ix->nlist);
-}
-
-// all lists again from the rows in the order added: (cell, id) order, every list on a block boundary
+// all lists again from the rows in the order added: blocks of 32 rows as A fragments, beside the bias and the rank
 int layout_lists(ivf_index *ix) {
-  const int64_t n = ix->n;
-  const int d = ix->d, nlist = ix->nlist;
-  // rank in (id, position) order: ids_sorted[rank], perm[rank] = position
-  ITRY(ix->ids_sorted.reserve((size_t)n * 8));
-  ITRY(ix->perm.reserve((size_t)n * 4));
-  ITRY(ix->iota.reserve((size_t)n * 4));
-  hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->iota.as<uint32_t>(), n);
-  ITRY(hipGetLastError());
-  size_t tb = 0;
-  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const uint32_t *)nullptr,
-                                          (uint32_t *)nullptr, (int)n, 0, 64, (hipStream_t)0));
-  ITRY(ix->sort_tmp.reserve(tb));
-  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, ix->ids.as<int64_t>(), ix->ids_sorted.as<int64_t>(),
-                                          ix->iota.as<uint32_t>(), ix->perm.as<uint32_t>(), (int)n, 0, 64, (hipStream_t)0));
-  ITRY(hipDeviceSynchronize());  // (segment_by_cell may replace sort_tmp)
-  // ranks by (cell, rank)
-  if (int rc = segment_by_cell(ix, ix->perm.as<uint32_t>(), n)) return rc;
-  hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, 0, ix->sizes.as<uint32_t>(), nlist, ix->nblk.as<uint32_t>());
-  ITRY(hipGetLastError());
-  if (int rc = exclusive_sum(ix, ix->nblk.as<uint32_t>(), ix->boff.as<uint32_t>(), nlist)) return rc;
-  std::vector<uint32_t> hs((size_t)nlist);
-  ITRY(hipMemcpy(hs.data(), ix->sizes.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
-  int64_t blocks = 0;
-  for (int c = 0; c < nlist; ++c) {
-    ix->h_sizes[(size_t)c] = hs[(size_t)c];
-    blocks += (hs[(size_t)c] + 31) / 32;
-  }
-  if (blocks * 32 >= (int64_t)0xffffff00u) return fail(IVF_ELIMIT, "the lists would hold 2^32 slots or more");
-  ix->total_blocks = blocks;
-  const size_t slots = (size_t)blocks * 32;
-  ITRY(ix->lf.reserve(slots * d * sizeof(_Float16)));
-  ITRY(ix->lbias.reserve(slots * sizeof(float)));
-  ITRY(ix->lrank.reserve(slots * sizeof(uint32_t)));
-  ITRY(hipMemset(ix->lf.p, 0, slots * d * sizeof(_Float16)));
-  ITRY(hipMemset(ix->lrank.p, 0, slots * sizeof(uint32_t)));
-  hipLaunchKernelGGL(fill_kernel, dim3(blocks_for((int64_t)slots)), dim3(256), 0, 0, ix->lbias.as<float>(), (int64_t)slots, -INFINITY);
-  ITRY(hipGetLastError());
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, 0, ix->flat.as<_Float16>(), ix->sumsq.as<float>(), n, d,
-                     ix->metric, ix->cell_sorted.as<uint32_t>(), ix->ord.as<uint32_t>(), ix->perm.as<uint32_t>(),
-                     ix->start.as<uint32_t>(), ix->boff.as<uint32_t>(), ix->lf.as<_Float16>(), ix->lbias.as<float>(),
-                     ix->lrank.as<uint32_t>());
-  ITRY(hipGetLastError());
-  ITRY(hipDeviceSynchronize());
-  return IVF_OK;
+  return layout_lists(ix, 32, [ix](size_t slots) -> int {
+    const int d = ix->d;
+    ITRY(ix->lf.reserve(slots * d * sizeof(_Float16)));
+    ITRY(ix->lbias.reserve(slots * sizeof(float)));
+    ITRY(hipMemset(ix->lf.p, 0, slots * d * sizeof(_Float16)));
+    hipLaunchKernelGGL(fill_kernel, dim3(blocks_for((int64_t)slots)), dim3(256), 0, 0, ix->lbias.as<float>(), (int64_t)slots, -INFINITY);
+    ITRY(hipGetLastError());
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3(blocks_for(ix->n, 4)), dim3(256), 0, 0, ix->flat.as<_Float16>(), ix->sumsq.as<float>(),
+                       ix->n, d, ix->metric, ix->cell_sorted.as<uint32_t>(), ix->ord.as<uint32_t>(), ix->perm.as<uint32_t>(),
+                       ix->start.as<uint32_t>(), ix->boff.as<uint32_t>(), ix->lf.as<_Float16>(), ix->lbias.as<float>(),
+                       ix->lrank.as<uint32_t>());
+    ITRY(hipGetLastError());
+    return IVF_OK;
+  });
 }
 
 int build_coarse(ivf_index *ix, const float *d_cent, bool stored = false) {
@@ -476,62 +272,18 @@ int build_coarse(ivf_index *ix, const float *d_cent, bool stored = false) {
 int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
                  int64_t *out_ids, int32_t *out_counts) {
   const int d = ix->d, S = d >> 4, nlist = ix->nlist;
-  const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
-  ann_by_id::DannTarget tgt;
-  DCALL(ann_by_id::dann_open(ix->coarse, nprobe, false, &tgt));
-  ann_by_id::DannChunk ch;
-  DCALL(ann_by_id::dann_chunk_open(ix->coarse, nq, nprobe, &ch));
   const int nq_pad = (nq + 31) / 32 * 32;
-  ITRY(ix->stage.reserve((size_t)nq * d * sizeof(float)));
   ITRY(ix->qf.reserve((size_t)nq_pad * d * sizeof(_Float16) * 2));  // the fp16 rows, then the scan's fragments
-  ITRY(ix->qsumsq.reserve((size_t)nq_pad * sizeof(float)));
-  ITRY(ix->c_dist.reserve((size_t)np * sizeof(float)));
-  ITRY(ix->c_ids.reserve((size_t)np * sizeof(int64_t)));
-  ITRY(ix->c_cnt.reserve((size_t)std::max(nq, CHUNK) * sizeof(int32_t)));
-  ITRY(ix->pair_cell.reserve((size_t)np * 4));
-  ITRY(ix->pair_q.reserve((size_t)np * 4));
-  ITRY(ix->pair_cell_s.reserve((size_t)np * 4));
-  ITRY(ix->pair_q_s.reserve((size_t)np * 4));
-  ITRY(ix->per_cell.reserve((size_t)nlist * 4));
   ITRY(ix->pstart.reserve((size_t)nlist * 4));
   ITRY(ix->ngrp.reserve((size_t)nlist * 4));
   ITRY(ix->gstart.reserve((size_t)nlist * 4));
-  ITRY(ix->rows_acc.reserve(8));
-  ITRY(ix->tau.reserve((size_t)nq * 4));
-  ITRY(ix->cnt.reserve((size_t)nq * 4));
-  ITRY(ix->done_cnt.reserve((size_t)nq * 4));
-  ITRY(ix->flags.reserve(sizeof(int)));
-  ITRY(ix->surv.reserve((size_t)nq * CAP * sizeof(Survivor)));
-  ITRY(ix->o_dist.reserve((size_t)nq * k * sizeof(float)));
-  ITRY(ix->o_ids.reserve((size_t)nq * k * sizeof(int64_t)));
-  ITRY(ix->o_cnt.reserve((size_t)nq * sizeof(int32_t)));
   _Float16 *q16 = ix->qf.as<_Float16>(), *qfrag = q16 + (size_t)nq_pad * d;
+  if (int rc = probe_chunk(ix, q0, nq, queries, false, k, nprobe, q16, qfrag)) return rc;
 
-  // coarse: the nprobe nearest centroids of every query
-  ITRY(hipEventRecord(ix->ev[0], st));
-  ITRY(hipMemcpyAsync(ix->stage.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, ix->stage.as<float>(), (int64_t)nq, d,
-                     ix->metric == IVF_METRIC_COSINE ? 1 : 0, q16, ix->qsumsq.as<float>());
-  ITRY(hipGetLastError());
-  hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, q16, ix->qsumsq.as<float>(), nq, d,
-                     tgt.S, ch.qf, ch.qsumsq, qfrag);
-  ITRY(hipGetLastError());
-  int64_t d2h = 0;
-  DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, nq, nprobe, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
-                                              ix->c_cnt.as<int32_t>(), &d2h));
-
-  // inversion: (cell, query) pairs sorted by cell, cut into groups of <= 32 queries
-  ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
-  ITRY(hipMemsetAsync(ix->rows_acc.p, 0, 8, st));
-  hipLaunchKernelGGL(probes_kernel, dim3(blocks_for(np)), dim3(256), 0, st, ix->c_ids.as<int64_t>(), nq, nprobe,
-                     ix->probes.as<int32_t>() + (size_t)q0 * nprobe, ix->pair_cell.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
-                     ix->per_cell.as<uint32_t>());
-  ITRY(hipGetLastError());
-  if (int rc = sort_by_cell(ix, ix->pair_cell.as<uint32_t>(), ix->pair_cell_s.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
-                            ix->pair_q_s.as<uint32_t>(), np))
-    return rc;
-  hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), nlist, ix->ngrp.as<uint32_t>());
+  // the pairs of a cell cut into groups of <= 32 queries
+  hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), nlist, 32u,
+                     ix->ngrp.as<uint32_t>());
   ITRY(hipGetLastError());
   if (int rc = exclusive_sum(ix, ix->per_cell.as<uint32_t>(), ix->pstart.as<uint32_t>(), nlist)) return rc;
   if (int rc = exclusive_sum(ix, ix->ngrp.as<uint32_t>(), ix->gstart.as<uint32_t>(), nlist)) return rc;
@@ -544,10 +296,6 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, in
                      ix->gstart.as<uint32_t>(), ix->sizes.as<uint32_t>(), nlist, ix->groups.as<Group>(),
                      ix->rows_acc.as<unsigned long long>());
   ITRY(hipGetLastError());
-  hipLaunchKernelGGL(arm_kernel, dim3(blocks_for(nq)), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
-                     ix->done_cnt.as<uint32_t>(), nq);
-  ITRY(hipGetLastError());
-  ITRY(hipEventRecord(ix->ev[1], st));
 
   // scan rounds
   ScanArgs a;
@@ -563,46 +311,20 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, in
   a.surv = ix->surv.as<Survivor>();
   a.S = S;
   int rounds = 0;
-  for (;; ++rounds) {
-    if (ix->n > 0) {
-      hipLaunchKernelGGL(scan_kernel, dim3(n_groups), dim3(256), (size_t)S * 64 * sizeof(half8), st, a);
-      ITRY(hipGetLastError());
-    }
-    int flags = 0;
-    ITRY(hipMemsetAsync(ix->flags.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(refine_kernel, dim3(nq), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
-                       ix->done_cnt.as<uint32_t>(), ix->surv.as<Survivor>(), k, ix->flags.as<int>());
-    ITRY(hipGetLastError());
-    ITRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    ITRY(hipStreamSynchronize(st));
-    if (flags & 2) return fail(IVF_ELIMIT, "more than 8192 rows of the probed lists tie at the k-th distance of a query");
-    if (rounds >= 16) return fail(IVF_ELIMIT, "threshold refinement did not converge");
-    if (!(flags & 1)) break;
-  }
-  ITRY(hipEventRecord(ix->ev[2], st));
+  if (int rc = scan_rounds(ix, nq, k, [&](int, hipStream_t s) -> int {
+        if (ix->n > 0) {
+          hipLaunchKernelGGL(scan_kernel, dim3(n_groups), dim3(256), (size_t)S * 64 * sizeof(half8), s, a);
+          ITRY(hipGetLastError());
+        }
+        return IVF_OK;
+      }, &rounds))
+    return rc;
 
-  ITRY(hipFuncSetAttribute((const void *)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
-  hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
-                     ix->done_cnt.as<uint32_t>(), ix->qsumsq.as<float>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(),
-                     ix->metric, k, ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
+  hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(512), SELECT_LDS, st, ix->surv.as<Survivor>(), ix->done_cnt.as<uint32_t>(),
+                     ix->qsumsq.as<float>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
+                     ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
   ITRY(hipGetLastError());
-  ITRY(hipEventRecord(ix->ev[3], st));
-  ITRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-  ITRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  ITRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  unsigned long long rows = 0;
-  ITRY(hipMemcpyAsync(&rows, ix->rows_acc.p, 8, hipMemcpyDeviceToHost, st));
-  ITRY(hipStreamSynchronize(st));
-  float tc = 0, ts = 0, tl = 0;
-  (void)hipEventElapsedTime(&tc, ix->ev[0], ix->ev[1]);
-  (void)hipEventElapsedTime(&ts, ix->ev[1], ix->ev[2]);
-  (void)hipEventElapsedTime(&tl, ix->ev[2], ix->ev[3]);
-  ix->t_coarse += tc;
-  ix->t_scan += ts;
-  ix->t_sel += tl;
-  ix->last_rows += (int64_t)rows;
-  ix->last_rounds = std::max(ix->last_rounds, rounds + 1);
-  return IVF_OK;
+  return finish_chunk(ix, nq, k, rounds, out_dist, out_ids, out_counts);
 }
 
 // ivf_index_train, over host rows or over rows that are on the device
@@ -620,7 +342,7 @@ int train_rows(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t
   Buf tflat, tsumsq, picks_d, cent;
   ITRY(tflat.reserve((size_t)n_train * d * sizeof(_Float16)));
   ITRY(tsumsq.reserve((size_t)n_train * sizeof(float)));
-  if (int rc = upload_rows(ix.get(), train_vectors, on_device, n_train, tflat, tsumsq, 0)) return rc;
+  if (int rc = upload_rows(ix.get(), train_vectors, on_device, n_train, tflat.as<_Float16>(), tsumsq.as<float>())) return rc;
   // initial centroids: rows mix64(seed + t) mod n_train, t = 0, 1, ..., without repetition
   std::vector<int64_t> picks;
   picks.reserve((size_t)nlist);
@@ -643,7 +365,7 @@ int train_rows(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t
   if (int rc = build_coarse(ix.get(), cent.as<float>())) return rc;
   ITRY(ix->cell.reserve((size_t)n_train * 4));
   for (int it = 0; it < rounds; ++it) {
-    if (int rc = assign_rows(ix.get(), ix->coarse, tflat.as<_Float16>(), tsumsq.as<float>(), n_train, ix->cell.as<int32_t>())) return rc;
+    if (int rc = assign_rows(ix.get(), tflat.as<_Float16>(), tsumsq.as<float>(), n_train, ix->cell.as<int32_t>())) return rc;
     if (int rc = segment_by_cell(ix.get(), nullptr, n_train)) return rc;
     hipLaunchKernelGGL(mean_kernel, dim3(nlist), dim3(256), 0, 0, tflat.as<_Float16>(), d, metric, ix->ord.as<uint32_t>(),
                        ix->start.as<uint32_t>(), ix->sizes.as<uint32_t>(), cent.as<float>());
@@ -674,8 +396,7 @@ int ivf_internal::restore_begin(int32_t device, int32_t metric, int32_t d, int32
                                 int64_t n, ivf_index **out) try {
   if (!centroids || !out) return fail(IVF_EINVAL, "null argument");
   if (int rc = check_shape(metric, d, nlist)) return rc;
-  if (n < 0 || n >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
-  if (ids_mode < -1 || ids_mode > 1 || (n == 0) != (ids_mode == -1)) return fail(IVF_EINVAL, "ids mode does not fit the row count");
+  if (int rc = check_restore(ids_mode, n)) return rc;
   std::unique_ptr<ivf_index> ix;
   if (int rc = new_index(device, metric, d, nlist, ix)) return rc;
   Buf cent;
@@ -684,65 +405,32 @@ int ivf_internal::restore_begin(int32_t device, int32_t metric, int32_t d, int32
   if (int rc = build_coarse(ix.get(), cent.as<float>(), true)) return rc;
   ITRY(ix->flat.reserve((size_t)n * d * sizeof(_Float16)));
   ITRY(ix->sumsq.reserve((size_t)n * 4));
-  ITRY(ix->cell.reserve((size_t)n * 4));
-  ITRY(ix->ids.reserve((size_t)n * 8));
-  ix->rs.n = n;
-  ix->rs.ids_mode = ids_mode;
-  ix->rs.open = true;
+  if (int rc = restore_open(ix.get(), ids_mode, n)) return rc;
   *out = ix.release();
   return IVF_OK;
 } ABI_CATCH
 
 int ivf_internal::restore_stage(ivf_index *ix, int64_t m, int64_t **ids, int32_t **cells, uint16_t **rows16) try {
-  if (!ix || !ix->rs.open || !ids || !cells || !rows16) return fail(IVF_EINVAL, "no restore in progress");
-  if (m < 1 || m > restore_slab_rows(ix->d)) return fail(IVF_EINVAL, "slab size out of range");
-  ITRY(hipSetDevice(ix->device));
-  ITRY(ix->rs.stage(m, (size_t)ix->d * sizeof(_Float16)));
-  *ids = ix->rs.ids();
-  *cells = ix->rs.cells();
-  *rows16 = (uint16_t *)ix->rs.payload();
-  return IVF_OK;
+  return restore_staging(ix, m, ix ? restore_slab_rows(ix->d) : 0, ix ? (size_t)ix->d * sizeof(_Float16) : 0, ids, cells, (void **)rows16);
 } ABI_CATCH
 
 int ivf_internal::restore_slab(ivf_index *ix, int64_t r0, int64_t m) try {
-  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
-  RestoreState &rs = ix->rs;
-  if (m < 1 || m > rs.slab || r0 != rs.done || m > rs.n - r0) return fail(IVF_EINVAL, "slab outside the rows announced");
-  ITRY(hipSetDevice(ix->device));
-  uint32_t bad[2] = {0, 0};
-  ITRY(restore_upload(rs, r0, m, ix->nlist, ix->ids.as<int64_t>(), ix->cell.as<int32_t>(), ix->flat.p, bad));
-  if (bad[0] != 0xffffffffu)
-    return fail(IVF_EINVAL, "row " + std::to_string(bad[0]) + ": its cell is outside [0, nlist = " + std::to_string(ix->nlist) + ")");
-  if (bad[1] != 0xffffffffu)
-    return fail(IVF_EINVAL, "row " + std::to_string(bad[1]) + ": the ids of this index are positions, and its id is not its position");
+  if (int rc = restore_rows(ix, r0, m, ix ? ix->flat.p : nullptr)) return rc;
   hipLaunchKernelGGL(stored_sumsq_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, ix->flat.as<_Float16>() + (size_t)r0 * ix->d, m,
                      ix->d, ix->sumsq.as<float>() + r0);
   ITRY(hipGetLastError());
   ITRY(hipDeviceSynchronize());
-  rs.done = r0 + m;
+  ix->rs.done = r0 + m;
   return IVF_OK;
 } ABI_CATCH
 
 int ivf_internal::restore_end(ivf_index *ix) try {
-  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
-  if (ix->rs.done != ix->rs.n) return fail(IVF_EINVAL, "rows are missing");
-  ITRY(hipSetDevice(ix->device));
-  ix->n = ix->rs.n;
-  ix->ids_mode = ix->rs.ids_mode;
-  ix->rs.close();
+  if (int rc = restore_close(ix)) return rc;
   return ix->n > 0 ? layout_lists(ix) : IVF_OK;
 } ABI_CATCH
 
 int ivf_internal::export_rows(const ivf_index *ix, int64_t r0, int64_t m, int64_t *ids, int32_t *cells, uint16_t *rows16) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (r0 < 0 || m < 0 || r0 > ix->n || m > ix->n - r0) return fail(IVF_EINVAL, "rows outside the index");
-  if (m == 0) return IVF_OK;
-  ITRY(hipSetDevice(ix->device));
-  if (ids) ITRY(hipMemcpy(ids, ix->ids.as<int64_t>() + r0, (size_t)m * 8, hipMemcpyDeviceToHost));
-  if (cells) ITRY(hipMemcpy(cells, ix->cell.as<int32_t>() + r0, (size_t)m * 4, hipMemcpyDeviceToHost));
-  if (rows16)
-    ITRY(hipMemcpy(rows16, ix->flat.as<_Float16>() + (size_t)r0 * ix->d, (size_t)m * ix->d * sizeof(_Float16), hipMemcpyDeviceToHost));
-  return IVF_OK;
+  return export_columns(ix, r0, m, ids, cells, rows16, ix ? ix->flat.p : nullptr, ix ? (size_t)ix->d * sizeof(_Float16) : 0);
 } ABI_CATCH
 
 int ivf_internal::ids_mode(const ivf_index *ix) { return ix->ids_mode; }
@@ -772,107 +460,51 @@ int ivf_index_train(int32_t device, int32_t metric, int32_t d, int32_t nlist, in
 int ivf_index_add(ivf_index_t *ix, int64_t n, const float *vectors, const int64_t *ids) try {
   if (!ix) return fail(IVF_EINVAL, "null index");
   if (n < 0) return fail(IVF_EINVAL, "n must not be negative");
-  if (ix->ids_mode == 1 && !ids) return fail(IVF_EINVAL, "the index holds rows added with ids: an add must give ids");
-  if (ix->ids_mode == 0 && ids) return fail(IVF_EINVAL, "the index holds rows added without ids (its ids are positions): ids must be NULL");
+  if (int rc = check_ids_rule(ix, ids != nullptr)) return rc;
   if (n == 0) return IVF_OK;
   if (!vectors) return fail(IVF_EINVAL, "null vectors");
+  if (int rc = grow_rows(ix, n)) return rc;
   const int64_t n_old = ix->n, total = n_old + n;
-  if (total >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
-  ITRY(hipSetDevice(ix->device));
   const int d = ix->d;
   ITRY(ix->flat.grow_keep((size_t)n_old * d * sizeof(_Float16), (size_t)total * d * sizeof(_Float16)));
   ITRY(ix->sumsq.grow_keep((size_t)n_old * 4, (size_t)total * 4));
-  ITRY(ix->cell.grow_keep((size_t)n_old * 4, (size_t)total * 4));
-  ITRY(ix->ids.grow_keep((size_t)n_old * 8, (size_t)total * 8));
-  if (int rc = upload_rows(ix, vectors, false, n, ix->flat, ix->sumsq, n_old)) return rc;
-  if (ids) {
-    ITRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
-  } else {
-    hipLaunchKernelGGL(iota64_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->ids.as<int64_t>() + n_old, n_old, n);
-    ITRY(hipGetLastError());
-  }
-  if (int rc = assign_rows(ix, ix->coarse, ix->flat.as<_Float16>() + (size_t)n_old * d, ix->sumsq.as<float>() + n_old, n,
-                           ix->cell.as<int32_t>() + n_old))
-    return rc;
-  ix->n = total;
-  ix->ids_mode = ids ? 1 : 0;
+  _Float16 *flat = ix->flat.as<_Float16>() + (size_t)n_old * d;
+  float *sumsq = ix->sumsq.as<float>() + n_old;
+  if (int rc = upload_rows(ix, vectors, false, n, flat, sumsq)) return rc;
+  if (int rc = assign_rows(ix, flat, sumsq, n, ix->cell.as<int32_t>() + n_old)) return rc;
+  if (int rc = commit_add(ix, n, ids)) return rc;
   return layout_lists(ix);
 } ABI_CATCH
 
 int ivf_search(ivf_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist, int64_t *out_ids,
                int32_t *out_counts) try {
   if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
-  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
-  if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
-  if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
-  nprobe = std::min(nprobe, ix->nlist);
-  ITRY(hipSetDevice(ix->device));
-  ITRY(ix->probes.reserve((size_t)nq * nprobe * sizeof(int32_t)));
-  ix->last_nq = 0;
-  ix->last_nprobe = nprobe;
-  ix->last_rows = 0;
-  ix->last_rounds = 0;
-  ix->t_coarse = ix->t_scan = ix->t_sel = 0;
-  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
-    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
-    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, k, nprobe, out_dist + (size_t)q0 * k,
-                              out_ids + (size_t)q0 * k, out_counts + q0))
-      return rc;
-  }
-  ix->last_nq = nq;
-  return IVF_OK;
+  if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
+  return search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
+    return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, k, nprobe, out_dist + (size_t)q0 * k, out_ids + (size_t)q0 * k,
+                        out_counts + q0);
+  });
 } ABI_CATCH
 
 int ivf_index_info(const ivf_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (n) *n = ix->n;
-  if (d) *d = ix->d;
-  if (metric) *metric = ix->metric;
-  if (nlist) *nlist = ix->nlist;
-  return IVF_OK;
+  return index_info(ix, n, d, metric, nlist);
 } ABI_CATCH
 
-int ivf_index_get_centroids(const ivf_index_t *ix, float *out) try {
-  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
-  DCALL(dann_index_get_vectors(ix->coarse, 0, ix->nlist, out));
-  return IVF_OK;
-} ABI_CATCH
+int ivf_index_get_centroids(const ivf_index_t *ix, float *out) try { return get_centroids(ix, out); } ABI_CATCH
 
-int ivf_index_list_sizes(const ivf_index_t *ix, int64_t *out) try {
-  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
-  std::copy(ix->h_sizes.begin(), ix->h_sizes.end(), out);
-  return IVF_OK;
-} ABI_CATCH
+int ivf_index_list_sizes(const ivf_index_t *ix, int64_t *out) try { return list_sizes(ix, out); } ABI_CATCH
 
 int ivf_index_get_assignment(const ivf_index_t *ix, int64_t *out_ids, int32_t *out_cells) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (ix->n == 0) return IVF_OK;
-  ITRY(hipSetDevice(ix->device));
-  if (out_ids) ITRY(hipMemcpy(out_ids, ix->ids.p, (size_t)ix->n * 8, hipMemcpyDeviceToHost));
-  if (out_cells) ITRY(hipMemcpy(out_cells, ix->cell.p, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
-  return IVF_OK;
+  return get_assignment(ix, out_ids, out_cells);
 } ABI_CATCH
 
 int ivf_last_probes(const ivf_index_t *ix, int32_t *nq, int32_t *nprobe, int32_t *out_cells) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (nq) *nq = ix->last_nq;
-  if (nprobe) *nprobe = ix->last_nprobe;
-  if (out_cells && ix->last_nq > 0) {
-    ITRY(hipSetDevice(ix->device));
-    ITRY(hipMemcpy(out_cells, ix->probes.p, (size_t)ix->last_nq * ix->last_nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  return IVF_OK;
+  return last_probes(ix, nq, nprobe, out_cells);
 } ABI_CATCH
 
 int ivf_last_stats(const ivf_index_t *ix, int64_t *rows_scanned, int32_t *rounds, float *coarse_ms, float *scan_ms,
                    float *select_ms) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (rows_scanned) *rows_scanned = ix->last_rows;
-  if (rounds) *rounds = ix->last_rounds;
-  if (coarse_ms) *coarse_ms = ix->t_coarse;
-  if (scan_ms) *scan_ms = ix->t_scan;
-  if (select_ms) *select_ms = ix->t_sel;
-  return IVF_OK;
+  return last_stats(ix, rows_scanned, rounds, coarse_ms, scan_ms, select_ms);
 } ABI_CATCH
 
 int ivf_index_destroy(ivf_index_t *ix) try {

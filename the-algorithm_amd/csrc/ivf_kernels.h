@@ -1,7 +1,8 @@
-// ivf_kernels.h -- what the two inverted-file indexes (ivf_ann.hip: flat lists; ivfpq_ann.hip: product-quantised lists)
-// share: row preparation, the small bookkeeping kernels of list construction and probe inversion, the survivor buffer's
-// arm / refine kernels with wg_kth_largest, and the device buffer Buf.  Moved here verbatim from ivf_ann.hip; a source
-// includes this once, after its hip_runtime / ivf_ann.h / sann_device.h includes.  Everything is file-local.
+// ivf_kernels.h -- the device side that the two inverted-file indexes (ivf_ann.hip: flat lists; ivfpq_ann.hip:
+// product-quantised lists) share: row preparation, the small bookkeeping kernels of list construction and probe inversion,
+// the survivor buffer's arm / refine kernels with wg_kth_largest, and the device buffer Buf.  The host code that launches
+// them is ivf_core.h, which includes this; opq_ann.hip and refine_ann.hip use the row preparation.  A source includes this
+// once.  Everything is file-local.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -110,9 +111,10 @@ __global__ void hist_kernel(const uint32_t *__restrict__ keys, int64_t n, uint32
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) atomicAdd(&hist[keys[i]], 1u);
 }
-__global__ void blocks_of_kernel(const uint32_t *__restrict__ sizes, int n, uint32_t *__restrict__ nblk) {
+// the blocks of `per` entries that each of n sizes fills
+__global__ void blocks_of_kernel(const uint32_t *__restrict__ sizes, int n, uint32_t per, uint32_t *__restrict__ nblk) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) nblk[i] = (sizes[i] + 31u) >> 5;
+  if (i < n) nblk[i] = (sizes[i] + per - 1u) / per;
 }
 
 __global__ void fill_kernel(float *__restrict__ p, int64_t n, float v) {

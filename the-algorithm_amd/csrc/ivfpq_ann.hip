@@ -25,7 +25,6 @@
 //     rounds.
 //   * Select sorts a query's survivors by (score desc, rank in id order asc), as ivf_ann.hip's select does.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -42,32 +41,11 @@
 #include "../../include/ivfpq_ann.h"
 #include "../../include/polysemous_ann.h"
 #include "sann_device.h"  // mix64
-#include "abi_guard.h"
-#include "ann_by_id_internal.h"
 #include "ivf_device_rows.h"
 #include "faiss_restore.h"
-#include "ivf_kernels.h"
-#include "ivf_restore.h"
-#define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
+#include "ivf_core.h"
 
 namespace {
-
-thread_local std::string g_err;
-int fail(int code, const std::string &m) {
-  g_err = m;
-  return code;
-}
-#define ITRY(expr)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(IVF_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-// a call into dense_ann.hip: its status codes carry the same numbers, its message is in dann_last_error()
-#define DCALL(expr)                                              \
-  do {                                                           \
-    int rc_ = (expr);                                            \
-    if (rc_) return fail(rc_, std::string("coarse quantizer: ") + dann_last_error()); \
-  } while (0)
 
 constexpr int KSUB = 256;    // codewords per sub-quantizer
 constexpr int MAX_M = 64;
@@ -204,10 +182,6 @@ __global__ void scatter_codes_kernel(const uint32_t *__restrict__ codes4 /*[n][M
   const int r = (int)(slot % LBLOCK);
   lc[(blk * M4 + g) * LBLOCK + r] = codes4[(size_t)src * M4 + g];
   if (g == 0) lrank[slot] = rank;
-}
-__global__ void blocks64_of_kernel(const uint32_t *__restrict__ sizes, int n, uint32_t *__restrict__ nblk) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) nblk[i] = (sizes[i] + (uint32_t)LBLOCK - 1u) / (uint32_t)LBLOCK;
 }
 // one thread per cell: its share of the rows scanned (integers: any order gives the sum)
 __global__ void rows_scanned_kernel(const uint32_t *__restrict__ per_cell, const uint32_t *__restrict__ sizes, int nlist,
@@ -430,32 +404,7 @@ __global__ __launch_bounds__(512) void pq_select_kernel(const Survivor *__restri
                                                         uint32_t *__restrict__ out_rank) {
   extern __shared__ unsigned long long keys[];
   const int q = blockIdx.x;
-  const uint32_t c = min(done_cnt[q], (uint32_t)CAP);
-  uint32_t n2 = 64;
-  while (n2 < c) n2 <<= 1;
-  for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) {
-    unsigned long long key = 0;
-    if (i < c) {
-      Survivor s = surv[(size_t)q * CAP + i];
-      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - lrank[s.slot]);
-    }
-    keys[i] = key;
-  }
-  __syncthreads();
-  for (uint32_t size = 2; size <= n2; size <<= 1)
-    for (uint32_t str = size >> 1; str > 0; str >>= 1) {
-      for (uint32_t i = threadIdx.x; i < n2 / 2; i += blockDim.x) {
-        uint32_t lo = 2 * i - (i & (str - 1));
-        uint32_t hi = lo + str;
-        bool desc = (lo & size) == 0;
-        unsigned long long x = keys[lo], y = keys[hi];
-        if ((x < y) == desc) {
-          keys[lo] = y;
-          keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  const uint32_t c = select_sorted(surv, done_cnt, lrank, q, keys);
   const uint32_t m = min(c, (uint32_t)k);
   if constexpr (POSITIONS) {
     for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
@@ -495,47 +444,26 @@ struct PosOut {
 
 }  // namespace
 
-struct ivfpq_index {
-  int device = 0, metric = 0, d = 0, nlist = 0, M = 0, dsub = 0;
-  int64_t n = 0;
-  int ids_mode = -1;  // -1: no add yet; 0: ids are positions; 1: ids given
-  dann_index *coarse = nullptr;
+struct ivfpq_index : IvfBase {
+  int M = 0, dsub = 0;
   Buf cent, cb;  // centroids fp32 [nlist][d] (the stored fp16 values), codebooks fp32 [M][256][dsub]
   // per row, in the order added
-  Buf codes, cell, ids;
-  // the lists
-  Buf ids_sorted, perm, cell_r, cell_sorted, ord, iota, sizes, start, nblk, boff, lc, lrank, sort_tmp;
-  std::vector<int64_t> h_sizes;
-  int64_t total_blocks = 0;
-  // per-call scratch
-  Buf stage, flat, sumsq, c_dist, c_ids, c_cnt, q16, qsumsq;
-  Buf pair_cell, pair_q, pair_cell_s, pair_q_s, per_cell, rows_acc;
-  Buf tau, cnt, done_cnt, surv, flags, o_dist, o_ids, o_cnt;
-  // the last search
-  Buf probes;
-  int32_t last_nq = 0, last_nprobe = 0, last_rounds = 0;
-  int64_t last_rows = 0;
-  float t_coarse = 0, t_scan = 0, t_sel = 0;
+  Buf codes;
+  // the lists' payload
+  Buf lc;
+  // per-call scratch: a slab of prepared rows, the prepared queries
+  Buf flat, sumsq, q16;
   // polysemous_ann.h: the flag of the training, and the last search with ht > 0
   bool polysemous = false;
   Buf qcodes, scored_acc;
   int32_t qc_nq = 0, qc_nprobe = 0;
   int64_t last_scored = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  RestoreState rs;  // faiss_restore.h
-  ~ivfpq_index() {
-    if (coarse) (void)dann_index_destroy(coarse);
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
 };
 
 namespace {
 
 int check_shape(int32_t metric, int32_t d, int32_t nlist, int32_t M) {
-  if (metric < IVF_METRIC_L2 || metric > IVF_METRIC_INNER_PRODUCT) return fail(IVF_EINVAL, "unknown metric");
-  if (d < 16 || d > MAX_D || d % 16) return fail(IVF_EINVAL, "dimension must be a multiple of 16 in 16..512");
-  if (nlist < 1 || nlist > MAX_NLIST) return fail(IVF_EINVAL, "nlist must be in 1..65536");
+  if (int rc = check_shape(metric, d, nlist)) return rc;
   if (M < 4 || M > MAX_M || M % 4) return fail(IVF_EINVAL, "M must be a multiple of 4 in 4..64");
   if (d % M) return fail(IVF_EINVAL, "M must divide the dimension");
   return IVF_OK;
@@ -548,26 +476,17 @@ size_t adc_ht_lds_bytes(int M, int d) { return adc_lds_bytes(M, d) + (size_t)M; 
 int new_index(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, std::unique_ptr<ivfpq_index> &ix) {
   ITRY(hipSetDevice(device));
   ix.reset(new ivfpq_index);
-  ix->device = device;
-  ix->metric = metric;
-  ix->d = d;
-  ix->nlist = nlist;
+  if (int rc = init_base(ix.get(), device, metric, d, nlist)) return rc;
   ix->M = M;
   ix->dsub = d / M;
-  ix->h_sizes.assign((size_t)nlist, 0);
-  for (auto &e : ix->ev) ITRY(hipEventCreate(&e));
-  for (Buf *b : {&ix->sizes, &ix->start, &ix->nblk, &ix->boff}) {
-    ITRY(b->reserve((size_t)nlist * 4));
-    ITRY(hipMemset(b->p, 0, (size_t)nlist * 4));
-  }
   ITRY(ix->cent.reserve((size_t)nlist * d * sizeof(float)));
   ITRY(ix->cb.reserve((size_t)M * KSUB * ix->dsub * sizeof(float)));
   // both kernels size their LDS by the shape: up to 64 KiB (encoder, dsub = 128) and 66 KiB (scan, M = 64, d = 512)
   ITRY(hipFuncSetAttribute((const void *)encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)encode_lds_bytes(MAX_D / 4)));
   ITRY(hipFuncSetAttribute((const void *)adc_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)adc_lds_bytes(MAX_M, MAX_D)));
   ITRY(hipFuncSetAttribute((const void *)adc_scan_ht_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)adc_ht_lds_bytes(MAX_M, MAX_D)));
-  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
-  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * sizeof(unsigned long long)));
+  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SELECT_LDS));
+  ITRY(hipFuncSetAttribute((const void *)pq_select_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SELECT_LDS));
   return IVF_OK;
 }
 
@@ -585,47 +504,6 @@ int set_centroids(ivfpq_index *ix, const float *centroids) {
   return IVF_OK;
 }
 
-// stable sort of n (cell number, value) pairs by cell
-int sort_by_cell(ivfpq_index *ix, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out, int64_t n) {
-  size_t tb = 0;
-  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
-  ITRY(ix->sort_tmp.reserve(tb));
-  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
-  return IVF_OK;
-}
-int exclusive_sum(ivfpq_index *ix, const uint32_t *in, uint32_t *out, int n) {
-  size_t tb = 0;
-  ITRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, (hipStream_t)0));
-  ITRY(ix->sort_tmp.reserve(tb));
-  ITRY(hipcub::DeviceScan::ExclusiveSum(ix->sort_tmp.p, tb, in, out, n, (hipStream_t)0));
-  return IVF_OK;
-}
-
-// the nearest centroid of each of n fp16 rows (the coarse search with k = 1, CHUNK rows at a time) -> cell[0 .. n)
-int assign_rows(ivfpq_index *ix, const _Float16 *flat, const float *sumsq, int64_t n, int32_t *cell) {
-  ann_by_id::DannTarget tgt;
-  DCALL(ann_by_id::dann_open(ix->coarse, 1, false, &tgt));
-  ITRY(ix->c_dist.reserve((size_t)CHUNK * sizeof(float)));
-  ITRY(ix->c_ids.reserve((size_t)CHUNK * sizeof(int64_t)));
-  ITRY(ix->c_cnt.reserve((size_t)CHUNK * sizeof(int32_t)));
-  const int d = ix->d;
-  for (int64_t r0 = 0; r0 < n; r0 += CHUNK) {
-    const int m = (int)std::min<int64_t>(CHUNK, n - r0);
-    ann_by_id::DannChunk ch;
-    DCALL(ann_by_id::dann_chunk_open(ix->coarse, m, 1, &ch));
-    hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)m * (d >> 3))), dim3(256), 0, 0, flat + (size_t)r0 * d,
-                       sumsq + r0, m, d, tgt.S, ch.qf, ch.qsumsq, (_Float16 *)nullptr);
-    ITRY(hipGetLastError());
-    int64_t d2h = 0;
-    DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, m, 1, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
-                                                ix->c_cnt.as<int32_t>(), &d2h));
-    hipLaunchKernelGGL(cells_kernel, dim3(blocks_for(m)), dim3(256), 0, 0, ix->c_ids.as<int64_t>(), m, cell + r0);
-    ITRY(hipGetLastError());
-  }
-  ITRY(hipDeviceSynchronize());
-  return IVF_OK;
-}
-
 int encode_rows(ivfpq_index *ix, const _Float16 *flat, const int32_t *cell, int64_t n, uint8_t *codes, int64_t row_stride,
                 int64_t m_stride) {
   if (n == 0) return IVF_OK;
@@ -635,77 +513,20 @@ int encode_rows(ivfpq_index *ix, const _Float16 *flat, const int32_t *cell, int6
   return IVF_OK;
 }
 
-// m device rows -> fp16 rows and their sums of squares at row `at` of `flat` / `sumsq`
-int prepare_slab(ivfpq_index *ix, const float *d_rows, int64_t m, Buf &flat, Buf &sumsq, int64_t at) {
-  const int d = ix->d;
-  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(m, 4)), dim3(256), 0, 0, d_rows, m, d,
-                     ix->metric == IVF_METRIC_COSINE ? 1 : 0, flat.as<_Float16>() + (size_t)at * d, sumsq.as<float>() + at);
-  ITRY(hipGetLastError());
-  ITRY(hipDeviceSynchronize());
-  return IVF_OK;
-}
 using ivfpq_internal::slab_rows;
-// host rows -> the staging buffer of the index
-int stage_rows(ivfpq_index *ix, const float *rows, int64_t m) {
-  ITRY(ix->stage.reserve((size_t)m * ix->d * sizeof(float)));
-  ITRY(hipMemcpy(ix->stage.p, rows, (size_t)m * ix->d * sizeof(float), hipMemcpyHostToDevice));
-  return IVF_OK;
-}
 
-// all lists again from the codes in the order added: (cell, id) order, every list on a block boundary
+// all lists again from the codes in the order added: blocks of LBLOCK rows, [M / 4][LBLOCK] dwords each, beside the rank
 int layout_lists(ivfpq_index *ix) {
-  const int64_t n = ix->n;
-  const int nlist = ix->nlist, M4 = ix->M >> 2;
-  // rank in (id, position) order: ids_sorted[rank], perm[rank] = position
-  ITRY(ix->ids_sorted.reserve((size_t)n * 8));
-  ITRY(ix->perm.reserve((size_t)n * 4));
-  ITRY(ix->iota.reserve((size_t)n * 4));
-  hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->iota.as<uint32_t>(), n);
-  ITRY(hipGetLastError());
-  size_t tb = 0;
-  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const int64_t *)nullptr, (int64_t *)nullptr, (const uint32_t *)nullptr,
-                                          (uint32_t *)nullptr, (int)n, 0, 64, (hipStream_t)0));
-  ITRY(ix->sort_tmp.reserve(tb));
-  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, ix->ids.as<int64_t>(), ix->ids_sorted.as<int64_t>(),
-                                          ix->iota.as<uint32_t>(), ix->perm.as<uint32_t>(), (int)n, 0, 64, (hipStream_t)0));
-  ITRY(hipDeviceSynchronize());  // (the sorts below may replace sort_tmp)
-  // ranks by (cell, rank)
-  ITRY(ix->cell_r.reserve((size_t)n * 4));
-  ITRY(ix->cell_sorted.reserve((size_t)n * 4));
-  ITRY(ix->ord.reserve((size_t)n * 4));
-  ITRY(hipMemset(ix->sizes.p, 0, (size_t)nlist * 4));
-  hipLaunchKernelGGL(gather_cells_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell.as<int32_t>(), ix->perm.as<uint32_t>(), n,
-                     ix->cell_r.as<uint32_t>());
-  ITRY(hipGetLastError());
-  if (int rc = sort_by_cell(ix, ix->cell_r.as<uint32_t>(), ix->cell_sorted.as<uint32_t>(), ix->iota.as<uint32_t>(),
-                            ix->ord.as<uint32_t>(), n))
-    return rc;
-  hipLaunchKernelGGL(hist_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->cell_r.as<uint32_t>(), n, ix->sizes.as<uint32_t>());
-  ITRY(hipGetLastError());
-  if (int rc = exclusive_sum(ix, ix->sizes.as<uint32_t>(), ix->start.as<uint32_t>(), nlist)) return rc;
-  hipLaunchKernelGGL(blocks64_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, 0, ix->sizes.as<uint32_t>(), nlist, ix->nblk.as<uint32_t>());
-  ITRY(hipGetLastError());
-  if (int rc = exclusive_sum(ix, ix->nblk.as<uint32_t>(), ix->boff.as<uint32_t>(), nlist)) return rc;
-  std::vector<uint32_t> hs((size_t)nlist);
-  ITRY(hipMemcpy(hs.data(), ix->sizes.p, (size_t)nlist * 4, hipMemcpyDeviceToHost));
-  int64_t blocks = 0;
-  for (int c = 0; c < nlist; ++c) {
-    ix->h_sizes[(size_t)c] = hs[(size_t)c];
-    blocks += (hs[(size_t)c] + LBLOCK - 1) / LBLOCK;
-  }
-  if (blocks * LBLOCK >= (int64_t)0xffffff00u) return fail(IVF_ELIMIT, "the lists would hold 2^32 slots or more");
-  ix->total_blocks = blocks;
-  const size_t slots = (size_t)blocks * LBLOCK;
-  ITRY(ix->lc.reserve(slots * M4 * sizeof(uint32_t)));
-  ITRY(ix->lrank.reserve(slots * sizeof(uint32_t)));
-  ITRY(hipMemset(ix->lc.p, 0, slots * M4 * sizeof(uint32_t)));
-  ITRY(hipMemset(ix->lrank.p, 0, slots * sizeof(uint32_t)));
-  hipLaunchKernelGGL(scatter_codes_kernel, dim3(blocks_for(n * M4)), dim3(256), 0, 0, ix->codes.as<uint32_t>(), n, M4,
-                     ix->cell_sorted.as<uint32_t>(), ix->ord.as<uint32_t>(), ix->perm.as<uint32_t>(), ix->start.as<uint32_t>(),
-                     ix->boff.as<uint32_t>(), ix->lc.as<uint32_t>(), ix->lrank.as<uint32_t>());
-  ITRY(hipGetLastError());
-  ITRY(hipDeviceSynchronize());
-  return IVF_OK;
+  return layout_lists(ix, LBLOCK, [ix](size_t slots) -> int {
+    const int M4 = ix->M >> 2;
+    ITRY(ix->lc.reserve(slots * M4 * sizeof(uint32_t)));
+    ITRY(hipMemset(ix->lc.p, 0, slots * M4 * sizeof(uint32_t)));
+    hipLaunchKernelGGL(scatter_codes_kernel, dim3(blocks_for(ix->n * M4)), dim3(256), 0, 0, ix->codes.as<uint32_t>(), ix->n, M4,
+                       ix->cell_sorted.as<uint32_t>(), ix->ord.as<uint32_t>(), ix->perm.as<uint32_t>(), ix->start.as<uint32_t>(),
+                       ix->boff.as<uint32_t>(), ix->lc.as<uint32_t>(), ix->lrank.as<uint32_t>());
+    ITRY(hipGetLastError());
+    return IVF_OK;
+  });
 }
 
 // the rows whose residuals are the initial codewords: picks[m][j], by the rule of ivfpq_ann.h
@@ -751,61 +572,12 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
   const int d = ix->d, nlist = ix->nlist;
   const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
-  ann_by_id::DannTarget tgt;
-  DCALL(ann_by_id::dann_open(ix->coarse, nprobe, false, &tgt));
-  ann_by_id::DannChunk ch;
-  DCALL(ann_by_id::dann_chunk_open(ix->coarse, nq, nprobe, &ch));
-  if (!on_device) ITRY(ix->stage.reserve((size_t)nq * d * sizeof(float)));
   ITRY(ix->q16.reserve((size_t)nq * d * sizeof(_Float16)));
-  ITRY(ix->qsumsq.reserve((size_t)nq * sizeof(float)));
-  ITRY(ix->c_dist.reserve((size_t)np * sizeof(float)));
-  ITRY(ix->c_ids.reserve((size_t)np * sizeof(int64_t)));
-  ITRY(ix->c_cnt.reserve((size_t)std::max(nq, CHUNK) * sizeof(int32_t)));
-  ITRY(ix->pair_cell.reserve((size_t)np * 4));
-  ITRY(ix->pair_q.reserve((size_t)np * 4));
-  ITRY(ix->pair_cell_s.reserve((size_t)np * 4));
-  ITRY(ix->pair_q_s.reserve((size_t)np * 4));
-  ITRY(ix->per_cell.reserve((size_t)nlist * 4));
-  ITRY(ix->rows_acc.reserve(8));
-  ITRY(ix->tau.reserve((size_t)nq * 4));
-  ITRY(ix->cnt.reserve((size_t)nq * 4));
-  ITRY(ix->done_cnt.reserve((size_t)nq * 4));
-  ITRY(ix->flags.reserve(sizeof(int)));
-  ITRY(ix->surv.reserve((size_t)nq * CAP * sizeof(Survivor)));
-  ITRY(ix->o_dist.reserve((size_t)nq * k * sizeof(float)));
-  ITRY(ix->o_ids.reserve((size_t)nq * k * sizeof(int64_t)));
-  ITRY(ix->o_cnt.reserve((size_t)nq * sizeof(int32_t)));
-
-  // coarse: the nprobe nearest centroids of every query
-  ITRY(hipEventRecord(ix->ev[0], st));
-  if (!on_device) ITRY(hipMemcpyAsync(ix->stage.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, on_device ? queries : ix->stage.as<float>(), (int64_t)nq, d,
-                     ix->metric == IVF_METRIC_COSINE ? 1 : 0, ix->q16.as<_Float16>(), ix->qsumsq.as<float>());
-  ITRY(hipGetLastError());
-  hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, ix->q16.as<_Float16>(),
-                     ix->qsumsq.as<float>(), nq, d, tgt.S, ch.qf, ch.qsumsq, (_Float16 *)nullptr);
-  ITRY(hipGetLastError());
-  int64_t d2h = 0;
-  DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, nq, nprobe, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
-                                              ix->c_cnt.as<int32_t>(), &d2h));
-
-  // inversion: (cell, query) pairs sorted by cell, one workgroup each
-  ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
-  ITRY(hipMemsetAsync(ix->rows_acc.p, 0, 8, st));
-  hipLaunchKernelGGL(probes_kernel, dim3(blocks_for(np)), dim3(256), 0, st, ix->c_ids.as<int64_t>(), nq, nprobe,
-                     ix->probes.as<int32_t>() + (size_t)q0 * nprobe, ix->pair_cell.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
-                     ix->per_cell.as<uint32_t>());
-  ITRY(hipGetLastError());
-  if (int rc = sort_by_cell(ix, ix->pair_cell.as<uint32_t>(), ix->pair_cell_s.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
-                            ix->pair_q_s.as<uint32_t>(), np))
-    return rc;
+  if (int rc = probe_chunk(ix, q0, nq, queries, on_device, k, nprobe, ix->q16.as<_Float16>(), nullptr)) return rc;
+  // one workgroup per pair
   hipLaunchKernelGGL(rows_scanned_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(),
                      ix->sizes.as<uint32_t>(), nlist, ix->rows_acc.as<unsigned long long>());
   ITRY(hipGetLastError());
-  hipLaunchKernelGGL(arm_kernel, dim3(blocks_for(nq)), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
-                     ix->done_cnt.as<uint32_t>(), nq);
-  ITRY(hipGetLastError());
-  ITRY(hipEventRecord(ix->ev[1], st));
 
   // scan rounds
   AdcArgs a;
@@ -832,59 +604,32 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
     h.ht = ht;
   }
   int rounds = 0;
-  for (;; ++rounds) {
-    if (ht > 0) {
-      h.scored = rounds == 0 ? ix->scored_acc.as<unsigned long long>() : nullptr;
-      hipLaunchKernelGGL(adc_scan_ht_kernel, dim3((unsigned)np), dim3(256), adc_ht_lds_bytes(ix->M, d), st, a, h);
-      ITRY(hipGetLastError());
-    } else if (ix->n > 0) {
-      hipLaunchKernelGGL(adc_scan_kernel, dim3((unsigned)np), dim3(256), adc_lds_bytes(ix->M, d), st, a);
-      ITRY(hipGetLastError());
-    }
-    int flags = 0;
-    ITRY(hipMemsetAsync(ix->flags.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(refine_kernel, dim3(nq), dim3(256), 0, st, ix->tau.as<float>(), ix->cnt.as<uint32_t>(),
-                       ix->done_cnt.as<uint32_t>(), ix->surv.as<Survivor>(), k, ix->flags.as<int>());
-    ITRY(hipGetLastError());
-    ITRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    ITRY(hipStreamSynchronize(st));
-    if (flags & 2) return fail(IVF_ELIMIT, "more than 8192 rows of the probed lists tie at the k-th distance of a query");
-    if (rounds >= 16) return fail(IVF_ELIMIT, "threshold refinement did not converge");
-    if (!(flags & 1)) break;
-  }
-  ITRY(hipEventRecord(ix->ev[2], st));
+  if (int rc = scan_rounds(ix, nq, k, [&](int round, hipStream_t s) -> int {
+        if (ht > 0) {
+          h.scored = round == 0 ? ix->scored_acc.as<unsigned long long>() : nullptr;
+          hipLaunchKernelGGL(adc_scan_ht_kernel, dim3((unsigned)np), dim3(256), adc_ht_lds_bytes(ix->M, d), s, a, h);
+          ITRY(hipGetLastError());
+        } else if (ix->n > 0) {
+          hipLaunchKernelGGL(adc_scan_kernel, dim3((unsigned)np), dim3(256), adc_lds_bytes(ix->M, d), s, a);
+          ITRY(hipGetLastError());
+        }
+        return IVF_OK;
+      }, &rounds))
+    return rc;
 
   if (po) {
-    hipLaunchKernelGGL(pq_select_kernel<true>, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
+    hipLaunchKernelGGL(pq_select_kernel<true>, dim3(nq), dim3(512), SELECT_LDS, st, ix->surv.as<Survivor>(),
                        ix->done_cnt.as<uint32_t>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
                        (float *)nullptr, (int64_t *)nullptr, po->cnt + q0, ix->perm.as<uint32_t>(), po->pos + (size_t)q0 * k,
                        po->rank + (size_t)q0 * k);
-    ITRY(hipGetLastError());
-    ITRY(hipEventRecord(ix->ev[3], st));
   } else {
-    hipLaunchKernelGGL(pq_select_kernel<false>, dim3(nq), dim3(512), CAP * sizeof(unsigned long long), st, ix->surv.as<Survivor>(),
+    hipLaunchKernelGGL(pq_select_kernel<false>, dim3(nq), dim3(512), SELECT_LDS, st, ix->surv.as<Survivor>(),
                        ix->done_cnt.as<uint32_t>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
                        ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>(), (const uint32_t *)nullptr,
                        (int32_t *)nullptr, (uint32_t *)nullptr);
-    ITRY(hipGetLastError());
-    ITRY(hipEventRecord(ix->ev[3], st));
-    ITRY(hipMemcpyAsync(out_dist, ix->o_dist.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-    ITRY(hipMemcpyAsync(out_ids, ix->o_ids.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    ITRY(hipMemcpyAsync(out_counts, ix->o_cnt.p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   }
-  unsigned long long rows = 0;
-  ITRY(hipMemcpyAsync(&rows, ix->rows_acc.p, 8, hipMemcpyDeviceToHost, st));
-  ITRY(hipStreamSynchronize(st));
-  float tc = 0, ts = 0, tl = 0;
-  (void)hipEventElapsedTime(&tc, ix->ev[0], ix->ev[1]);
-  (void)hipEventElapsedTime(&ts, ix->ev[1], ix->ev[2]);
-  (void)hipEventElapsedTime(&tl, ix->ev[2], ix->ev[3]);
-  ix->t_coarse += tc;
-  ix->t_scan += ts;
-  ix->t_sel += tl;
-  ix->last_rows += (int64_t)rows;
-  ix->last_rounds = std::max(ix->last_rounds, rounds + 1);
-  return IVF_OK;
+  ITRY(hipGetLastError());
+  return finish_chunk(ix, nq, k, rounds, po ? nullptr : out_dist, out_ids, out_counts);
 }
 
 // ivfpq_index_train, over host rows or over rows that are on the device
@@ -915,16 +660,7 @@ int train_rows(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t
   Buf tflat, tsumsq;
   ITRY(tflat.reserve((size_t)n_train * d * sizeof(_Float16)));
   ITRY(tsumsq.reserve((size_t)n_train * sizeof(float)));
-  const int64_t slab = slab_rows(d);
-  for (int64_t r0 = 0; r0 < n_train; r0 += slab) {
-    const int64_t m = std::min(slab, n_train - r0);
-    const float *src = train_vectors + r0 * d;
-    if (!on_device) {
-      if (int rc = stage_rows(ix.get(), src, m)) return rc;
-      src = ix->stage.as<float>();
-    }
-    if (int rc = prepare_slab(ix.get(), src, m, tflat, tsumsq, r0)) return rc;
-  }
+  if (int rc = upload_rows(ix.get(), train_vectors, on_device, n_train, tflat.as<_Float16>(), tsumsq.as<float>())) return rc;
   if (int rc = train_codebooks(ix.get(), tflat.as<_Float16>(), tsumsq.as<float>(), n_train, rounds, seed)) return rc;
   *out = ix.release();
   return IVF_OK;
@@ -993,28 +729,12 @@ int train_rows_polysemous(int32_t device, int32_t metric, int32_t d, int32_t nli
   return IVF_OK;
 }
 
-int check_ids_rule(const ivfpq_index *ix, bool with_ids) {
-  if (ix->ids_mode == 1 && !with_ids) return fail(IVF_EINVAL, "the index holds rows added with ids: an add must give ids");
-  if (ix->ids_mode == 0 && with_ids) return fail(IVF_EINVAL, "the index holds rows added without ids (its ids are positions): ids must be NULL");
-  return IVF_OK;
-}
-
 // ivfpq_search, over host queries or over queries that are on the device
 int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe, float *out_dist,
                 int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr, int32_t ht = 0) {
   if (!ix || !queries) return fail(IVF_EINVAL, "null argument");
   if (po ? !po->pos || !po->rank || !po->cnt : !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
-  if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
-  if (k < 1 || k > MAX_K) return fail(IVF_EINVAL, "k must be in 1..1024");
-  if (nprobe < 1 || nprobe > MAX_NPROBE) return fail(IVF_EINVAL, "nprobe must be in 1..1024");
-  nprobe = std::min(nprobe, ix->nlist);
-  ITRY(hipSetDevice(ix->device));
-  ITRY(ix->probes.reserve((size_t)nq * nprobe * sizeof(int32_t)));
-  ix->last_nq = 0;
-  ix->last_nprobe = nprobe;
-  ix->last_rows = 0;
-  ix->last_rounds = 0;
-  ix->t_coarse = ix->t_scan = ix->t_sel = 0;
+  if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
   if (ht > 0) {
     ix->qc_nq = 0;  // (a failure below leaves no query codes to ask for)
     ITRY(ix->qcodes.reserve((size_t)nq * nprobe * ix->M));
@@ -1022,13 +742,11 @@ int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_dev
     ITRY(hipMemset(ix->qcodes.p, 0, (size_t)nq * nprobe * ix->M));
     ITRY(hipMemset(ix->scored_acc.p, 0, 8));
   }
-  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
-    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
-    if (int rc = search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, po ? nullptr : out_dist + (size_t)q0 * k,
-                              po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po, ht))
-      return rc;
-  }
-  ix->last_nq = nq;
+  if (int rc = search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
+        return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, po ? nullptr : out_dist + (size_t)q0 * k,
+                            po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po, ht);
+      }))
+    return rc;
   if (ht > 0) {
     unsigned long long scored = 0;
     ITRY(hipMemcpy(&scored, ix->scored_acc.p, 8, hipMemcpyDeviceToHost));
@@ -1044,7 +762,7 @@ int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_dev
 // ---------------------------------------------------------------------------------------------
 // the device-rows seam (ivf_device_rows.h)
 // ---------------------------------------------------------------------------------------------
-int64_t ivfpq_internal::slab_rows(int d) { return std::max<int64_t>(1, (int64_t)(64 << 20) / (d * 4)); }
+int64_t ivfpq_internal::slab_rows(int d) { return stage_slab_rows(d); }
 
 int ivfpq_internal::train_device(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
                                  const float *d_rows, int32_t niter, uint64_t seed, ivfpq_index **out) try {
@@ -1055,13 +773,10 @@ int ivfpq_internal::add_begin(ivfpq_index *ix, int64_t n, bool with_ids) try {
   if (!ix) return fail(IVF_EINVAL, "null index");
   if (n < 1) return fail(IVF_EINVAL, "n must be positive");
   if (int rc = check_ids_rule(ix, with_ids)) return rc;
+  if (int rc = grow_rows(ix, n)) return rc;
   const int64_t n_old = ix->n, total = n_old + n;
-  if (total >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
-  ITRY(hipSetDevice(ix->device));
   const int d = ix->d, M = ix->M;
   ITRY(ix->codes.grow_keep((size_t)n_old * M, (size_t)total * M));
-  ITRY(ix->cell.grow_keep((size_t)n_old * 4, (size_t)total * 4));
-  ITRY(ix->ids.grow_keep((size_t)n_old * 8, (size_t)total * 8));
   // a slab of rows at a time: prepare, assign, encode; the fp16 rows are scratch
   const int64_t slab = slab_rows(d);
   ITRY(ix->flat.reserve((size_t)std::min(slab, n) * d * sizeof(_Float16)));
@@ -1072,7 +787,7 @@ int ivfpq_internal::add_begin(ivfpq_index *ix, int64_t n, bool with_ids) try {
 int ivfpq_internal::add_slab(ivfpq_index *ix, int64_t r0, int64_t m, const float *d_rows) try {
   const int64_t at = ix->n + r0;
   const int M = ix->M;
-  if (int rc = prepare_slab(ix, d_rows, m, ix->flat, ix->sumsq, 0)) return rc;
+  if (int rc = prepare_slab(ix, d_rows, m, ix->flat.as<_Float16>(), ix->sumsq.as<float>())) return rc;
   int32_t *cell = ix->cell.as<int32_t>() + at;
   if (int rc = assign_rows(ix, ix->flat.as<_Float16>(), ix->sumsq.as<float>(), m, cell)) return rc;
   if (int rc = encode_rows(ix, ix->flat.as<_Float16>(), cell, m, ix->codes.as<uint8_t>() + (size_t)at * M, M, 1)) return rc;
@@ -1081,15 +796,7 @@ int ivfpq_internal::add_slab(ivfpq_index *ix, int64_t r0, int64_t m, const float
 } ABI_CATCH
 
 int ivfpq_internal::add_end(ivfpq_index *ix, int64_t n, const int64_t *ids) try {
-  const int64_t n_old = ix->n;
-  if (ids) {
-    ITRY(hipMemcpy(ix->ids.as<int64_t>() + n_old, ids, (size_t)n * 8, hipMemcpyHostToDevice));
-  } else {
-    hipLaunchKernelGGL(iota64_kernel, dim3(blocks_for(n)), dim3(256), 0, 0, ix->ids.as<int64_t>() + n_old, n_old, n);
-    ITRY(hipGetLastError());
-  }
-  ix->n = n_old + n;
-  ix->ids_mode = ids ? 1 : 0;
+  if (int rc = commit_add(ix, n, ids)) return rc;
   return layout_lists(ix);
 } ABI_CATCH
 
@@ -1171,8 +878,7 @@ int ivfpq_internal::restore_begin(int32_t device, int32_t metric, int32_t d, int
                                   const float *codebooks, int32_t ids_mode, int64_t n, ivfpq_index **out) try {
   if (!centroids || !codebooks || !out) return fail(IVF_EINVAL, "null argument");
   if (int rc = check_shape(metric, d, nlist, M)) return rc;
-  if (n < 0 || n >= ((int64_t)1 << 31) - 64) return fail(IVF_EINVAL, "vector count out of range");
-  if (ids_mode < -1 || ids_mode > 1 || (n == 0) != (ids_mode == -1)) return fail(IVF_EINVAL, "ids mode does not fit the row count");
+  if (int rc = check_restore(ids_mode, n)) return rc;
   std::unique_ptr<ivfpq_index> ix;
   if (int rc = new_index(device, metric, d, nlist, M, ix)) return rc;
   // the stored centroids are what the index keeps and what its coarse quantizer holds: neither is rounded or normalised again
@@ -1180,60 +886,28 @@ int ivfpq_internal::restore_begin(int32_t device, int32_t metric, int32_t d, int
   DCALL(ann_by_id::dann_build_device(device, metric, nlist, d, ix->cent.as<float>(), &ix->coarse, true));
   ITRY(hipMemcpy(ix->cb.p, codebooks, (size_t)M * KSUB * ix->dsub * sizeof(float), hipMemcpyHostToDevice));
   ITRY(ix->codes.reserve((size_t)n * M));
-  ITRY(ix->cell.reserve((size_t)n * 4));
-  ITRY(ix->ids.reserve((size_t)n * 8));
-  ix->rs.n = n;
-  ix->rs.ids_mode = ids_mode;
-  ix->rs.open = true;
+  if (int rc = restore_open(ix.get(), ids_mode, n)) return rc;
   *out = ix.release();
   return IVF_OK;
 } ABI_CATCH
 
 int ivfpq_internal::restore_stage(ivfpq_index *ix, int64_t m, int64_t **ids, int32_t **cells, uint8_t **codes) try {
-  if (!ix || !ix->rs.open || !ids || !cells || !codes) return fail(IVF_EINVAL, "no restore in progress");
-  if (m < 1 || m > restore_slab_rows(ix->M)) return fail(IVF_EINVAL, "slab size out of range");
-  ITRY(hipSetDevice(ix->device));
-  ITRY(ix->rs.stage(m, (size_t)ix->M));
-  *ids = ix->rs.ids();
-  *cells = ix->rs.cells();
-  *codes = (uint8_t *)ix->rs.payload();
-  return IVF_OK;
+  return restore_staging(ix, m, ix ? restore_slab_rows(ix->M) : 0, ix ? (size_t)ix->M : 0, ids, cells, (void **)codes);
 } ABI_CATCH
 
 int ivfpq_internal::restore_slab(ivfpq_index *ix, int64_t r0, int64_t m) try {
-  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
-  RestoreState &rs = ix->rs;
-  if (m < 1 || m > rs.slab || r0 != rs.done || m > rs.n - r0) return fail(IVF_EINVAL, "slab outside the rows announced");
-  ITRY(hipSetDevice(ix->device));
-  uint32_t bad[2] = {0, 0};
-  ITRY(restore_upload(rs, r0, m, ix->nlist, ix->ids.as<int64_t>(), ix->cell.as<int32_t>(), ix->codes.p, bad));
-  if (bad[0] != 0xffffffffu)
-    return fail(IVF_EINVAL, "row " + std::to_string(bad[0]) + ": its cell is outside [0, nlist = " + std::to_string(ix->nlist) + ")");
-  if (bad[1] != 0xffffffffu)
-    return fail(IVF_EINVAL, "row " + std::to_string(bad[1]) + ": the ids of this index are positions, and its id is not its position");
-  rs.done = r0 + m;
+  if (int rc = restore_rows(ix, r0, m, ix ? ix->codes.p : nullptr)) return rc;
+  ix->rs.done = r0 + m;
   return IVF_OK;
 } ABI_CATCH
 
 int ivfpq_internal::restore_end(ivfpq_index *ix) try {
-  if (!ix || !ix->rs.open) return fail(IVF_EINVAL, "no restore in progress");
-  if (ix->rs.done != ix->rs.n) return fail(IVF_EINVAL, "rows are missing");
-  ITRY(hipSetDevice(ix->device));
-  ix->n = ix->rs.n;
-  ix->ids_mode = ix->rs.ids_mode;
-  ix->rs.close();
+  if (int rc = restore_close(ix)) return rc;
   return ix->n > 0 ? layout_lists(ix) : IVF_OK;
 } ABI_CATCH
 
 int ivfpq_internal::export_rows(const ivfpq_index *ix, int64_t r0, int64_t m, int64_t *ids, int32_t *cells, uint8_t *codes) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (r0 < 0 || m < 0 || r0 > ix->n || m > ix->n - r0) return fail(IVF_EINVAL, "rows outside the index");
-  if (m == 0) return IVF_OK;
-  ITRY(hipSetDevice(ix->device));
-  if (ids) ITRY(hipMemcpy(ids, ix->ids.as<int64_t>() + r0, (size_t)m * 8, hipMemcpyDeviceToHost));
-  if (cells) ITRY(hipMemcpy(cells, ix->cell.as<int32_t>() + r0, (size_t)m * 4, hipMemcpyDeviceToHost));
-  if (codes) ITRY(hipMemcpy(codes, ix->codes.as<uint8_t>() + (size_t)r0 * ix->M, (size_t)m * ix->M, hipMemcpyDeviceToHost));
-  return IVF_OK;
+  return export_columns(ix, r0, m, ids, cells, codes, ix ? ix->codes.p : nullptr, ix ? (size_t)ix->M : 0);
 } ABI_CATCH
 
 int ivfpq_internal::ids_mode(const ivfpq_index *ix) { return ix->ids_mode; }
@@ -1321,20 +995,12 @@ int ivfpq_last_ht_stats(const ivfpq_index_t *ix, int64_t *rows_scored) try {
 } ABI_CATCH
 
 int ivfpq_index_info(const ivfpq_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist, int32_t *M) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (n) *n = ix->n;
-  if (d) *d = ix->d;
-  if (metric) *metric = ix->metric;
-  if (nlist) *nlist = ix->nlist;
+  if (int rc = index_info(ix, n, d, metric, nlist)) return rc;
   if (M) *M = ix->M;
   return IVF_OK;
 } ABI_CATCH
 
-int ivfpq_index_get_centroids(const ivfpq_index_t *ix, float *out) try {
-  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
-  DCALL(dann_index_get_vectors(ix->coarse, 0, ix->nlist, out));
-  return IVF_OK;
-} ABI_CATCH
+int ivfpq_index_get_centroids(const ivfpq_index_t *ix, float *out) try { return get_centroids(ix, out); } ABI_CATCH
 
 int ivfpq_index_get_codebooks(const ivfpq_index_t *ix, float *out) try {
   if (!ix || !out) return fail(IVF_EINVAL, "null argument");
@@ -1351,41 +1017,19 @@ int ivfpq_index_get_codes(const ivfpq_index_t *ix, uint8_t *out) try {
   return IVF_OK;
 } ABI_CATCH
 
-int ivfpq_index_list_sizes(const ivfpq_index_t *ix, int64_t *out) try {
-  if (!ix || !out) return fail(IVF_EINVAL, "null argument");
-  std::copy(ix->h_sizes.begin(), ix->h_sizes.end(), out);
-  return IVF_OK;
-} ABI_CATCH
+int ivfpq_index_list_sizes(const ivfpq_index_t *ix, int64_t *out) try { return list_sizes(ix, out); } ABI_CATCH
 
 int ivfpq_index_get_assignment(const ivfpq_index_t *ix, int64_t *out_ids, int32_t *out_cells) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (ix->n == 0) return IVF_OK;
-  ITRY(hipSetDevice(ix->device));
-  if (out_ids) ITRY(hipMemcpy(out_ids, ix->ids.p, (size_t)ix->n * 8, hipMemcpyDeviceToHost));
-  if (out_cells) ITRY(hipMemcpy(out_cells, ix->cell.p, (size_t)ix->n * 4, hipMemcpyDeviceToHost));
-  return IVF_OK;
+  return get_assignment(ix, out_ids, out_cells);
 } ABI_CATCH
 
 int ivfpq_last_probes(const ivfpq_index_t *ix, int32_t *nq, int32_t *nprobe, int32_t *out_cells) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (nq) *nq = ix->last_nq;
-  if (nprobe) *nprobe = ix->last_nprobe;
-  if (out_cells && ix->last_nq > 0) {
-    ITRY(hipSetDevice(ix->device));
-    ITRY(hipMemcpy(out_cells, ix->probes.p, (size_t)ix->last_nq * ix->last_nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  return IVF_OK;
+  return last_probes(ix, nq, nprobe, out_cells);
 } ABI_CATCH
 
 int ivfpq_last_stats(const ivfpq_index_t *ix, int64_t *rows_scanned, int32_t *rounds, float *coarse_ms, float *scan_ms,
                      float *select_ms) try {
-  if (!ix) return fail(IVF_EINVAL, "null index");
-  if (rows_scanned) *rows_scanned = ix->last_rows;
-  if (rounds) *rounds = ix->last_rounds;
-  if (coarse_ms) *coarse_ms = ix->t_coarse;
-  if (scan_ms) *scan_ms = ix->t_scan;
-  if (select_ms) *select_ms = ix->t_sel;
-  return IVF_OK;
+  return last_stats(ix, rows_scanned, rounds, coarse_ms, scan_ms, select_ms);
 } ABI_CATCH
 
 int ivfpq_index_destroy(ivfpq_index_t *ix) try {

@@ -34,24 +34,13 @@
 #include "../../include/opq_ann.h"
 #include "../../include/polysemous_ann.h"
 #include "sann_device.h"  // mix64
-#include "abi_guard.h"
 #include "ivf_device_rows.h"
 #include "faiss_restore.h"
+#include "ivf_error.h"  // g_err, fail, ITRY, ABI_CATCH
 #include "ivf_kernels.h"
-#define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &m) {
-  g_err = m;
-  return code;
-}
-#define ITRY(expr)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(IVF_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 // a call into ivfpq_ann.hip: the same status codes, its message is in ivfpq_last_error()
 #define PCALL(expr)                                              \
   do {                                                           \

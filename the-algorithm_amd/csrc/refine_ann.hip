@@ -30,24 +30,13 @@
 #include "../../include/ivfpq_ann.h"
 #include "../../include/opq_ann.h"
 #include "../../include/refine_ann.h"
-#include "abi_guard.h"
 #include "ivf_device_rows.h"
 #include "faiss_restore.h"
+#include "ivf_error.h"  // g_err, fail, ITRY, ABI_CATCH
 #include "ivf_kernels.h"
-#define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &m) {
-  g_err = m;
-  return code;
-}
-#define ITRY(expr)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(IVF_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 // a call into the base: the same status codes, its message is in the base's *_last_error()
 #define BCALL(ix, expr)                                                                           \
   do {                                                                                            \
