@@ -800,9 +800,14 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
     }
     // the cluster-level cut counted postings the filters then removed: cut by the data after all.  (With nothing
     // removed -- live + folded = T -- the count behind the cut is exact; it may then be below kl on purpose: the
-    // descriptor kernel's query-level rule.)
+    // descriptor kernel's query-level rule.)  The cut also counted the postings that then FOLDED into a representative:
+    // when the survivors and the folded together reach kl, the unit's own rule was the one in force and the folding took
+    // the offer below kl -- a unit that is the whole query (P = 1) then offered fewer than k and was re-run every time.
+    // (Sufficient, not exact: CTL_FOLD counts every folded posting of the unit, behind the cut or not, so a unit that the
+    // query-level rule held below kl on purpose and that folded a few duplicates elsewhere re-cuts too.  That costs it a
+    // second pass of 5a / 5b and the merge a few more candidates, never an answer.)
     if (!cut_by_data && tau != 0u && s_ctl[CTL_NSURV] < kl && s_ctl[CTL_NSURV] < s_ctl[CTL_LIVE] &&
-        s_ctl[CTL_LIVE] + s_ctl[CTL_FOLD] < (int)T && !s_ctl[CTL_BAD] && !overflow) {
+        (s_ctl[CTL_LIVE] + s_ctl[CTL_FOLD] < (int)T || s_ctl[CTL_NSURV] + s_ctl[CTL_FOLD] >= kl) && !s_ctl[CTL_BAD] && !overflow) {
       __syncthreads();  // (everyone has read the counters)
       if (tid == 0) s_ctl[CTL_NSURV] = 0;
       cut_by_data = true;

@@ -555,6 +555,22 @@ class QueryBatch:
         _check(load_library().sann_batch_stats(self._h, C.byref(s)))
         return s
 
+    def unit_arrays(self):
+        """sann_debug_unit_arrays: (unit_T, unit_unique, cand_cnt, unit_flags), each [nq, P], as the last run() left them
+        (finish() lets the general path rewrite the units it re-ran).  Synchronises the device."""
+        P = self.index.info().n_partitions
+        t, u, c = (np.zeros((self.nq, P), np.int32) for _ in range(3))
+        f = np.zeros((self.nq, P), np.uint32)
+        _check(load_library().sann_debug_unit_arrays(self._h, _ptr(u), _ptr(c), _ptr(f), _ptr(t)))
+        return t, u, c, f
+
+    def overflow_reasons(self) -> np.ndarray:
+        """sann_debug_overflow_reasons: units flagged UNIT_OVERFLOW by reason (1 scanned clusters, 2 postings, 3 match
+        list, 4 key range, 5 survivor list), int32[8]."""
+        counts = np.zeros(8, np.int32)
+        _check(load_library().sann_debug_overflow_reasons(self._h, counts.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        return counts
+
     def close(self):
         if self._h:
             load_library().sann_batch_destroy(self._h)
