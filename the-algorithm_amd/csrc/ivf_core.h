@@ -4,8 +4,9 @@
 // steps of an add and of a restore around the payload, and the exports.  Where the two indexes differ the difference is
 // an argument: the rows of a list block, a payload buffer and its row bytes, or a callable (the payload scatter, the scan
 // launch).  Failures go through the error channel of ivf_error.h.  A source includes this once, as it does ivf_kernels.h;
-// everything is file-local.  Its host functions instantiate the hipcub sorts and scans, so only the two index sources
-// include it: opq_ann.hip and refine_ann.hip take ivf_error.h and ivf_kernels.h alone.
+// everything is file-local.  Its host functions instantiate the hipcub sorts and scans, so only the index sources include
+// it (the two above and grouped_ann.hip, whose cell is the caller's group: IvfBase without a coarse quantizer, cell_bits
+// wide enough for its group numbers): opq_ann.hip and refine_ann.hip take ivf_error.h and ivf_kernels.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -35,6 +36,7 @@ namespace {
 // what an ivf_index and an ivfpq_index both hold; each adds its payload (rows or codes), its list payload and its own scratch
 struct IvfBase {
   int device = 0, metric = 0, d = 0, nlist = 0;
+  int cell_bits = CELL_BITS;  // radix-sort key width of a cell number of this index
   int64_t n = 0;
   int ids_mode = -1;  // -1: no add yet; 0: ids are positions; 1: ids given
   dann_index *coarse = nullptr;
@@ -122,9 +124,9 @@ int upload_rows(IvfBase *ix, const float *rows, bool on_device, int64_t n, _Floa
 // stable sort of n (cell number, value) pairs by cell
 int sort_by_cell(IvfBase *ix, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out, int64_t n) {
   size_t tb = 0;
-  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
+  ITRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_out, vals, vals_out, (int)n, 0, ix->cell_bits, (hipStream_t)0));
   ITRY(ix->sort_tmp.reserve(tb));
-  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, keys, keys_out, vals, vals_out, (int)n, 0, CELL_BITS, (hipStream_t)0));
+  ITRY(hipcub::DeviceRadixSort::SortPairs(ix->sort_tmp.p, tb, keys, keys_out, vals, vals_out, (int)n, 0, ix->cell_bits, (hipStream_t)0));
   return IVF_OK;
 }
 int exclusive_sum(IvfBase *ix, const uint32_t *in, uint32_t *out, int n) {

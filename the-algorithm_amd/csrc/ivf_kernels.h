@@ -250,6 +250,11 @@ struct Buf {
     if (e == hipSuccess) bytes = n ? n : 8;
     return e;
   }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
   // growth that keeps the first `keep` bytes (device to device)
   hipError_t grow_keep(size_t keep, size_t want) {
     if (p && want <= bytes) return hipSuccess;
