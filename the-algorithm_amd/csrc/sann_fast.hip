@@ -43,7 +43,9 @@
 // divergent branch, so lanes that sat the branch out reloaded garbage: results differed from run to run.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdlib>
+#include <type_traits>
 
 #include "sann_device.h"
 #include "sann_kernels.h"
@@ -903,10 +905,14 @@ static hipError_t launch_one(const IndexView &ix, const BatchView &b, const Fast
 }
 
 // The same descriptors, one WORKGROUP per query (P <= 32): the n_scan x P sub-lists of a query are resolved by 256
-// threads with all their loads in flight at once and partition-contiguous (coalesced) reads of the offset and cut
-// tables; the per-partition prefix over the clusters runs in LDS, and the rows are written out coalesced.  One
-// round of 1024 workgroups instead of four rounds of one-wave units, each a chain of three dependent trips to memory.
+// threads in three dependent trips to memory -- the header; the scan rows of up to DESC_SLOTS sub-lists per thread
+// (and the weights the key sort reads); their starts and cuts, partition-contiguous (coalesced) reads of the offset
+// and cut tables -- each trip's loads issued together and waited for once.  (As a plain `for (i = tid; ...)` loop
+// hipcc did not unroll it: two trips per iteration, fourteen in a row at 50 clusters x 32 partitions, behind three for
+// the header.)  The per-partition prefix over the clusters runs in LDS, and the rows are written out coalesced.  One
+// round of 1024 workgroups instead of four rounds of one-wave units.
 constexpr int DESC_Q_ITEMS = 4096;  // NSCAN_MAX x 32
+constexpr int DESC_SLOTS = 8;       // sub-lists a thread resolves per group of loads
 // QPW = queries per workgroup: 1 (all 256 threads on one query: P >= 16, up to 4096 sub-lists) or 4 (one WAVE per
 // query and no workgroup barrier: a shard's queries have 4 or 8 partitions, 200-400 sub-lists each, and N times as many
 // of them -- 8192 workgroups of mostly idle threads took 30 us).
@@ -922,11 +928,41 @@ __global__ __launch_bounds__(256) void desc_query_kernel(IndexView ix, BatchView
   const int P = ix.P;
   uint32_t *const s_base = s_desc + grp * 2 * P * ld, *const s_len = s_base + P * ld;
   const int q = blockIdx.x * QPW + grp;
-  {
-    const int g = blockIdx.x * 256 + threadIdx.x;  // per-run state (see desc_kernel)
+  // per-run state (see desc_kernel).  The stores of this kernel's first part stand BEHIND the loads of the chain below:
+  // a store in front of a load is counted by the same vmcnt, and (the pointers may alias) pins the load behind it.
+  auto clear_status = [&]() {
+    const int g = blockIdx.x * 256 + threadIdx.x;
     if (g < b.nq + 2) b.status[g] = 0;
+  };
+  if (q >= b.nq) {  // (QPW > 1: whole waves, and nothing below synchronises across a query's threads' workgroup)
+    clear_status();
+    return;
   }
-  if (q >= b.nq) return;  // (QPW > 1: whole waves, and nothing below synchronises across a query's threads' workgroup)
+  // Trip 1: the header, once -- scan_begin, n_scan, M, k, alg, use_norms and inv_l2_32 are bytes 48..79 of it, two
+  // 16-byte loads and one wait.  (Left to hipcc, `b.hdr[q]` was read field by field where each was first used: three
+  // dependent trips.)  A wave serves one query, so the words are wave-uniform and go to scalar registers.
+  static_assert(offsetof(QueryHdr, scan_begin) == 48 && offsetof(QueryHdr, n_scan) == 52 && offsetof(QueryHdr, M) == 56 &&
+                    offsetof(QueryHdr, k) == 60 && offsetof(QueryHdr, alg) == 64 && offsetof(QueryHdr, use_norms) == 72 &&
+                    offsetof(QueryHdr, inv_l2_32) == 76,
+                "desc_query_kernel's header loads");
+  QueryHdr h{};  // (only these seven fields are filled: the kernel reads no other)
+  {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 h0, h1;
+    const QueryHdr *const hp = b.hdr + q;
+    asm volatile("global_load_dwordx4 %0, %2, off offset:48\n\tglobal_load_dwordx4 %1, %2, off offset:64\n\ts_waitcnt vmcnt(0)"
+                 : "=&v"(h0), "=&v"(h1) : "v"(hp) : "memory");
+    h.scan_begin = __builtin_amdgcn_readfirstlane((int)h0.x);
+    h.n_scan = __builtin_amdgcn_readfirstlane((int)h0.y);
+    h.M = __builtin_amdgcn_readfirstlane((int)h0.z);
+    h.k = __builtin_amdgcn_readfirstlane((int)h0.w);
+    h.alg = __builtin_amdgcn_readfirstlane((int)h1.x);
+    h.use_norms = __builtin_amdgcn_readfirstlane((int)h1.z);
+    h.inv_l2_32 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)h1.w));
+  }
+  const int M = h.M;
+  const int scan_begin = h.scan_begin;
+  const int n_scan = h.n_scan;
   // a query's threads meet: the workgroup's barrier, or -- one wave per query -- just the order of the wave's own LDS traffic
   auto meet = [&]() {
     if constexpr (QPW == 1) __syncthreads();
@@ -936,12 +972,10 @@ __global__ __launch_bounds__(256) void desc_query_kernel(IndexView ix, BatchView
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
   };
-  const int M = b.hdr[q].M;
-  const int scan_begin = b.hdr[q].scan_begin;
-  const int n_scan = b.hdr[q].n_scan;
-  for (int p = tid; p < P; p += G) b.unit_fb[(int64_t)q * P + p] = -1;
   if (n_scan > NSCAN_MAX) {  // the unit kernel sends such units to the general path
+    clear_status();
     for (int p = tid; p < P; p += G) {
+      b.unit_fb[(int64_t)q * P + p] = -1;
       b.unit_T[(int64_t)q * P + p] = 0;
       b.unit_pre[(int64_t)q * P + p] = 0u;
     }
@@ -953,37 +987,83 @@ __global__ __launch_bounds__(256) void desc_query_kernel(IndexView ix, BatchView
   __shared__ uint8_t s_ocl_all[QPW][64];    // ... and the cluster
   uint32_t *const s_okey = s_okey_all[grp];
   uint8_t *const s_ocl = s_ocl_all[grp];
-  const QueryHdr h = b.hdr[q];
   const bool cluster_cut = query_has_cluster_cut(h);  // (uniform)
-  if (cluster_cut && tid < 64) {
-    const float inv_l2_32 = h.inv_l2_32;
-    const uint32_t kc = tid < n_scan ? cosine_cluster_key(h.alg, b.scan_w[scan_begin + tid], inv_l2_32) : 0u;
-    const uint32_t pk = wave_sort_desc_u32(kc ? ((kc & ~0xffu) | (uint32_t)tid) : 0u);
-    const int c = (int)(pk & 0xffu);
-    s_ocl[tid] = (uint8_t)c;
-    s_okey[tid] = pk ? __shfl(kc, c, 64) : 0u;
-  }
-  const uint32_t *cut = nullptr;  // cached cut table for this query's M, if any (uniform)
+  const uint32_t *cut = nullptr;  // cached cut table for this query's M, if any (uniform; cut_M / cut are kernel arguments)
 #pragma unroll
   for (int j = 0; j < 4; j++)
     if (b.cut_M[j] == M) cut = b.cut[j];
+  // Each sub-list needs its start and one more word at the same index: its cut, or -- no cached table -- its end.
+  const uint32_t *const second = cut ? cut : ix.sub_offsets + 1;
   const int n_items = n_scan * P;
-  for (int i = tid; i < n_items; i += G) {
-    const int c = i >> ix.log2P, p = i & (P - 1);
-    const int row = b.scan_row[scan_begin + c];
-    const uint32_t base = ix.sub_offsets[(int64_t)row * P + p];
-    uint32_t len;
-    if (cut) {
-      len = cut[(int64_t)row * P + p];
-    } else {
-      const int n = (int)(ix.sub_offsets[(int64_t)row * P + p + 1] - base);
-      // postings with rank < M are a prefix of the sub-list
-      len = (n > 0 && ix.ranks[base + n - 1] < (uint32_t)M) ? (uint32_t)n
-                                                          : (uint32_t)lower_bound_rank(ix.ranks + base, n, (uint32_t)M);
-    }
-    s_base[p * ld + c] = base;
-    s_len[p * ld + c] = len;
+  // A thread's items, DESC_SLOTS at a time (50 clusters x 32 partitions: 7 of one group's 8 slots; 128 clusters: two
+  // groups).  Every slot loads, unconditionally, from an item index clamped into the query's range, so no loaded register
+  // has a second definition hipcc would have to merge behind the load -- the merge is what brings a wait per load (see
+  // the unit kernel's gather).  A slot past n_items re-reads the query's last item and writes nothing.  A query without
+  // clusters has no item to clamp to and loads nothing.
+  if (n_items > 0) {  // (uniform)
+    // Trip 2: the cluster weight the key sort reads, and all of the group's scan rows
+    double w_sort = b.scan_w[scan_begin + (tid < n_scan ? tid : n_scan - 1)];
+    // (one group, or two: written out, not a loop -- hipcc moved the key arithmetic, and with it the wait for w_sort,
+    // out of the loop and in front of the rows' loads)
+    auto group = [&](const int i0, auto first) {
+      int row[DESC_SLOTS];
+#pragma unroll
+      for (int s = 0; s < DESC_SLOTS; s++) {
+        const int i = i0 + s * G + tid, ii = i < n_items ? i : n_items - 1;
+        row[s] = b.scan_row[scan_begin + (ii >> ix.log2P)];
+      }
+      // (w_sort is pinned here, where it arrives together with the rows: hipcc otherwise sinks its load into the sort's
+      // branch below, a trip of its own behind trip 3)
+      if constexpr (decltype(first)::value) asm volatile("" : "+v"(w_sort));
+      // Trip 3: all of the group's sub-list starts and cuts (or ends)
+      uint32_t base[DESC_SLOTS], len[DESC_SLOTS];
+#pragma unroll
+      for (int s = 0; s < DESC_SLOTS; s++) {
+        const int i = i0 + s * G + tid, ii = i < n_items ? i : n_items - 1;
+        const int64_t at = (int64_t)row[s] * P + (ii & (P - 1));
+        base[s] = ix.sub_offsets[at];
+        len[s] = second[at];
+      }
+      // cluster-level cut: the order of the query's clusters by key is the same for all of its units -- sorted once, by
+      // wave 0 (lane c = cluster c), while trip 3 is in flight
+      if (decltype(first)::value && cluster_cut && tid < 64) {
+        const uint32_t kc = tid < n_scan ? cosine_cluster_key(h.alg, w_sort, h.inv_l2_32) : 0u;
+        const uint32_t pk = wave_sort_desc_u32(kc ? ((kc & ~0xffu) | (uint32_t)tid) : 0u);
+        const int c = (int)(pk & 0xffu);
+        s_ocl[tid] = (uint8_t)c;
+        s_okey[tid] = pk ? __shfl(kc, c, 64) : 0u;
+      }
+      if (!cut) {  // (uniform) postings with rank < M are a prefix of the sub-list: all of it if its last rank is < M ...
+        uint32_t last[DESC_SLOTS];
+#pragma unroll
+        for (int s = 0; s < DESC_SLOTS; s++) {  // (trip 4, again for all slots together; no posting, no rank to read)
+          const int n = (int)(len[s] - base[s]);
+          last[s] = ix.n_postings != 0u ? ix.ranks[n > 0 ? base[s] + (uint32_t)n - 1u : 0u] : 0u;
+        }
+#pragma unroll
+        for (int s = 0; s < DESC_SLOTS; s++) {  // ... else found by a search (slots past n_items search nothing)
+          const int n = i0 + s * G + tid < n_items ? (int)(len[s] - base[s]) : 0;
+          len[s] = (n > 0 && last[s] < (uint32_t)M) ? (uint32_t)n : (uint32_t)lower_bound_rank(ix.ranks + base[s], n, (uint32_t)M);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < DESC_SLOTS; s++) {
+        const int i = i0 + s * G + tid;
+        if (i < n_items) {
+          const int c = i >> ix.log2P, p = i & (P - 1);
+          s_base[p * ld + c] = base[s];
+          s_len[p * ld + c] = len[s];
+        }
+      }
+    };
+    group(0, std::true_type{});
+    if (n_items > DESC_SLOTS * G) group(DESC_SLOTS * G, std::false_type{});  // (uniform; n_items <= 2 * DESC_SLOTS * G)
+  } else if (cluster_cut && tid < 64) {  // (no cluster: no key)
+    s_ocl[tid] = 0;
+    s_okey[tid] = 0u;
   }
+  clear_status();
+  for (int p = tid; p < P; p += G) b.unit_fb[(int64_t)q * P + p] = -1;
   meet();
   // The query-level rule: clusters in key order until k plus a margin postings are covered in ALL the query's partitions
   // together.  A cluster's single-cluster candidates share one key, so a cut below that cluster keeps every candidate
@@ -1056,6 +1136,8 @@ hipError_t launch_desc(const IndexView &ix, const BatchView &b, int n_units, int
   // (one workgroup per query from 8 partitions up: the cluster-level cut's sort is then done once per query, not once per
   // unit -- 38 us against 54 for an 8-GPU shard's 65536 units)
   if (ix.P >= 4 && ix.P * NSCAN_MAX <= DESC_Q_ITEMS) {
+    // (a query's threads take its sub-lists in at most two groups of DESC_SLOTS each)
+    static_assert(DESC_Q_ITEMS <= 2 * DESC_SLOTS * 256 && 8 * NSCAN_MAX <= 2 * DESC_SLOTS * 64, "desc_query_kernel's groups");
     if (ix.P <= 8)  // four queries per workgroup, one wave each
       hipLaunchKernelGGL((desc_query_kernel<4>), dim3((unsigned)((b.nq + 3) / 4)), dim3(256), (size_t)4 * ix.P * ld * 8, stream, ix, b, ld, k_local_floor);
     else

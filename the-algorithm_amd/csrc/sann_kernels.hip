@@ -563,6 +563,73 @@ __device__ bool sample_cut(const uint64_t *hi, const uint64_t *lo, int n, int ne
   return false;
 }
 
+// Entries a fast unit handed over as (cluster, posting position) (sann_device.h, CAND_DEFERRED), nr <= RC of a thread's
+// (kh, kid) pairs: the posting and the cluster's weight (and, for the offline forms, the tweet's norm) are fetched and the
+// entry is scored exactly as ApproximateCosineSimilarity.scala:92-96,111-125 does for a tweet met in one cluster.
+// All RC entries' postings and weights go out before any is waited for (the norms likewise, in a second trip).  Every entry loads, unconditionally: one that is not deferred,
+// or whose hand-over fails the range check, reads posting 0 and the query's cluster 0 instead, so no loaded register
+// has a second definition -- `ps = {0, 0.0}; if (deferred) ps = load` made hipcc merge the two behind each load, with a
+// wait of its own: one trip per entry (the unit kernel's gather met the same).  The selects come after the loads.
+// (posting position, cluster sequence number) were written by the unit kernel: checked against the index and the query
+// before they address anything -- a corrupted hand-over becomes an unproven query (re-answered exactly by the general
+// path), never a faulting load.  An index without postings, or a query without clusters, has no position to clamp to
+// and loads nothing.  A wave none of whose entries is deferred skips the trip.
+template <int RC>
+__device__ __forceinline__ void score_deferred(const IndexView &ix, const BatchView &b, const QueryHdr &h, uint64_t *kh, int64_t *kid,
+                                               int nr, bool &bad_handover) {
+  const bool can_load = ix.n_postings != 0u && h.n_scan > 0;  // (uniform; false: every hand-over fails the range check)
+  bool any = false;
+#pragma unroll
+  for (int rr = 0; rr < RC; rr++) {
+    if (rr < nr && kh[rr] == CAND_DEFERRED) {
+      if (can_load && (uint32_t)kid[rr] < ix.n_postings && (uint32_t)((uint64_t)kid[rr] >> 32) < (uint32_t)h.n_scan) {
+        any = true;
+      } else {
+        kh[rr] = CAND_DROPPED;
+        bad_handover = true;
+      }
+    }
+  }
+  if (__ballot(any) == 0ull) return;  // (uniform per wave)
+  // (from here on an entry that is still deferred has passed the check, and the index and the query are not empty)
+  int64_t id[RC];
+  double dot[RC], nsq[RC];
+  {
+    Posting ps[RC];
+    double wq[RC];
+#pragma unroll
+    for (int rr = 0; rr < RC; rr++) {
+      const bool live = rr < nr && kh[rr < nr ? rr : 0] == CAND_DEFERRED;
+      const uint64_t e = (uint64_t)kid[rr < nr ? rr : 0];
+      ps[rr] = ix.postings[live ? (uint32_t)e : 0u];
+      wq[rr] = b.scan_w[h.scan_begin + (live ? (int)(e >> 32) : 0)];
+    }
+#pragma unroll
+    for (int rr = 0; rr < RC; rr++) {
+      id[rr] = ps[rr].id;
+      dot[rr] = 0.0 + ps[rr].score * wq[rr];        // getOrElse(tweetId, 0.0) + score * sourceClusterScore  (:92-94)
+      nsq[rr] = 0.0 + ps[rr].score * ps[rr].score;  // (:95-96)
+    }
+  }
+  // tweets_ann.sql:50-51 -- the offline forms' normaliser: one more trip for the group (behind the first, whose registers
+  // it takes over: with both in flight merge_kernel<512, 1728> spilled)
+  if (h.use_norms) {  // (uniform)
+#pragma unroll
+    for (int rr = 0; rr < RC; rr++) {
+      const bool live = rr < nr && kh[rr < nr ? rr : 0] == CAND_DEFERRED;
+      nsq[rr] = ix.norms[live ? (uint32_t)kid[rr < nr ? rr : 0] : 0u];
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < RC; rr++) {
+    if (rr < nr && kh[rr] == CAND_DEFERRED) {
+      const double v = normalise(h.alg, dot[rr], nsq[rr], h.l2norm, h.lognorm);
+      kh[rr] = v >= h.min_score ? score_key(v) : CAND_DROPPED;  // :125 (false for NaN)
+      kid[rr] = id[rr];
+    }
+  }
+}
+
 // SURV = capacity of the survivor list: 512 when every k of the batch is <= 448, else 1024.  The staging
 // area holds 1728 entries for SURV = 512: 39.8 KB of LDS in all, FOUR workgroups per CU, so a 1024-query batch
 // merges in one round of workgroups (at 2048 entries it was 44 KB, three per CU, two rounds: twice the time).
@@ -616,19 +683,6 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
   int64_t *out_ids = (int64_t *)((char *)b.out_ids + out_shift) + (int64_t)ql * b.stride;
   double *out_scores = (double *)((char *)b.out_scores + out_shift) + (int64_t)ql * b.stride;
 
-  // what the exactness proof at the end reads per unit (P <= WG: one unit per thread), fetched now so that the two
-  // dependent trips to memory are long over when the sort is
-  int pf_unique = 0;
-  uint32_t pf_T = 0, pf_flags = 0;
-  uint64_t pf_thi = 0, pf_tlo = 0;
-  if (tid < P) {
-    const int64_t unit = unit0 + tid;
-    pf_unique = b.unit_unique[unit];
-    pf_T = b.q_stat ? (uint32_t)b.unit_T[unit] : 0u;
-    pf_flags = b.unit_flags[unit];
-    pf_thi = b.unit_thr[2 * unit];
-    pf_tlo = b.unit_thr[2 * unit + 1];
-  }
   MSTAMP(1);  // offsets
   int best_n = 0;  // entries currently in s_e2
   int u_begin = 0;
@@ -671,45 +725,13 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
           kid[r] = id[j];
         }
       }
-      // Entries a fast unit handed over as (cluster, posting position) (sann_device.h, CAND_DEFERRED): the posting and the
-      // cluster's weight are fetched here -- all of a thread's entries in one trip -- and scored exactly as
-      // ApproximateCosineSimilarity.scala:92-96,111-125 does for a tweet met in one cluster.
+      // Entries a fast unit handed over as (cluster, posting position) are fetched and scored here (score_deferred), RC of
+      // a thread's entries per trip.
       // (four entries at a time: with all seven in flight the kernel needed 176 registers and lost half its occupancy)
       constexpr int RC = 4;
 #pragma unroll
       for (int r0 = 0; r0 < R; r0 += RC) {
-        Posting ps[RC];
-        double wq[RC];
-#pragma unroll
-        for (int rr = 0; rr < RC; rr++) {
-          const int r = r0 + rr;
-          ps[rr] = Posting{0, 0.0};
-          wq[rr] = 0.0;
-          if (r < R && kh[r] == CAND_DEFERRED) {
-            // (posting position, cluster sequence number) were written by the unit kernel: checked against the index and
-            // the query before they address anything -- a corrupted hand-over becomes an unproven query (re-answered
-            // exactly by the general path), never a faulting load
-            if ((uint32_t)kid[r] < ix.n_postings && (uint32_t)((uint64_t)kid[r] >> 32) < (uint32_t)h.n_scan) {
-              ps[rr] = ix.postings[(uint32_t)kid[r]];
-              wq[rr] = b.scan_w[h.scan_begin + (int)((uint64_t)kid[r] >> 32)];
-            } else {
-              kh[r] = CAND_DROPPED;
-              bad_handover = true;
-            }
-          }
-        }
-#pragma unroll
-        for (int rr = 0; rr < RC; rr++) {
-          const int r = r0 + rr;
-          if (r < R && kh[r] == CAND_DEFERRED) {
-            const double dot = 0.0 + ps[rr].score * wq[rr];  // getOrElse(tweetId, 0.0) + score * sourceClusterScore  (:92-94)
-            double nsq = 0.0 + ps[rr].score * ps[rr].score;  // (:95-96)
-            if (h.use_norms) nsq = ix.norms[(uint32_t)kid[r]];  // tweets_ann.sql:50-51 (offline forms: one more trip)
-            const double v = normalise(h.alg, dot, nsq, h.l2norm, h.lognorm);
-            kh[r] = v >= h.min_score ? score_key(v) : CAND_DROPPED;  // :125 (false for NaN)
-            kid[r] = ps[rr].id;
-          }
-        }
+        score_deferred<RC>(ix, b, h, kh + r0, kid + r0, R - r0 < RC ? R - r0 : RC, bad_handover);
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
@@ -757,6 +779,14 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
     __syncthreads();
   }
 
+  // what the exactness proof at the end reads per unit (P <= WG: one unit per thread), fetched here so that the trip to
+  // memory is long over when the sort is -- and not in front of the staging, whose grouped loads need the registers.
+  // Every thread loads, from a unit index clamped into the query's (`x = 0; if (tid < P) x = load` is two definitions
+  // merged right behind the load: hipcc waited for the trip here); who may use the values is decided where they are used.
+  const int64_t pf_unit = unit0 + (tid < P ? tid : P - 1);
+  const int pf_unique = b.unit_unique[pf_unit];
+  const uint32_t pf_T = (uint32_t)b.unit_T[pf_unit], pf_flags = b.unit_flags[pf_unit];
+  const uint64_t pf_thi = b.unit_thr[2 * pf_unit], pf_tlo = b.unit_thr[2 * pf_unit + 1];
   MSTAMP(4);  // compacted
   // sort the survivors, keep the first k: every wave sorts runs of 64 in registers (DPP / permlane network, no barriers);
   // the runs are then merged pairwise -- an entry's place in the merged pair is its offset in its own run plus the
@@ -850,8 +880,8 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
   uint32_t t_max = 0, t_sum = 0;
   if (tid < P) {
     msz = pf_unique;
-    t_max = pf_T;
-    t_sum = pf_T;
+    t_max = b.q_stat ? pf_T : 0u;
+    t_sum = t_max;
     if (k > 0 && (pf_flags & UNIT_TRUNCATED) && key_gt(pf_thi, pf_tlo, xk_hi, xk_lo)) inexact = 1;
   }
   if (tid == 0) { s_ctl[0] = 0; s_ctl[1] = 0; s_ctl[2] = 0; s_ctl[3] = 0; }
@@ -943,39 +973,11 @@ __global__ __launch_bounds__(WG, (E <= 4 ? 6 : 4)) void merge_wave_kernel(IndexV
       kid[r] = id[j];
     }
   }
-  // candidates handed over as (cluster, posting position): fetch and score (as merge_kernel's staging does), four at a time
+  // candidates handed over as (cluster, posting position): fetched and scored as merge_kernel's staging does, four per trip
   bool bad_handover = false;
 #pragma unroll
   for (int r0 = 0; r0 < E; r0 += 4) {
-    Posting ps[4];
-    double wq[4];
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++) {
-      const int r = r0 + rr;
-      ps[rr] = Posting{0, 0.0};
-      wq[rr] = 0.0;
-      if (kh[r] == CAND_DEFERRED) {
-        if ((uint32_t)kid[r] < ix.n_postings && (uint32_t)((uint64_t)kid[r] >> 32) < (uint32_t)h.n_scan) {  // (as merge_kernel)
-          ps[rr] = ix.postings[(uint32_t)kid[r]];
-          wq[rr] = b.scan_w[h.scan_begin + (int)((uint64_t)kid[r] >> 32)];
-        } else {
-          kh[r] = CAND_DROPPED;
-          bad_handover = true;
-        }
-      }
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++) {
-      const int r = r0 + rr;
-      if (kh[r] == CAND_DEFERRED) {
-        const double dot = 0.0 + ps[rr].score * wq[rr];  // :92-94
-        double nsq = 0.0 + ps[rr].score * ps[rr].score;  // :95-96
-        if (h.use_norms) nsq = ix.norms[(uint32_t)kid[r]];  // tweets_ann.sql:50-51
-        const double v = normalise(h.alg, dot, nsq, h.l2norm, h.lognorm);
-        kh[r] = v >= h.min_score ? score_key(v) : CAND_DROPPED;  // :125 (false for NaN)
-        kid[r] = ps[rr].id;
-      }
-    }
+    score_deferred<4>(ix, b, h, kh + r0, kid + r0, 4, bad_handover);
     if (r0 + 4 < E) __builtin_amdgcn_sched_barrier(0);
   }
   // sort: runs of 64 in registers, then every entry's rank among all runs (ties -- only dropped entries tie -- by run)
