@@ -21,45 +21,15 @@
 #include <vector>
 
 #include "../../include/ann_by_id.h"
-#include "abi_guard.h"
 #include "ann_by_id_internal.h"
+#include "device_buf.h"
+#include "host_error.h"
+#define BTRY(expr) HIP_TRY_AS(ANN_BY_ID_EDEVICE, expr)
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, ANN_BY_ID_ENOMEM, ANN_BY_ID_EINTERNAL); }
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &m) {
-  g_err = m;
-  return code;
-}
-#define BTRY(expr)                                                                                      \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return fail(ANN_BY_ID_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 constexpr int MAX_D = 512;
-
-struct Buf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  Buf() = default;
-  Buf(const Buf &) = delete;
-  Buf &operator=(const Buf &) = delete;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t reserve(size_t n) {
-    if (n <= bytes && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    hipError_t e = hipMalloc(&p, n ? n : 8);
-    if (e == hipSuccess) bytes = n ? n : 8;
-    return e;
-  }
-  template <class T> T *as() const { return (T *)p; }
-};
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 

@@ -45,56 +45,24 @@
 
 #include "../../include/dense_ann.h"
 #include "sann_device.h"  // mix64
-#include "abi_guard.h"
 #include "ann_by_id_internal.h"
+#include "device_buf.h"
+#include "host_error.h"
+#include "survivor_topk.h"
+#define DTRY(expr) HIP_TRY_AS(DANN_EDEVICE, expr)
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, DANN_ENOMEM, DANN_EINTERNAL); }
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &m) {
-  g_err = m;
-  return code;
-}
-#define DTRY(expr)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(DANN_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float16v __attribute__((ext_vector_type(16)));
-
 constexpr int W2 = 4;             // waves per workgroup: one per SIMD, the whole 512-register file each
 constexpr int TILE_MAXIMA = 2 * W2;  // pass A writes two tile maxima per wave
-constexpr int CAP = 8192;         // survivors kept per query
-constexpr int MAX_K = 1024;
-constexpr int MAX_D = 512;
 constexpr int MAX_NQ = 4096;     // queries per GEMM launch
-
-struct Survivor {
-  float score;
-  uint32_t pos;
-};
-
-__device__ __forceinline__ uint32_t f2key(float f) {  // order-preserving float -> uint
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // ---------------------------------------------------------------------------------------------
 // rows (fp32, row-major) -> fp16 MFMA fragments.  One wave per row.  Serves the index (A operand)
 // and the queries (B operand): both want "row r of a 32-row block on lane r + 32h, k = 16s + 8h + j".
 // sumsq[row] = sum of the squares of the stored (rounded) halves, in fp32 arithmetic order-fixed.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ void prep_rows_kernel(const float *__restrict__ src, int64_t n, int d, int S, int normalise,
                                  int64_t row0, _Float16 *__restrict__ frag, float *__restrict__ sumsq) {
   int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -483,39 +451,6 @@ __global__ __launch_bounds__(W2 * 64) void gemm2_kernel(GemmArgs a) {
 #undef DANN_LDB
 }
 
-// ---------------------------------------------------------------------------------------------
-// k-th largest of n floats (stride in floats), one workgroup, 4 radix passes over an LDS histogram
-// ---------------------------------------------------------------------------------------------
-__device__ float wg_kth_largest(const float *vals, int64_t n, int stride, int k, uint32_t *hist /*[258]*/) {
-  uint32_t prefix = 0, mask = 0;
-  uint32_t want = (uint32_t)k;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-      uint32_t key = f2key(vals[i * stride]);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t acc = 0;
-      int dgt = 255;
-      for (; dgt > 0; --dgt) {
-        if (acc + hist[dgt] >= want) break;
-        acc += hist[dgt];
-      }
-      hist[256] = (uint32_t)dgt;
-      hist[257] = want - acc;
-    }
-    __syncthreads();
-    prefix |= hist[256] << shift;
-    mask |= 255u << shift;
-    want = hist[257];
-    __syncthreads();
-  }
-  return key2f(prefix);
-}
-
 // tau[q] from the pass-A tile maxima; padded queries get +inf (never emit)
 // (exact mode: slack > 0 lowers tau by two rounding bounds, so that the vectors the fp32 re-rank could still prefer are
 // among the survivors from the first pass on; see prove_kernel)
@@ -607,20 +542,7 @@ __global__ __launch_bounds__(512) void select_kernel(const Survivor *__restrict_
     keys[i] = key;
   }
   __syncthreads();
-  for (uint32_t size = 2; size <= n2; size <<= 1)
-    for (uint32_t str = size >> 1; str > 0; str >>= 1) {
-      for (uint32_t i = threadIdx.x; i < n2 / 2; i += blockDim.x) {
-        uint32_t lo = 2 * i - (i & (str - 1));
-        uint32_t hi = lo + str;
-        bool desc = (lo & size) == 0;
-        unsigned long long x = keys[lo], y = keys[hi];
-        if ((x < y) == desc) {
-          keys[lo] = y;
-          keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  sort_keys_desc(keys, n2);
   const uint32_t m = min(c, (uint32_t)k);
   for (uint32_t i = threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
     float dist = 0.0f;
@@ -741,22 +663,6 @@ __global__ __launch_bounds__(256) void prove_kernel(const Survivor *__restrict__
   }
 }
 
-struct Buf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  ~Buf() { if (p) (void)hipFree(p); }
-  hipError_t reserve(size_t n) {
-    if (n <= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    hipError_t e = hipMalloc(&p, n);
-    if (e == hipSuccess) bytes = n;
-    return e;
-  }
-  template <class T> T *as() const { return (T *)p; }
-};
-
 }  // namespace
 
 struct dann_index {
@@ -849,34 +755,15 @@ __global__ void rank_scatter_kernel(const uint32_t *__restrict__ rpos, int64_t n
   if (r < n) rank[rpos[r]] = (uint32_t)r;
 }
 
-// growth that keeps the first `keep` bytes (device to device); the old buffer goes only once the new one holds them
-hipError_t grow_keep(Buf &b, size_t keep, size_t want) {
-  if (b.p && want <= b.bytes) return hipSuccess;
-  void *p = nullptr;
-  hipError_t e = hipMalloc(&p, want ? want : 8);
-  if (e != hipSuccess) return e;
-  if (keep && b.p) {
-    e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      return e;
-    }
-  }
-  if (b.p) (void)hipFree(b.p);
-  b.p = p;
-  b.bytes = want ? want : 8;
-  return hipSuccess;
-}
-
 // room for cap_pad rows (a multiple of the tile) in every per-row buffer
 int dense_grow(dann_index *ix, int64_t cap_pad) {
   const size_t row_bytes = (size_t)ix->S * 16 * sizeof(_Float16);
-  DTRY(grow_keep(ix->xf, (size_t)ix->n_pad * row_bytes, (size_t)cap_pad * row_bytes));
-  DTRY(grow_keep(ix->bias, (size_t)ix->n_pad * sizeof(float), (size_t)cap_pad * sizeof(float)));
-  if (ix->has_ids) DTRY(grow_keep(ix->ids, (size_t)ix->n * sizeof(int64_t), (size_t)cap_pad * sizeof(int64_t)));
+  DTRY(ix->xf.grow_keep((size_t)ix->n_pad * row_bytes, (size_t)cap_pad * row_bytes));
+  DTRY(ix->bias.grow_keep((size_t)ix->n_pad * sizeof(float), (size_t)cap_pad * sizeof(float)));
+  if (ix->has_ids) DTRY(ix->ids.grow_keep((size_t)ix->n * sizeof(int64_t), (size_t)cap_pad * sizeof(int64_t)));
   if (ix->exact) {
-    DTRY(grow_keep(ix->x32, (size_t)ix->n * ix->d * sizeof(float), (size_t)cap_pad * ix->d * sizeof(float)));
-    DTRY(grow_keep(ix->xss32, (size_t)ix->n * sizeof(float), (size_t)cap_pad * sizeof(float)));
+    DTRY(ix->x32.grow_keep((size_t)ix->n * ix->d * sizeof(float), (size_t)cap_pad * ix->d * sizeof(float)));
+    DTRY(ix->xss32.grow_keep((size_t)ix->n * sizeof(float), (size_t)cap_pad * sizeof(float)));
   }
   ix->cap_pad = std::max(ix->cap_pad, cap_pad);
   return DANN_OK;

@@ -43,22 +43,13 @@
 
 #include "../../include/hnsw_ann.h"
 #include "sann_device.h"  // mix64
-#include "abi_guard.h"
 #include "ann_by_id_internal.h"
+#include "device_buf.h"
+#include "host_error.h"
+#define HTRY(expr) HIP_TRY_AS(HNSW_EDEVICE, expr)
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, HNSW_ENOMEM, HNSW_EINTERNAL); }
 
 namespace {
-
-thread_local std::string g_err;
-int fail(int code, const std::string &m) {
-  g_err = m;
-  return code;
-}
-#define HTRY(expr)                                                                                 \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return fail(HNSW_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 constexpr int MAX_D = 512;
 constexpr int MAX_M = 32;        // lists of <= 2*MAX_M = 64 neighbours: one lane each
@@ -69,25 +60,6 @@ constexpr int CCAP_FIRST = 8192;        // global part of the candidate queue, f
 constexpr int CCAP_GLOBAL = 1 << 17;    // ... of the re-run of a query that outgrew it
 constexpr int64_t VLOG_MIN_VWORDS = 1 << 18;  // bitmaps of at least 1 MB keep an undo log
 constexpr int VLOG_CAP = 1 << 16;       // visited nodes a walk remembers for cleaning up after itself (more: it wipes its whole bitmap)
-
-struct Buf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  ~Buf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  hipError_t reserve(size_t n) {
-    if (n <= bytes && p) return hipSuccess;
-    release();
-    hipError_t e = hipMalloc(&p, n ? n : 8);
-    if (e == hipSuccess) bytes = n ? n : 8;
-    return e;
-  }
-  template <class T> T *as() const { return (T *)p; }
-};
 
 // ---------------------------------------------------------------------------------------------
 // shared host/device pieces: Float.compare and java.util.PriorityQueue
@@ -1271,26 +1243,6 @@ __global__ void hnsw_key_merge_kernel(const int64_t *__restrict__ a, int64_t na,
   }
 }
 
-// Device buffer growth that keeps the first `keep` bytes (device to device) and frees the old buffer only once the new one
-// holds them: a failed growth leaves the buffer as it was.
-hipError_t grow_keep(Buf &b, size_t keep, size_t want) {
-  if (b.p && want <= b.bytes) return hipSuccess;
-  void *p = nullptr;
-  hipError_t e = hipMalloc(&p, want ? want : 8);
-  if (e != hipSuccess) return e;
-  if (keep && b.p) {
-    e = hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      return e;
-    }
-  }
-  if (b.p) (void)hipFree(b.p);
-  b.p = p;
-  b.bytes = want ? want : 8;
-  return hipSuccess;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1723,11 +1675,11 @@ int64_t grown_capacity(const hnsw_index *ix, int64_t need) {
 // the per-row buffers grown to `capacity` rows, device to device; a failed growth leaves the index as it was
 int grow_rows(hnsw_index *ix, int64_t capacity) {
   const int64_t n = ix->n;
-  HTRY(grow_keep(ix->x, (size_t)n * ix->dpad * sizeof(_Float16), (size_t)capacity * ix->dpad * sizeof(_Float16)));
-  HTRY(grow_keep(ix->adj0, (size_t)n * (ix->m0 + 1) * 4, (size_t)capacity * (ix->m0 + 1) * 4));
-  HTRY(grow_keep(ix->upper_slot, (size_t)n * 4, (size_t)capacity * 4));
-  HTRY(grow_keep(ix->levels, 0, (size_t)capacity * 4));
-  if (ix->keyed) HTRY(grow_keep(ix->ids, (size_t)n * 8, (size_t)capacity * 8));
+  HTRY(ix->x.grow_keep((size_t)n * ix->dpad * sizeof(_Float16), (size_t)capacity * ix->dpad * sizeof(_Float16)));
+  HTRY(ix->adj0.grow_keep((size_t)n * (ix->m0 + 1) * 4, (size_t)capacity * (ix->m0 + 1) * 4));
+  HTRY(ix->upper_slot.grow_keep((size_t)n * 4, (size_t)capacity * 4));
+  HTRY(ix->levels.grow_keep(0, (size_t)capacity * 4));
+  if (ix->keyed) HTRY(ix->ids.grow_keep((size_t)n * 8, (size_t)capacity * 8));
   ix->cap = capacity;
   return HNSW_OK;
 }
@@ -1977,8 +1929,8 @@ static int insert_rows(hnsw_index *ix, int64_t n, const float *vectors, const in
   int64_t slots_cap = std::max(ix->upper_slots_cap, old_slots + 1), rows_cap = std::max(ix->upper_rows_cap, std::max<int64_t>(old_rows, 1));
   if (n_slots + 1 > slots_cap) slots_cap = std::max(n_slots + 1, slots_cap + slots_cap / 2);
   if (n_rows > rows_cap) rows_cap = std::max(n_rows, rows_cap + rows_cap / 2);
-  HTRY(grow_keep(ix->upper_base, (size_t)(old_slots + 1) * 4, (size_t)slots_cap * 4));
-  HTRY(grow_keep(ix->upper_adj, (size_t)old_rows * (ix->m + 1) * 4, (size_t)rows_cap * (ix->m + 1) * 4));
+  HTRY(ix->upper_base.grow_keep((size_t)(old_slots + 1) * 4, (size_t)slots_cap * 4));
+  HTRY(ix->upper_adj.grow_keep((size_t)old_rows * (ix->m + 1) * 4, (size_t)rows_cap * (ix->m + 1) * 4));
   ix->upper_slots_cap = slots_cap;
   ix->upper_rows_cap = rows_cap;
   // construction scratch (kept on the handle)
@@ -2462,7 +2414,7 @@ int hnsw_index_reserve(hnsw_index_t *ix, int64_t capacity) try {
   HTRY(hipSetDevice(ix->device));
   if (int rc = grow_rows(ix, capacity)) return rc;
   if (ix->keyed) {
-    if (ix->key_n >= 0) HTRY(grow_keep(ix->key_table, (size_t)ix->key_n * 8, (size_t)capacity * 8));
+    if (ix->key_n >= 0) HTRY(ix->key_table.grow_keep((size_t)ix->key_n * 8, (size_t)capacity * 8));
     HTRY(ix->key_next.reserve((size_t)capacity * 8));
   }
   return HNSW_OK;

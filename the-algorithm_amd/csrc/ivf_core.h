@@ -1,9 +1,10 @@
 // ivf_core.h -- the host side that the two inverted-file indexes (ivf_ann.hip: flat lists; ivfpq_ann.hip: product-quantised
 // lists) share, written once against IvfBase, the fields both index structs hold: row preparation and assignment, the
-// layout of the lists up to the payload scatter, the steps of a search around the scan launch, the select step's sort, the
-// steps of an add and of a restore around the payload, and the exports.  Where the two indexes differ the difference is
-// an argument: the rows of a list block, a payload buffer and its row bytes, or a callable (the payload scatter, the scan
-// launch).  Failures go through the error channel of ivf_error.h.  A source includes this once, as it does ivf_kernels.h;
+// layout of the lists up to the payload scatter, the steps of a search around the scan launch, the select step's key load
+// (the sort itself is survivor_topk.h's), the steps of an add and of a restore around the payload, and the exports.  Where
+// the two indexes differ the difference is an argument: the rows of a list block, a payload buffer and its row bytes, or a
+// callable (the payload scatter, the scan launch).  Failures go through the error channel of ivf_error.h (host_error.h with
+// the IVF_* codes).  A source includes this once, as it does ivf_kernels.h;
 // everything is file-local.  Its host functions instantiate the hipcub sorts and scans, so only the index sources include
 // it (the two above and grouped_ann.hip, whose cell is the caller's group: IvfBase without a coarse quantizer, cell_bits
 // wide enough for its group numbers): opq_ann.hip and refine_ann.hip take ivf_error.h and ivf_kernels.h alone.
@@ -367,8 +368,8 @@ int finish_chunk(IvfBase *ix, int32_t nq, int32_t k, int rounds, float *out_dist
 }
 
 // The select step of query q, one workgroup: its survivors as keys (score desc, rank in id order asc) in `keys`, sorted by
-// a bitonic network -- the order of dense_ann.hip's select.  Returns the number of survivors; keys[i] >> 32 is f2key of the
-// i-th best score, 0xffffffff - (uint32_t)keys[i] its rank.
+// survivor_topk.h's network, the one dense_ann.hip's select runs.  Returns the number of survivors; keys[i] >> 32 is f2key
+// of the i-th best score, 0xffffffff - (uint32_t)keys[i] its rank.
 __device__ __forceinline__ uint32_t select_sorted(const Survivor *__restrict__ surv, const uint32_t *__restrict__ done_cnt,
                                                   const uint32_t *__restrict__ lrank, int q, unsigned long long *keys) {
   const uint32_t c = min(done_cnt[q], (uint32_t)CAP);
@@ -378,25 +379,12 @@ __device__ __forceinline__ uint32_t select_sorted(const Survivor *__restrict__ s
     unsigned long long key = 0;
     if (i < c) {
       Survivor s = surv[(size_t)q * CAP + i];
-      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - lrank[s.slot]);
+      key = ((unsigned long long)f2key(s.score) << 32) | (0xffffffffu - lrank[s.pos]);
     }
     keys[i] = key;
   }
   __syncthreads();
-  for (uint32_t size = 2; size <= n2; size <<= 1)
-    for (uint32_t str = size >> 1; str > 0; str >>= 1) {
-      for (uint32_t i = threadIdx.x; i < n2 / 2; i += blockDim.x) {
-        uint32_t lo = 2 * i - (i & (str - 1));
-        uint32_t hi = lo + str;
-        bool desc = (lo & size) == 0;
-        unsigned long long x = keys[lo], y = keys[hi];
-        if ((x < y) == desc) {
-          keys[lo] = y;
-          keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  sort_keys_desc(keys, n2);
   return c;
 }
 

@@ -1,8 +1,10 @@
 // ivf_kernels.h -- the device side that the two inverted-file indexes (ivf_ann.hip: flat lists; ivfpq_ann.hip:
 // product-quantised lists) share: row preparation, the small bookkeeping kernels of list construction and probe inversion,
-// the survivor buffer's arm / refine kernels with wg_kth_largest, and the device buffer Buf.  The host code that launches
-// them is ivf_core.h, which includes this; opq_ann.hip and refine_ann.hip use the row preparation.  A source includes this
-// once.  Everything is file-local.
+// and the survivor buffer's arm / refine kernels.  The survivor buffer itself (Survivor, CAP, f2key, wg_kth_largest, the
+// select step's sort) comes from survivor_topk.h, which dense_ann.hip shares, and the device buffer Buf from device_buf.h;
+// both reach the sources below through this header.  The host code that launches the kernels is ivf_core.h, which
+// includes this; opq_ann.hip and refine_ann.hip use the row preparation.  A source includes this once.  Everything is
+// file-local.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,39 +13,19 @@
 
 #include "../../include/ivf_ann.h"
 #include "ann_by_id_internal.h"
+#include "device_buf.h"
+#include "survivor_topk.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float16v __attribute__((ext_vector_type(16)));
-
-constexpr int CAP = 8192;  // survivors kept per query
-constexpr int MAX_K = 1024;
-constexpr int MAX_D = 512;
 constexpr int MAX_NLIST = 65536;
 constexpr int MAX_NPROBE = 1024;
 constexpr int CHUNK = ann_by_id::DANN_CHUNK;  // queries (or rows to assign) per coarse search
 constexpr int CELL_BITS = 17;                 // radix-sort key width of a cell number
 
-struct Survivor {
-  float score;
-  uint32_t slot;
-};
 struct Group {
   uint32_t cell, p0, count;  // the queries of the group: pairs [p0, p0 + count) of the probe table sorted by cell
 };
-
-__device__ __forceinline__ uint32_t f2key(float f) {  // order-preserving float -> uint
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // rows (fp32, row-major) -> fp16 rows (row-major) and the sum of squares of the stored halves.  One wave per row; the
@@ -170,37 +152,6 @@ __global__ void groups_kernel(const uint32_t *__restrict__ per_cell, const uint3
   atomicAdd(rows_scanned, (unsigned long long)cnt * sizes[c]);
 }
 
-// k-th largest of n floats (stride in floats), one workgroup, 4 radix passes over an LDS histogram (as dense_ann.hip)
-__device__ float wg_kth_largest(const float *vals, int64_t n, int stride, int k, uint32_t *hist /*[258]*/) {
-  uint32_t prefix = 0, mask = 0;
-  uint32_t want = (uint32_t)k;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-      uint32_t key = f2key(vals[i * stride]);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t acc = 0;
-      int dgt = 255;
-      for (; dgt > 0; --dgt) {
-        if (acc + hist[dgt] >= want) break;
-        acc += hist[dgt];
-      }
-      hist[256] = (uint32_t)dgt;
-      hist[257] = want - acc;
-    }
-    __syncthreads();
-    prefix |= hist[256] << shift;
-    mask |= 255u << shift;
-    want = hist[257];
-    __syncthreads();
-  }
-  return key2f(prefix);
-}
-
 // after a scan round: a query whose candidates fitted is finished (tau = +inf); one that overflowed is re-armed with the
 // k-th largest buffered score.  flags: 1 = another round, 2 = cannot tighten (more than CAP scores tie at the k-th).
 __global__ void refine_kernel(float *__restrict__ tau, uint32_t *__restrict__ cnt, uint32_t *__restrict__ done_cnt,
@@ -236,45 +187,6 @@ __global__ void arm_kernel(float *__restrict__ tau, uint32_t *__restrict__ cnt, 
   cnt[q] = 0;
   done_cnt[q] = 0xffffffffu;
 }
-
-struct Buf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  ~Buf() { if (p) (void)hipFree(p); }
-  hipError_t reserve(size_t n) {
-    if (n <= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    hipError_t e = hipMalloc(&p, n ? n : 8);
-    if (e == hipSuccess) bytes = n ? n : 8;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  // growth that keeps the first `keep` bytes (device to device)
-  hipError_t grow_keep(size_t keep, size_t want) {
-    if (p && want <= bytes) return hipSuccess;
-    void *np = nullptr;
-    hipError_t e = hipMalloc(&np, want ? want : 8);
-    if (e != hipSuccess) return e;
-    if (keep && p) {
-      e = hipMemcpy(np, p, keep, hipMemcpyDeviceToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(np);
-        return e;
-      }
-    }
-    if (p) (void)hipFree(p);
-    p = np;
-    bytes = want ? want : 8;
-    return hipSuccess;
-  }
-  template <class T> T *as() const { return (T *)p; }
-};
 
 inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
