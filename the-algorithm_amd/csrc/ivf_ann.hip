@@ -219,8 +219,10 @@ int build_coarse(ivf_index *ix, const float *d_cent, bool stored = false) {
   return IVF_OK;
 }
 
-int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
-                 int64_t *out_ids, int32_t *out_counts) {
+// One chunk of a search.  out_on_device: out_dist / out_ids / out_counts are device buffers, which the select launch writes
+// itself; otherwise it writes the index's own and finish_chunk brings them to the host.
+int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
+                 float *out_dist, int64_t *out_ids, int32_t *out_counts, bool out_on_device) {
   const int d = ix->d, S = d >> 4, nlist = ix->nlist;
   hipStream_t st = 0;
   const int nq_pad = (nq + 31) / 32 * 32;
@@ -229,7 +231,7 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, in
   ITRY(ix->ngrp.reserve((size_t)nlist * 4));
   ITRY(ix->gstart.reserve((size_t)nlist * 4));
   _Float16 *q16 = ix->qf.as<_Float16>(), *qfrag = q16 + (size_t)nq_pad * d;
-  if (int rc = probe_chunk(ix, q0, nq, queries, false, k, nprobe, q16, qfrag)) return rc;
+  if (int rc = probe_chunk(ix, q0, nq, queries, on_device, k, nprobe, q16, qfrag)) return rc;
 
   // the pairs of a cell cut into groups of <= 32 queries
   hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), nlist, 32u,
@@ -241,6 +243,7 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, in
   ITRY(hipMemcpy(&last[0], ix->gstart.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
   ITRY(hipMemcpy(&last[1], ix->ngrp.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
   const uint32_t n_groups = last[0] + last[1];
+  ix->last_ctl += 8;
   ITRY(ix->groups.reserve((size_t)n_groups * sizeof(Group)));
   hipLaunchKernelGGL(groups_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), ix->pstart.as<uint32_t>(),
                      ix->gstart.as<uint32_t>(), ix->sizes.as<uint32_t>(), nlist, ix->groups.as<Group>(),
@@ -272,9 +275,22 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, in
 
   hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(512), SELECT_LDS, st, ix->surv.as<Survivor>(), ix->done_cnt.as<uint32_t>(),
                      ix->qsumsq.as<float>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
-                     ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
+                     out_on_device ? out_dist : ix->o_dist.as<float>(), out_on_device ? out_ids : ix->o_ids.as<int64_t>(),
+                     out_on_device ? out_counts : ix->o_cnt.as<int32_t>());
   ITRY(hipGetLastError());
+  if (out_on_device) return finish_chunk(ix, nq, k, rounds, nullptr, nullptr, nullptr);
   return finish_chunk(ix, nq, k, rounds, out_dist, out_ids, out_counts);
+}
+
+// ivf_search, over host queries into host buffers or over device queries into device buffers
+int search_rows(ivf_index *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist, int64_t *out_ids,
+                int32_t *out_counts, bool on_device) {
+  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+  if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
+  return search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
+    return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, out_dist + (size_t)q0 * k,
+                        out_ids + (size_t)q0 * k, out_counts + q0, on_device);
+  });
 }
 
 // ivf_index_train, over host rows or over rows that are on the device
@@ -336,6 +352,14 @@ int ivf_internal::train_device(int32_t device, int32_t metric, int32_t d, int32_
                                int32_t niter, uint64_t seed, ivf_index **out) try {
   return train_rows(device, metric, d, nlist, n_train, d_rows, true, niter, seed, out);
 } ABI_CATCH
+
+int ivf_internal::search_device_out(ivf_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *d_dist,
+                                    int64_t *d_ids, int32_t *d_counts) try {
+  return search_rows(ix, nq, d_queries, k, nprobe, d_dist, d_ids, d_counts, true);
+} ABI_CATCH
+
+int ivf_internal::device_of(const ivf_index *ix) { return ix->device; }
+int64_t ivf_internal::last_control_bytes(const ivf_index *ix) { return ix->last_ctl; }
 
 // ---------------------------------------------------------------------------------------------
 // restoring a saved index (faiss_restore.h)
@@ -428,12 +452,7 @@ int ivf_index_add(ivf_index_t *ix, int64_t n, const float *vectors, const int64_
 
 int ivf_search(ivf_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist, int64_t *out_ids,
                int32_t *out_counts) try {
-  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
-  if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
-  return search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
-    return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, k, nprobe, out_dist + (size_t)q0 * k, out_ids + (size_t)q0 * k,
-                        out_counts + q0);
-  });
+  return search_rows(ix, nq, queries, k, nprobe, out_dist, out_ids, out_counts, false);
 } ABI_CATCH
 
 int ivf_index_info(const ivf_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist) try {

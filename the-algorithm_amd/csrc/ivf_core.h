@@ -55,6 +55,7 @@ struct IvfBase {
   Buf probes;
   int32_t last_nq = 0, last_nprobe = 0, last_rounds = 0;
   int64_t last_rows = 0;
+  int64_t last_ctl = 0;  // control bytes the search read back: round flags, row and group counts (never an answer)
   float t_coarse = 0, t_scan = 0, t_sel = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   RestoreState rs;  // faiss_restore.h
@@ -247,6 +248,7 @@ int search_begin(IvfBase *ix, int32_t nq, int32_t k, int32_t *nprobe) {
   ix->last_nprobe = *nprobe;
   ix->last_rows = 0;
   ix->last_rounds = 0;
+  ix->last_ctl = 0;
   ix->t_coarse = ix->t_scan = ix->t_sel = 0;
   return IVF_OK;
 }
@@ -304,6 +306,7 @@ int probe_chunk(IvfBase *ix, int32_t q0, int32_t nq, const float *queries, bool 
   int64_t d2h = 0;
   DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, nq, nprobe, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
                                               ix->c_cnt.as<int32_t>(), &d2h));
+  ix->last_ctl += d2h;
 
   // inversion: (cell, query) pairs sorted by cell
   ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
@@ -334,6 +337,7 @@ int scan_rounds(IvfBase *ix, int32_t nq, int32_t k, Launch launch, int *rounds) 
     ITRY(hipGetLastError());
     ITRY(hipMemcpyAsync(&flags, ix->flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
     ITRY(hipStreamSynchronize(st));
+    ix->last_ctl += (int64_t)sizeof(int);
     if (flags & 2) return fail(IVF_ELIMIT, "more than 8192 rows of the probed lists tie at the k-th distance of a query");
     if (*rounds >= 16) return fail(IVF_ELIMIT, "threshold refinement did not converge");
     if (!(flags & 1)) break;
@@ -343,7 +347,8 @@ int scan_rounds(IvfBase *ix, int32_t nq, int32_t k, Launch launch, int *rounds) 
 }
 
 // The last step of a chunk, after the select launch (event 3): with out_dist != NULL the answers of o_dist / o_ids / o_cnt
-// go to the host; the rows scanned and the three phase times are added to the stats of the search.
+// go to the host (a search whose answer stays on the device -- ivf_device_rows.h's search_device_out -- passes NULL: its
+// select launch wrote to the caller's device buffers); the rows scanned and the three phase times are added to the stats of the search.
 int finish_chunk(IvfBase *ix, int32_t nq, int32_t k, int rounds, float *out_dist, int64_t *out_ids, int32_t *out_counts) {
   hipStream_t st = 0;
   ITRY(hipEventRecord(ix->ev[3], st));
@@ -363,6 +368,7 @@ int finish_chunk(IvfBase *ix, int32_t nq, int32_t k, int rounds, float *out_dist
   ix->t_scan += ts;
   ix->t_sel += tl;
   ix->last_rows += (int64_t)rows;
+  ix->last_ctl += 8;
   ix->last_rounds = std::max(ix->last_rounds, rounds + 1);
   return IVF_OK;
 }

@@ -19,6 +19,15 @@ namespace ivf_internal __attribute__((visibility("hidden"))) {
 int train_device(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64_t n_train, const float *d_rows, int32_t niter,
                  uint64_t seed, ivf_index **out);
 
+// ivf_search over queries that are on the device, the answer left in the caller's device buffers d_dist / d_ids [nq][k] and
+// d_counts [nq] by the select launch itself (slots past a count are zeros, as ivf_search leaves them): nothing but control
+// words (round flags, the rows counter, the two group counts) leaves the device.  The bytes are ivf_search's.
+int search_device_out(ivf_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *d_dist, int64_t *d_ids,
+                      int32_t *d_counts);
+int device_of(const ivf_index *ix);
+// the control bytes the last search read back (answers not counted)
+int64_t last_control_bytes(const ivf_index *ix);
+
 }  // namespace ivf_internal
 
 namespace ivfpq_internal __attribute__((visibility("hidden"))) {
@@ -47,6 +56,11 @@ int search_device(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k
 // ivfpq_search_ht (polysemous_ann.h) over queries that are on the device; ht <= 0 is search_device.
 int search_device_ht(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht, float *out_dist,
                      int64_t *out_ids, int32_t *out_counts);
+
+// search_device_ht with the answer left in the caller's device buffers, as ivf_internal::search_device_out leaves it.
+int search_device_out(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht, float *d_dist,
+                      int64_t *d_ids, int32_t *d_counts);
+int64_t last_control_bytes(const ivfpq_index *ix);
 
 // After a search_device that stood in for a search with ht <= 0: every scanned row counts as scored (ivfpq_last_ht_stats).
 int search_stats_unfiltered(ivfpq_index *ix);
@@ -82,5 +96,11 @@ int64_t slab_rows(const opq_index *ix);
 // ivfpq_internal::search_positions over device queries [nq][d_in], which are prepared and transformed first.
 int search_positions(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t *d_pos,
                      uint32_t *d_rank, int32_t *d_counts);
+// opq_search_ht over device queries [nq][d_in] (prepared and transformed on the device, no staging copy), the answer left
+// in the caller's device buffers as ivf_internal::search_device_out leaves it.
+int search_device_out(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht, float *d_dist,
+                      int64_t *d_ids, int32_t *d_counts);
+int device_of(const opq_index *ix);
+int64_t last_control_bytes(const opq_index *ix);
 
 }  // namespace opq_internal

@@ -567,8 +567,10 @@ int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq,
   return IVF_OK;
 }
 
+// One chunk of a search.  out_on_device (without po): out_dist / out_ids / out_counts are device buffers, which the select
+// launch writes itself; otherwise it writes the index's own and finish_chunk brings them to the host.
 int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
-                 float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po, int32_t ht) {
+                 float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po, int32_t ht, bool out_on_device) {
   const int d = ix->d, nlist = ix->nlist;
   const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
@@ -625,11 +627,12 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
   } else {
     hipLaunchKernelGGL(pq_select_kernel<false>, dim3(nq), dim3(512), SELECT_LDS, st, ix->surv.as<Survivor>(),
                        ix->done_cnt.as<uint32_t>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
-                       ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>(), (const uint32_t *)nullptr,
-                       (int32_t *)nullptr, (uint32_t *)nullptr);
+                       out_on_device ? out_dist : ix->o_dist.as<float>(), out_on_device ? out_ids : ix->o_ids.as<int64_t>(),
+                       out_on_device ? out_counts : ix->o_cnt.as<int32_t>(), (const uint32_t *)nullptr, (int32_t *)nullptr,
+                       (uint32_t *)nullptr);
   }
   ITRY(hipGetLastError());
-  return finish_chunk(ix, nq, k, rounds, po ? nullptr : out_dist, out_ids, out_counts);
+  return finish_chunk(ix, nq, k, rounds, po || out_on_device ? nullptr : out_dist, out_ids, out_counts);
 }
 
 // ivfpq_index_train, over host rows or over rows that are on the device
@@ -729,9 +732,9 @@ int train_rows_polysemous(int32_t device, int32_t metric, int32_t d, int32_t nli
   return IVF_OK;
 }
 
-// ivfpq_search, over host queries or over queries that are on the device
+// ivfpq_search, over host queries or over queries that are on the device; out_on_device: the three outputs are device buffers
 int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe, float *out_dist,
-                int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr, int32_t ht = 0) {
+                int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr, int32_t ht = 0, bool out_on_device = false) {
   if (!ix || !queries) return fail(IVF_EINVAL, "null argument");
   if (po ? !po->pos || !po->rank || !po->cnt : !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
   if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
@@ -744,12 +747,13 @@ int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_dev
   }
   if (int rc = search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
         return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, po ? nullptr : out_dist + (size_t)q0 * k,
-                            po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po, ht);
+                            po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po, ht, out_on_device);
       }))
     return rc;
   if (ht > 0) {
     unsigned long long scored = 0;
     ITRY(hipMemcpy(&scored, ix->scored_acc.p, 8, hipMemcpyDeviceToHost));
+    ix->last_ctl += 8;
     ix->last_scored = (int64_t)scored;
     ix->qc_nq = nq;
     ix->qc_nprobe = nprobe;
@@ -823,6 +827,15 @@ int ivfpq_internal::search_device_ht(ivfpq_index *ix, int32_t nq, const float *d
   if (ht <= 0) ix->last_scored = ix->last_rows;
   return IVF_OK;
 } ABI_CATCH
+
+int ivfpq_internal::search_device_out(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht,
+                                      float *d_dist, int64_t *d_ids, int32_t *d_counts) try {
+  if (int rc = search_rows(ix, nq, d_queries, true, k, nprobe, d_dist, d_ids, d_counts, nullptr, std::max(ht, 0), true)) return rc;
+  if (ht <= 0) ix->last_scored = ix->last_rows;
+  return IVF_OK;
+} ABI_CATCH
+
+int64_t ivfpq_internal::last_control_bytes(const ivfpq_index *ix) { return ix->last_ctl; }
 
 int ivfpq_internal::search_stats_unfiltered(ivfpq_index *ix) {
   if (!ix) return fail(IVF_EINVAL, "null index");

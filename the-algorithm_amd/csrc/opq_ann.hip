@@ -518,8 +518,9 @@ int opq_internal::add_slab(opq_index *ix, int64_t r0, int64_t m, const float *d_
   return IVF_OK;
 } ABI_CATCH
 
-int opq_internal::search_positions(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t *d_pos,
-                                   uint32_t *d_rank, int32_t *d_counts) try {
+namespace {
+// the first half of a search over device queries [nq][d_in]: prepared and transformed where they lie into ix->y, timed
+int transform_queries(opq_index *ix, const float *d_queries, int32_t nq) {
   if (!ix || !d_queries) return fail(IVF_EINVAL, "null argument");
   if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
   ITRY(hipSetDevice(ix->device));
@@ -532,9 +533,26 @@ int opq_internal::search_positions(opq_index *ix, int32_t nq, const float *d_que
   float ms = 0;
   (void)hipEventElapsedTime(&ms, ix->ev[0], ix->ev[1]);
   ix->t_transform += ms;
+  return IVF_OK;
+}
+}  // namespace
+
+int opq_internal::search_positions(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t *d_pos,
+                                   uint32_t *d_rank, int32_t *d_counts) try {
+  if (int rc = transform_queries(ix, d_queries, nq)) return rc;
   PCALL(ivfpq_internal::search_positions(ix->inner, nq, ix->y.as<float>(), k, nprobe, d_pos, d_rank, d_counts));
   return IVF_OK;
 } ABI_CATCH
+
+int opq_internal::search_device_out(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht,
+                                    float *d_dist, int64_t *d_ids, int32_t *d_counts) try {
+  if (int rc = transform_queries(ix, d_queries, nq)) return rc;  // (the inner search checks k, nprobe and the outputs)
+  PCALL(ivfpq_internal::search_device_out(ix->inner, nq, ix->y.as<float>(), k, nprobe, ht, d_dist, d_ids, d_counts));
+  return IVF_OK;
+} ABI_CATCH
+
+int opq_internal::device_of(const opq_index *ix) { return ix->device; }
+int64_t opq_internal::last_control_bytes(const opq_index *ix) { return ivfpq_internal::last_control_bytes(ix->inner); }
 
 namespace {
 int train_index(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, int32_t nlist, int32_t M, int64_t n_train,

@@ -18,11 +18,12 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import dense_ann, opq_ann
+from . import dense_ann, opq_ann, polysemous_ann
 from .dense_ann import DistanceMetric
 from .ivf_ann import FaissIvfFlat, FaissQueryable, IvfError, _rows
 from .ivfpq_ann import KSUB, FaissIvfPq
 from .opq_ann import FaissOpqIvfPq
+from .shard_set import ShardSet
 from .simclusters_ann import load_library
 
 _P = C.POINTER
@@ -267,15 +268,19 @@ class HourlyShardedIndex:
     """HourlyShardedIndex.scala: the newest shards_to_load hourly directories under root, served as one index.  reload(now)
     is the body of the reference's task() (:66-93); the timer that calls it every shardWatchInterval is the caller's.
     Loaded shards are kept by directory as MemoizedInEpochs keeps them: an unchanged set reloads nothing, a changed one
-    reads only the new directories and closes the dropped ones.  search() asks every shard for k and merges by
-    (distance, id) with dann_compose_shards; ids pass through as they are and duplicates across shards are kept, as
-    IndexShards(d, threaded = false, successive_ids = false) does.  FaissQueryable works over it unchanged."""
+    reads only the new directories and closes the dropped ones.  search() goes through a ShardSet (shard_set.h) that holds
+    the shards being served: the queries go up once, every shard searches them on the device and its answer is folded
+    there into the best k by (distance, id); ids pass through as they are and duplicates across shards are kept, as
+    IndexShards(d, threaded = false, successive_ids = false) does.  search_composed() is the same answer, byte for byte,
+    by the host: every shard's own search, then dann_compose_shards.  FaissQueryable and, with ht,
+    polysemous_ann.PolysemousFaissQueryable work over it unchanged."""
 
     def __init__(self, metric: DistanceMetric, dimension: int, root, shards_to_load: int, lookback_interval: int, *, device: int = 0):
         self.metric, self.dimension, self.root = DistanceMetric(metric), int(dimension), os.fspath(root)
         self.shards_to_load, self.lookback_interval, self.device = int(shards_to_load), int(lookback_interval), device
         self._shards: Dict[str, object] = {}
         self._order: List[str] = []
+        self._set: Optional[ShardSet] = None  # made by the first reload that changes the set
         self._started = False  # a reload has found a shard (the reference's castedIndex != null)
         self.loads = 0    # directories read since construction
         self.closes = 0   # shards closed since construction
@@ -302,6 +307,9 @@ class HourlyShardedIndex:
                         shards[directory] = load_native_index(self.dimension, self.metric, directory, device=self.device)
                         new.append(shards[directory])
                         self.loads += 1
+                if self._set is None:
+                    self._set = ShardSet.create(self.metric, self.dimension, device=self.device)
+                self._set.set_members([shards[d] for d in fresh])  # (the body of the reference's replaceIndex)
             except Exception:
                 for s in new:
                     s.close()
@@ -317,15 +325,35 @@ class HourlyShardedIndex:
             raise RuntimeError("requirement failed: Failed to find any shards during startup")
         return changed
 
-    def search(self, queries: np.ndarray, k: int, nprobe: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def search(self, queries: np.ndarray, k: int, nprobe: int, ht: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The shards' answers merged on the device (ShardSet.search).  ht > 0 is the Hamming filter of IVF-PQ and OPQ
+        shards; IVF-Flat shards refuse it."""
+        if not self._started:
+            raise RuntimeError("no shard was ever loaded: call reload() first")
+        return self._set.search(_rows(queries, self.dimension), k, nprobe, ht)
+
+    def search_composed(self, queries: np.ndarray, k: int, nprobe: int, ht: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """search() by the host: every shard's own search from host memory, merged by dann_compose_shards."""
         if not self._started:
             raise RuntimeError("no shard was ever loaded: call reload() first")
         q = _rows(queries, self.dimension)
         if not self._order:  # an empty IndexShards: nothing to find
             return np.zeros((q.shape[0], k), np.int64), np.zeros((q.shape[0], k), np.float32), np.zeros(q.shape[0], np.int32)
-        return dense_ann.compose([self._shards[d].search(q, k, nprobe) for d in self._order], k)
+        shards = [self._shards[d] for d in self._order]
+        if ht > 0:
+            return dense_ann.compose([polysemous_ann.search_ht(s, q, k, nprobe, ht) for s in shards], k)
+        return dense_ann.compose([s.search(q, k, nprobe) for s in shards], k)
+
+    def last_stats(self) -> dict:
+        """ShardSet.last_stats of the last search(): bus bytes and the search / fold split."""
+        if self._set is None:
+            raise RuntimeError("no shard was ever loaded: call reload() first")
+        return self._set.last_stats()
 
     def close(self) -> None:
+        if self._set is not None:
+            self._set.close()
+            self._set = None
         for s in self._shards.values():
             s.close()
             self.closes += 1

@@ -110,11 +110,31 @@ def renumber(codebooks: np.ndarray, perms: np.ndarray) -> np.ndarray:
     return out
 
 
+def search_ht(index, queries: np.ndarray, k: int, nprobe: int, ht: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """ivfpq_search_ht / opq_search_ht over the handle of a FaissIvfPq / FaissOpqIvfPq or of its Polysemous twin; the handle
+    stays with its holder."""
+    if isinstance(index, FaissOpqIvfPq):
+        prefix, d = "opq", index.d_in
+    elif isinstance(index, FaissIvfPq):
+        prefix, d = "ivfpq", index.d
+    else:
+        raise TypeError(f"{type(index).__name__} has no product-quantiser codes to filter by")
+    lib = _lib()
+    q = _rows(queries, d)
+    nq = q.shape[0]
+    dist = np.zeros((nq, k), np.float32)
+    ids = np.zeros((nq, k), np.int64)
+    cnt = np.zeros(nq, np.int32)
+    fn = getattr(lib, prefix + "_search_ht")
+    _check(lib, fn(index._h, nq, q.ctypes.data, k, nprobe, int(ht), dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data),
+           getattr(lib, prefix + "_last_error"))
+    return ids, dist, cnt
+
+
 class _HtSearch:
     """search(queries, k, nprobe, ht) and the exports of the last filtered search, over the handle of either index type."""
 
     _prefix = ""
-    _d_query = "d"
 
     def _last_error(self, lib):
         return getattr(lib, self._prefix + "_last_error")
@@ -122,16 +142,7 @@ class _HtSearch:
     def search(self, queries: np.ndarray, k: int, nprobe: int, ht: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(ids [nq, k], distances [nq, k], counts [nq]) of the rows whose code is at Hamming distance < ht from the query
         code of their (query, cell) pair; ht <= 0: the unfiltered search."""
-        lib = _lib()
-        q = _rows(queries, getattr(self, self._d_query))
-        nq = q.shape[0]
-        dist = np.zeros((nq, k), np.float32)
-        ids = np.zeros((nq, k), np.int64)
-        cnt = np.zeros(nq, np.int32)
-        fn = getattr(lib, self._prefix + "_search_ht")
-        _check(lib, fn(self._h, nq, q.ctypes.data, k, nprobe, int(ht), dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data),
-               self._last_error(lib))
-        return ids, dist, cnt
+        return search_ht(self, queries, k, nprobe, ht)
 
     def last_query_codes(self) -> np.ndarray:
         """The query codes of the last search with ht > 0, in the order of last_probes(): uint8 [nq, nprobe, M]."""
@@ -186,7 +197,6 @@ class PolysemousOpqIvfPq(_HtSearch, FaissOpqIvfPq):
     """FaissOpqIvfPq with polysemous training of the inner index and the filtered search."""
 
     _prefix = "opq"
-    _d_query = "d_in"
 
     @classmethod
     def train(cls, metric: DistanceMetric, nlist: int, M: int, d_out: int, train_vectors: np.ndarray, *, niter: int = 0,
