@@ -208,9 +208,11 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
   constexpr int FBLOOM_WORDS = BW >= 11 ? 64 : 256;  // (beside the 16 KB Bloom filter: 64, so that eight workgroups fit a CU)
   constexpr int FB = BW >= 11 ? 6 : 8;
   constexpr int MCAP = (WG * U <= 1024) ? 64 : 128;
+  constexpr int SHORT_NM = 12;  // match lists up to here are settled by every wave for itself; the sorted path starts above
   __shared__ unsigned long long s_bloom[BLOOM_ALLOC];
-  __shared__ uint32_t s_begin[NS];
-  __shared__ uint32_t s_pre[NS];
+  // posting j of the unit (flat index) lies at s_off[cluster of j] + j: the sub-list's start in the index MINUS the
+  // postings of the unit in front of it (mod 2^32).  The two are only ever used as this difference.
+  __shared__ uint32_t s_off[NS];
   __shared__ uint8_t s_map[WG * U];  // flat posting index -> cluster sequence number
   __shared__ double s_w[NS];
   __shared__ float s_w32[NS];
@@ -281,8 +283,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
       uint32_t nxt = last ? 0u : d[c + 1].y;
       if (part == 0) {
         const double w = wq[c];
-        s_begin[c] = v.x;
-        s_pre[c] = v.y;
+        s_off[c] = v.x - v.y;
         s_w[c] = w;
         s_w32[c] = (float)w;
         s_wkey[c] = cosine_cluster_key(h.alg, w, inv_l2_32);
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
   const bool overflow_T = overflow && !overflow_n;
   __syncthreads();
   STAMP(1);  // descriptors + map done
-  ABLATE(6, (unsigned long long)T + s_map[tid] + s_begin[tid & (NS - 1)] + s_pre[tid & (NS - 1)] + s_wkey[tid & (NS - 1)] + (unsigned long long)s_w[tid & (NS - 1)]);
+  ABLATE(6, (unsigned long long)T + s_map[tid] + s_off[tid & (NS - 1)] + s_wkey[tid & (NS - 1)] + (unsigned long long)s_w[tid & (NS - 1)]);
 
   // entries a unit must offer before it may withhold the rest (unit_kl), and the size up to which it simply offers
   // everything
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
         const uint32_t jj = j < Tg ? j : Tg - 1;
         const int c = (int)s_map[jj];
         seq[u] = (j < Tg) ? c : -1;
-        const Posting *src = ix.postings + (s_begin[c] + (jj - s_pre[c]));
+        const Posting *src = ix.postings + (s_off[c] + jj);
         asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(raw[u]) : "v"(src) : "memory");
       }
     STAMP(2);  // posting loads issued
@@ -388,7 +389,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
           nrm32[u] = 1.f;
           if (use_norms) {
             const int c = have ? seq[u] : 0;
-            const double nrm = have ? ix.norms[s_begin[c] + ((uint32_t)(u * WG + tid) - s_pre[c])] : 0.0;
+            const double nrm = have ? ix.norms[s_off[c] + (uint32_t)(u * WG + tid)] : 0.0;
             nrm32[u] = (float)nrm;
             keep_n = keep && nrm > 0.0;  // tweets_ann.sql:14  HAVING norm > 0.0
           }
@@ -437,39 +438,50 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
 
   // ---- 3b. resolve flagged ids ------------------------------------------------------------------
   // Every posting whose bits are all set in the flagged filter (the flagged posting itself, the
-  // earlier postings of the same tweet, and a few hash collisions) joins the match list M; one
-  // thread per M entry then settles its group by comparing ids inside M only.
+  // earlier postings of the same tweet, and a few hash collisions) joins the match list M; its
+  // groups are then settled by comparing ids inside M only: behind ONE barrier when M is short.
+  // CTL_LIVE counts the live POSTINGS and is final here; the postings that fold into a representative are counted apart
+  // (CTL_FOLD), by whoever settles the match list: the unit's live tweets are live_tweets() = CTL_LIVE - CTL_FOLD.
+  auto live_tweets = [&]() { return s_ctl[CTL_LIVE] - s_ctl[CTL_FOLD]; };
   if (!overflow && s_ctl[CTL_NFLAG] != 0) {
     // a flagged unit (one in five at the benchmark's shape: tweets met in two of the scanned clusters) looks its
     // postings' hashes up in the flagged filter; only the few that match fetch their posting again (from L2) -- every
     // unit carrying the 16-byte postings through the whole kernel cost more registers than the kernel has.  (Until
     // round 2 ALL postings of a flagged unit were fetched and hashed again: 40 % of the flagged unit's extra time.)
     int mi[U];
-    Posting pm[U];
+    // A hit's place in the match list and its cluster depend on nothing the re-fetched posting brings: they are settled
+    // right behind the fetch's issue, so the atomic's LDS round trip runs under the posting's trip to L2, and the wait for
+    // the posting stands behind them.  Up to six slots a thread's fetches also share ONE trip: the postings wait in
+    // registers (four per slot) while the slots behind them issue theirs.  The wider geometries have no registers for
+    // that below their occupancy step and finish each hit where it was found (two hits in one thread: two trips).
+    constexpr bool ONE_TRIP = U <= 6;
+    Posting pm[ONE_TRIP ? U : 1];
+    auto list_entry = [&](int m, int u, const Posting &pv) {
+      s_Mid[m] = pv.id;
+      s_Msc[m] = pv.score;
+      if constexpr (NORMS) s_Mnrm[m] = use_norms ? ix.norms[s_off[seq[u]] + (uint32_t)(u * WG + tid)] : 0.0;
+    };
 #pragma unroll
-    for (int u = 0; u < U; u++) {  // (all of a thread's fetches in one trip)
+    for (int u = 0; u < U; u++) {
       const uint32_t hv = hsh[u];
       const unsigned long long bits = bloom_bits(hv);
       const bool hit = seq[u] >= 0 && (s_fbloom[hv >> (HB - FB)] & bits) == bits;
-      mi[u] = hit ? 0 : -1;
-      pm[u] = Posting{0, 0.0};
+      mi[u] = -1;
+      if constexpr (ONE_TRIP) pm[u] = Posting{0, 0.0};
       if (hit) {
         const int c = seq[u];
-        pm[u] = ix.postings[s_begin[c] + ((uint32_t)(u * WG + tid) - s_pre[c])];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      if (mi[u] >= 0) {
-        const int c = seq[u];
+        const Posting pv = ix.postings[s_off[c] + (uint32_t)(u * WG + tid)];
         const int m = atomicAdd(&s_ctl[CTL_NM], 1);
         mi[u] = m;
-        if (m < MCAP) {
-          s_Mid[m] = pm[u].id;
-          s_Mseq[m] = c;
-          s_Msc[m] = pm[u].score;
-          if constexpr (NORMS) s_Mnrm[m] = use_norms ? ix.norms[s_begin[c] + ((uint32_t)(u * WG + tid) - s_pre[c])] : 0.0;
-        }
+        if (m < MCAP) s_Mseq[m] = c;
+        if constexpr (ONE_TRIP) pm[u] = pv;
+        else if (m < MCAP) list_entry(m, u, pv);
+      }
+    }
+    if constexpr (ONE_TRIP) {
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        if (mi[u] >= 0 && mi[u] < MCAP) list_entry(mi[u], u, pm[u]);
       }
     }
     __syncthreads();
@@ -478,63 +490,119 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
     if (nm > MCAP) {
       overflow = true;
       if (tid == 0) s_ctl[CTL_BAD] = 8;  // (diagnostics: the match list overflowed)
-    } else if (nm > 12 && nm <= 64) {
-      // A duplicate-heavy corpus (1M tweets under 144k clusters: every unit, 40-60 entries): the entries are SORTED by
-      // (tweet id, cluster sequence) in wave 0's registers -- groups become runs of neighbouring lanes, a run's first
-      // lane is its representative and walks the run for its sums (ascending cluster sequence: the reference's order).
-      // The pairwise comparison below costs nm^2 dependent LDS reads: 18 k of such a unit's 40 k cycles.
-      if (tid < 64) {
-        const bool have = tid < nm;
-        uint64_t kh = have ? id_key(s_Mid[tid]) : 0ull;  // descending id_key = ascending id
-        uint64_t kl = have ? ~(uint64_t)(((uint32_t)s_Mseq[tid] << 6) | (uint32_t)tid) : 0ull;  // (never 0 for an entry)
-        wave_sort_desc_k128(kh, kl);
-        const bool live = (kh | kl) != 0ull;
-        const uint32_t pk = (uint32_t)~kl;  // cluster sequence << 6 | entry
-        const int ee = (int)(pk & 63u);
-        const uint64_t prev = __shfl_up((unsigned long long)kh, 1, 64);
-        const bool start = live && (tid == 0 || prev != kh);
-        const unsigned long long sm = __ballot(start);
-        const int n_ent = __popcll(__ballot(live));
-        const unsigned long long above = tid == 63 ? 0ull : (sm >> (tid + 1));
-        const int len = start ? (above != 0ull ? __ffsll((long long)above) : n_ent - tid) : 0;
-        const int role = !live ? 0 : (start ? (len >= 2 ? 1 : 0) : 2);
-        const int max_len = (int)wave_max_u32((uint32_t)len);
-        double dot = 0.0, nsq = 0.0;
-        for (int j = 0; j < max_len; j++) {  // (uniform)
-          const uint32_t pj = (uint32_t)__shfl((int)pk, tid + j < 64 ? tid + j : 63, 64);
-          if (role == 1 && j < len) {
-            const double bs = s_Msc[pj & 63u];
-            dot = dot + bs * s_w[pj >> 6];  // :92-94
-            nsq = nsq + bs * bs;            // :95-96
+    } else if (nm <= SHORT_NM) {
+      // A handful of entries (a large corpus: 2-6): EVERY WAVE settles the whole list for itself -- lane e of each wave
+      // takes entry e: how often its id occurs, the group's representative (its lowest cluster sequence), its role and,
+      // for a representative, the sums in ascending cluster sequence (the reference's order).  A few dozen LDS reads,
+      // repeated in every wave, instead of a barrier behind one wave's work and another behind the counters.
+      // No workgroup barrier follows before the one behind the compaction (or the lane maxima), so until then no wave may
+      // read from LDS what ANOTHER wave wrote after the match-list barrier above:
+      //  - roles travel by a cross-lane read inside the owner's own wave: two ballots (representatives, folded), whose bit
+      //    mi[u] is entry mi[u]'s role.  The ballots stand here, where all 64 lanes run them, not under `if (mi[u] >= 0)`;
+      //  - a representative's sums go to s_Mdot / s_Mnsq from EVERY wave (the same bits, from the same additions in
+      //    the same order): phase 4 reads what its own wave wrote -- a wave's LDS accesses keep their order --, and the
+      //    hand-over reads them behind the compaction's barrier;
+      //  - the folded count is a ballot's popcount, the same in every wave, and EVERY wave stores it to CTL_FOLD: phase 5
+      //    takes its first decision from live_tweets(), that is from a CTL_LIVE nobody writes any more and from the
+      //    CTL_FOLD its own wave wrote (the others store the same number).
+      const int lane = tid & 63;
+      const int e = lane < nm ? lane : 0;
+      const long long my = s_Mid[e];
+      const int myseq = s_Mseq[e];
+      int cnt = 0, rep = myseq;
+#pragma unroll 4
+      for (int e2 = 0; e2 < nm; e2++) {  // (uniform addresses: broadcast reads)
+        const bool same = s_Mid[e2] == my;
+        const int se = s_Mseq[e2];
+        cnt += same ? 1 : 0;
+        rep = (same && se < rep) ? se : rep;
+      }
+      int role = 0;
+      if (lane < nm && cnt >= 2) {
+        role = 2;
+        if (myseq == rep) {
+          double dot = 0.0, nsq = 0.0;
+          int last = -1;
+          for (int rr = 0; rr < cnt; rr++) {  // ascending cluster sequence
+            int best = 0x7fffffff;
+            double bs = 0.0;
+#pragma unroll 4
+            for (int e2 = 0; e2 < nm; e2++) {
+              const int se = s_Mseq[e2];
+              if (s_Mid[e2] == my && se > last && se < best) { best = se; bs = s_Msc[e2]; }
+            }
+            dot = dot + bs * s_w[best];  // :92-94
+            nsq = nsq + bs * bs;         // :95-96
+            last = best;
           }
-        }
-        if (live) {
-          if (role == 1) {
-            if constexpr (NORMS) nsq = use_norms ? s_Mnrm[ee] : nsq;  // one norm per tweet, not a sum over clusters
-            s_Mdot[ee] = dot;
-            s_Mnsq[ee] = nsq;
-          }
-          s_Mrole[ee] = role;
+          if constexpr (NORMS) nsq = use_norms ? s_Mnrm[e] : nsq;  // one norm per tweet, not a sum over clusters
+          s_Mdot[e] = dot;
+          s_Mnsq[e] = nsq;
+          role = 1;
         }
       }
-      __syncthreads();
+      // (the wave's own writes above, before its reads in phase 4)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       STAMP(10);  // groups settled
-      int folded = 0;
+      static_assert(SHORT_NM <= 32, "the roles of a short list travel as two 32-bit masks");
+      const uint32_t reps = (uint32_t)__ballot(role == 1), folds = (uint32_t)__ballot(role == 2);  // bit e = entry e
+      const int folded = __popc(folds);  // every entry belongs to exactly one posting slot
 #pragma unroll
       for (int u = 0; u < U; u++) {
-        const int role = mi[u] >= 0 ? s_Mrole[mi[u]] : 0;
-        seq[u] = role == 1 ? (0x10000 | mi[u]) : (role == 2 ? -1 : seq[u]);
-        folded += __popcll(__ballot(role == 2));
+        const uint32_t bit = mi[u] >= 0 ? 1u << mi[u] : 0u;
+        seq[u] = (reps & bit) ? (0x10000 | mi[u]) : ((folds & bit) ? -1 : seq[u]);
       }
-      if ((tid & 63) == 0 && folded) {
-        atomicSub(&s_ctl[CTL_LIVE], folded);
-        atomicAdd(&s_ctl[CTL_FOLD], folded);
-      }
-      __syncthreads();
+      if ((tid & 63) == 0) s_ctl[CTL_FOLD] = folded;
     } else {
-      {
-        // one thread per match-list entry, ids compared inside M (a handful of entries on a large corpus, or more than a
-        // wave holds)
+      // Longer lists are settled once, for the workgroup.  Every entry belongs to exactly one posting slot, so the
+      // postings that fold are the entries of role 2: whoever settles counts them, in front of the barrier that
+      // publishes the roles -- the owners' pass behind it needs no atomics and no barrier of its own.
+      if (nm <= 64) {
+        // A duplicate-heavy corpus (1M tweets under 144k clusters: every unit, 40-60 entries): the entries are SORTED by
+        // (tweet id, cluster sequence) in wave 0's registers -- groups become runs of neighbouring lanes, a run's first
+        // lane is its representative and walks the run for its sums (ascending cluster sequence: the reference's order).
+        // The pairwise comparison below costs nm^2 dependent LDS reads: 18 k of such a unit's 40 k cycles.
+        if (tid < 64) {
+          const bool have = tid < nm;
+          uint64_t kh = have ? id_key(s_Mid[tid]) : 0ull;  // descending id_key = ascending id
+          uint64_t kl = have ? ~(uint64_t)(((uint32_t)s_Mseq[tid] << 6) | (uint32_t)tid) : 0ull;  // (never 0 for an entry)
+          wave_sort_desc_k128(kh, kl);
+          const bool live = (kh | kl) != 0ull;
+          const uint32_t pk = (uint32_t)~kl;  // cluster sequence << 6 | entry
+          const int ee = (int)(pk & 63u);
+          const uint64_t prev = __shfl_up((unsigned long long)kh, 1, 64);
+          const bool start = live && (tid == 0 || prev != kh);
+          const unsigned long long sm = __ballot(start);
+          const int n_ent = __popcll(__ballot(live));
+          const unsigned long long above = tid == 63 ? 0ull : (sm >> (tid + 1));
+          const int len = start ? (above != 0ull ? __ffsll((long long)above) : n_ent - tid) : 0;
+          const int role = !live ? 0 : (start ? (len >= 2 ? 1 : 0) : 2);
+          const int max_len = (int)wave_max_u32((uint32_t)len);
+          double dot = 0.0, nsq = 0.0;
+          for (int j = 0; j < max_len; j++) {  // (uniform)
+            const uint32_t pj = (uint32_t)__shfl((int)pk, tid + j < 64 ? tid + j : 63, 64);
+            if (role == 1 && j < len) {
+              const double bs = s_Msc[pj & 63u];
+              dot = dot + bs * s_w[pj >> 6];  // :92-94
+              nsq = nsq + bs * bs;            // :95-96
+            }
+          }
+          if (live) {
+            if (role == 1) {
+              if constexpr (NORMS) nsq = use_norms ? s_Mnrm[ee] : nsq;  // one norm per tweet, not a sum over clusters
+              s_Mdot[ee] = dot;
+              s_Mnsq[ee] = nsq;
+            }
+            s_Mrole[ee] = role;
+          }
+          const int folded = __popcll(__ballot(role == 2));  // (wave 0, all 64 lanes)
+          if (tid == 0) s_ctl[CTL_FOLD] = folded;
+        }
+      } else {
+        // one thread per match-list entry, ids compared inside M (more entries than a wave holds)
+        int folded = 0;  // of the wave (lane 0 runs the loop whenever a lane of its wave does)
         for (int m = tid; m < nm; m += WG) {
           const long long my = s_Mid[m];
           const int myseq = s_Mseq[m];
@@ -571,23 +639,18 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
             }
           }
           s_Mrole[m] = role;
+          folded += __popcll(__ballot(role == 2));
         }
+        if ((tid & 63) == 0 && folded) atomicAdd(&s_ctl[CTL_FOLD], folded);
       }
       __syncthreads();
       STAMP(10);  // groups settled
-      int folded = 0;
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int role = mi[u] >= 0 ? s_Mrole[mi[u]] : 0;
         // representative: carries the group's sums (bit 16 + its M index); the others fold into it
         seq[u] = role == 1 ? (0x10000 | mi[u]) : (role == 2 ? -1 : seq[u]);
-        folded += __popcll(__ballot(role == 2));
       }
-      if ((tid & 63) == 0 && folded) {
-        atomicSub(&s_ctl[CTL_LIVE], folded);
-        atomicAdd(&s_ctl[CTL_FOLD], folded);
-      }
-      __syncthreads();
     }
   }
 
@@ -598,7 +661,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
 #pragma unroll
       for (int u = 0; u < U; u++) x_ ^= (unsigned long long)__float_as_uint(s32[u]) ^ (unsigned)seq[u];
     }
-    ABLATE(2, x_ + (unsigned)s_ctl[CTL_LIVE]);
+    ABLATE(2, x_ + (unsigned)live_tweets());
   }
   // ---- 4. approximate fp32 keys ---------------------------------------------------------------------------
   // One uniform branch per algorithm around the slot loop (not a switch per slot).  Cosine and the no-source-norm
@@ -658,7 +721,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
           double nsq64 = 0.0;
           if (sv * sv < 1e-6f) {
             const int c = seq[u];
-            const double sd = ix.postings[s_begin[c] + ((uint32_t)(u * WG + tid) - s_pre[c])].score;
+            const double sd = ix.postings[s_off[c] + (uint32_t)(u * WG + tid)].score;
             nsq64 = sd * sd;
           }
           a = approx_score(3, sv * s_w32[seq[u] & (NS - 1)], sv * sv, nsq64, 0.f, invln, &forced);
@@ -698,10 +761,10 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
   uint32_t *const s_lm = s_hist;  // [WG], in the dead Bloom filter's memory (or s_hist_own, which is WG <= 256 words)
   uint32_t tau = 0;  // survivors: k32 >= tau
   bool cut_by_data = !pre_cut;  // uniform
-  if (pre_cut && s_ctl[CTL_LIVE] > keep_all) tau = pre_tau;
+  if (pre_cut && live_tweets() > keep_all) tau = pre_tau;
   for (;;) {
     if (cut_by_data) {
-      const bool select = s_ctl[CTL_LIVE] > keep_all && !overflow;  // uniform
+      const bool select = live_tweets() > keep_all && !overflow;  // uniform
       if (select) {
         uint32_t m = 0u;
 #pragma unroll
@@ -801,15 +864,15 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
       ABLATE(9, x_ + s_ent[tid & 63] + (unsigned)s_ctl[CTL_NSURV]);
     }
     // the cluster-level cut counted postings the filters then removed: cut by the data after all.  (With nothing
-    // removed -- live + folded = T -- the count behind the cut is exact; it may then be below kl on purpose: the
+    // removed -- CTL_LIVE, the live postings, = T -- the count behind the cut is exact; it may then be below kl on purpose: the
     // descriptor kernel's query-level rule.)  The cut also counted the postings that then FOLDED into a representative:
     // when the survivors and the folded together reach kl, the unit's own rule was the one in force and the folding took
     // the offer below kl -- a unit that is the whole query (P = 1) then offered fewer than k and was re-run every time.
     // (Sufficient, not exact: CTL_FOLD counts every folded posting of the unit, behind the cut or not, so a unit that the
     // query-level rule held below kl on purpose and that folded a few duplicates elsewhere re-cuts too.  That costs it a
     // second pass of 5a / 5b and the merge a few more candidates, never an answer.)
-    if (!cut_by_data && tau != 0u && s_ctl[CTL_NSURV] < kl && s_ctl[CTL_NSURV] < s_ctl[CTL_LIVE] &&
-        (s_ctl[CTL_LIVE] + s_ctl[CTL_FOLD] < (int)T || s_ctl[CTL_NSURV] + s_ctl[CTL_FOLD] >= kl) && !s_ctl[CTL_BAD] && !overflow) {
+    if (!cut_by_data && tau != 0u && s_ctl[CTL_NSURV] < kl && s_ctl[CTL_NSURV] < live_tweets() &&
+        (s_ctl[CTL_LIVE] < (int)T || s_ctl[CTL_NSURV] + s_ctl[CTL_FOLD] >= kl) && !s_ctl[CTL_BAD] && !overflow) {
       __syncthreads();  // (everyone has read the counters)
       if (tid == 0) s_ctl[CTL_NSURV] = 0;
       cut_by_data = true;
@@ -834,7 +897,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
   unsigned long long theta_key = 0ull;
   // ... unless every live candidate survived the cut (tau can be non-zero and still below all of them when the
   // need-th key sits in the lowest occupied digit): then nothing is withheld and nothing may be dropped below.
-  if (tau != 0u && s_ctl[CTL_NSURV] < s_ctl[CTL_LIVE]) {
+  if (tau != 0u && s_ctl[CTL_NSURV] < live_tweets()) {
     double tau_val = (double)__uint_as_float(tau & 0x7fffffffu);
     tau_val = tau_val < 1e30 ? tau_val : 1e30;  // a cut inside the forced (+inf) band: the others are still < 1e30
     theta_key = score_key(tau_val * (1.0 + 2.0 * (double)APPROX_EPS));
@@ -867,14 +930,14 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
       const double v = normalise_f(h.alg, s_Mdot[c & 0xffff], s_Mnsq[c & 0xffff], l2, ln);
       key = v >= *(const volatile double *)&hq->min_score ? score_key(v) : CAND_DROPPED;  // :125 (false for NaN)
     } else {
-      const uint32_t pos = s_begin[c] + ((uint32_t)e - s_pre[c]);
+      const uint32_t pos = s_off[c] + (uint32_t)e;
       idv = (long long)(((unsigned long long)(uint32_t)c << 32) | pos);
     }
     cand_key[obase + i] = key;
     cand_id[obase + i] = idv;
   }
   if (tid == 0) {
-    const int n_live = s_ctl[CTL_LIVE];
+    const int n_live = live_tweets();
     const bool withheld = n_live > ns;  // candidates below the cut were not examined exactly
     LATE_ARG(cand_cnt)[unit] = ns;
     LATE_ARG(unit_unique)[unit] = n_live;

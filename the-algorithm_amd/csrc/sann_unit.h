@@ -113,8 +113,10 @@ constexpr int BLOOM_POS_BITS = 20;
 
 constexpr int bloom_log2(int capacity) { return capacity <= 512 ? 8 : capacity <= 1024 ? 9 : 11; }
 
+// CTL_LIVE: live postings (final behind the gather's barrier); CTL_FOLD: those of them that folded into a representative
+// of their tweet (the duplicate phase); live tweets = CTL_LIVE - CTL_FOLD
 enum {
-  CTL_NFLAG = 0, CTL_NM, CTL_LIVE, CTL_NSURV, CTL_FOLD, CTL_SEL_D, CTL_SEL_A, CTL_SEL_B, CTL_BAD, CTL_KMIN, CTL_KMAX, CTL_PRE,
+  CTL_NFLAG = 0, CTL_NM, CTL_LIVE, CTL_FOLD, CTL_NSURV, CTL_SEL_D, CTL_SEL_A, CTL_SEL_B, CTL_BAD, CTL_KMIN, CTL_KMAX, CTL_PRE,
   CTL_N
 };
 
