@@ -113,8 +113,9 @@ int hnsw_index_build_insert_gpu_levels(int32_t device, int32_t metric, int64_t n
  * Refused with HNSW_EINVAL before anything changes: a duplicate key, ids present or absent contrary to the index, a level
  * outside 0..60, ef_construction outside 1..256, batch outside 0..2^20, n_old + n >= 2^31 - 1.  A device error part-way
  * leaves the index unusable: every later call on it fails with HNSW_EDEVICE.
- * Room: the buffers grow by 1.5x at least, device to device (exactly to the capacity after hnsw_index_reserve).  The host copy
- * of the graph that exports and files read is refreshed by the first such call after an append, not by the append.
+ * Room: the buffers grow by 1.5x at least, device to device (exactly to the capacity after hnsw_index_reserve).  An append
+ * touches no host copy of the lists: the first export (hnsw_index_graph_size, hnsw_index_graph) or save after it reads them from
+ * the device, and that read is kept until the next append or update.
  * One call at a time per index, appends and searches alike (the handle's scratch is shared), as for hnsw_search.
  * hnsw_index_build_stats reports the last append. */
 int hnsw_index_append(hnsw_index_t *index, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction,
@@ -161,7 +162,7 @@ int hnsw_index_append_levels(hnsw_index_t *index, int64_t n, const float *vector
  * index unusable (as an append does).  If the append of the absent keys fails after the rounds (device memory for its growth,
  * a device error), the present keys stay updated, the absent ones are not added, and the message says so; the index is then as
  * after update(P) (or unusable, for a device error part-way through the append).
- * The host copy of the graph is refreshed by the next export.  One call at a time per index, as for appends and searches. */
+ * The next export reads the lists from the device again.  One call at a time per index, as for appends and searches. */
 int hnsw_index_update(hnsw_index_t *index, int64_t n, const float *vectors, const int64_t *ids, int32_t ef_construction,
                       uint64_t seed, int32_t batch, int64_t *out_appended);
 /* Counters of the last hnsw_index_update (any pointer may be NULL): rounds, relink proposals, proposals superseded by a later item

@@ -1,4 +1,6 @@
-// hnsw_ann.hip -- HNSW graph search on gfx950 (include/hnsw_ann.h) + the host-side graph builder.
+// hnsw_ann.hip -- HNSW graph search, construction, append and update on gfx950 (include/hnsw_ann.h).  Of the graph the host
+// keeps the slot and base tables and one "key exists" flag per row of storage (hnsw_graph_host.h); the lists live on the device,
+// and an export reads them from there.  The host-only builder is hnsw_host_builder.h; hnsw_queue.h is what it shares with the kernels.
 //
 // Reference (paths relative to /root/reference/ann/src/main/java/com/twitter/ann/hnsw/):
 //   HnswIndex.java:538-553   searchKnn            HnswIndex.java:447-475  bestEntryPointUntilLayer
@@ -33,11 +35,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
 #include <memory>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -46,6 +45,9 @@
 #include "ann_by_id_internal.h"
 #include "device_buf.h"
 #include "host_error.h"
+#include "hnsw_graph_host.h"
+#include "hnsw_host_builder.h"
+#include "hnsw_queue.h"
 #define HTRY(expr) HIP_TRY_AS(HNSW_EDEVICE, expr)
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, HNSW_ENOMEM, HNSW_EINTERNAL); }
 
@@ -60,77 +62,6 @@ constexpr int CCAP_FIRST = 8192;        // global part of the candidate queue, f
 constexpr int CCAP_GLOBAL = 1 << 17;    // ... of the re-run of a query that outgrew it
 constexpr int64_t VLOG_MIN_VWORDS = 1 << 18;  // bitmaps of at least 1 MB keep an undo log
 constexpr int VLOG_CAP = 1 << 16;       // visited nodes a walk remembers for cleaning up after itself (more: it wipes its whole bitmap)
-
-// ---------------------------------------------------------------------------------------------
-// shared host/device pieces: Float.compare and java.util.PriorityQueue
-// ---------------------------------------------------------------------------------------------
-struct HEntry {
-  float dist;
-  uint32_t node;
-};
-
-__host__ __device__ inline int32_t float_to_int_bits(float f) {  // Float.floatToIntBits: canonical NaN
-  if (f != f) return 0x7fc00000;
-#ifdef __HIP_DEVICE_COMPILE__
-  return __float_as_int(f);
-#else
-  int32_t i;
-  std::memcpy(&i, &f, 4);
-  return i;
-#endif
-}
-__host__ __device__ inline int float_compare(float a, float b) {  // java.lang.Float.compare
-  if (a < b) return -1;
-  if (a > b) return 1;
-  const int32_t x = float_to_int_bits(a), y = float_to_int_bits(b);
-  return x == y ? 0 : (x < y ? -1 : 1);
-}
-// comparator of a DistancedItemQueue (DistancedItemQueue.java:37-43)
-template <bool MINQ>
-__host__ __device__ inline int qcmp(const HEntry &a, const HEntry &b) {
-  return MINQ ? float_compare(a.dist, b.dist) : float_compare(b.dist, a.dist);
-}
-// PriorityQueue.offer -> siftUpUsingComparator
-template <bool MINQ>
-__host__ __device__ inline void pq_add(HEntry *q, int &n, HEntry x) {
-  int k = n++;
-  while (k > 0) {
-    const int parent = (k - 1) >> 1;
-    const HEntry e = q[parent];
-    if (qcmp<MINQ>(x, e) >= 0) break;
-    q[k] = e;
-    k = parent;
-  }
-  q[k] = x;
-}
-// PriorityQueue.poll -> siftDownUsingComparator
-template <bool MINQ>
-__host__ __device__ inline HEntry pq_poll(HEntry *q, int &n) {
-  const HEntry result = q[0];
-  const int s = --n;
-  if (s > 0) {
-    const HEntry x = q[s];
-    int k = 0;
-    const int half = s >> 1;
-    while (k < half) {
-      int child = 2 * k + 1;
-      HEntry c = q[child];
-      const int right = child + 1;
-      if (right < s) {
-        const HEntry r = q[right];
-        if (qcmp<MINQ>(c, r) > 0) {
-          c = r;
-          child = right;
-        }
-      }
-      if (qcmp<MINQ>(x, c) <= 0) break;
-      q[k] = c;
-      k = child;
-    }
-    q[k] = x;
-  }
-  return result;
-}
 
 // ---- the search kernel's queues -------------------------------------------------------------------------------------
 // Entries carry the distance as an integer KEY whose signed order is Float.compare's (floatToIntBits, then the low 31
@@ -265,11 +196,6 @@ __device__ inline KEntry kq_poll(KEntry *q, int &n) {
     q[k] = x;
   }
   return result;
-}
-
-// distance from the fixed-order sum (see file header)
-__host__ __device__ inline float finish_distance(int metric, float s) {
-  return metric == HNSW_METRIC_L2 ? sqrtf(s) : 1.0f - s;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1251,11 +1177,10 @@ __global__ void hnsw_key_merge_kernel(const int64_t *__restrict__ a, int64_t na,
 struct hnsw_index {
   int device = 0, metric = 0, d = 0, dpad = 0, m = 0, m0 = 0, max_level = 0;
   int64_t n = 0, entry = -1;
-  std::vector<std::vector<std::vector<uint32_t>>> upper;  // [level - 1][slot] lists, host copy for export
-  std::vector<std::vector<uint32_t>> level0;              // host copy
-  std::vector<uint8_t> has0;                              // node has a level-0 entry
+  // The graph (hnsw_graph::FlatGraph): the lists live on the device (`exported` is a read-back), the two small tables on both
+  // sides, and the host alone knows which keys HnswNode(level, item) exist besides those with a non-empty list.
   std::vector<int32_t> upper_slot_h, upper_base_h;
-  std::vector<std::vector<uint8_t>> has_upper;            // [slot][level - 1]: entry exists
+  mutable std::vector<uint8_t> has0, has_up;  // [n], [rows of upper_adj]: key loaded or wired, or seen non-empty by an export
   Buf x, adj0, upper_slot, upper_base, upper_adj, ids;
   bool has_ids = false;
   // scratch
@@ -1273,7 +1198,8 @@ struct hnsw_index {
   int64_t upper_rows_cap = 0, upper_slots_cap = 0;
   bool keyed = false;           // created with ids (has_ids may be false only because n was 0)
   bool broken = false;          // a device error part-way through an append: every later call fails with HNSW_EDEVICE
-  mutable bool host_stale = false;  // level0 / upper / has0 / has_upper behind the device graph (refreshed by an export)
+  mutable hnsw_graph::FlatGraph exported;  // the last export's read-back of the device's lists (read_graph) ...
+  mutable bool exported_fresh = false;     // ... which no append or update has changed since
   Buf levels;                   // [cap] levels of inserted rows (read by the insert kernel by position)
   Buf b_order, b_pair_off, b_keys, b_sorted, b_tmp, b_bstats, b_visited, b_vlog;
   int64_t bv_items = 0, bv_vwords = 0;  // layout of b_visited: walks at a time, words per walk (reserve_visited)
@@ -1295,287 +1221,24 @@ struct hnsw_index {
 
 namespace {
 
-// graph under construction / being loaded.  Dense rows: item i owns rows base[i] .. base[i] + top[i] (levels
-// 0..top[i]); `has` says whether the reference's map holds the key HnswNode(level, item) at all.
-// One lock per stripe of items guards a row's read-modify-write, so the builder can run on several
-// host threads (the reference inserts concurrently too, HnswIndex.java:150-200); at most one lock is
-// ever held, so there is nothing to deadlock on.
-struct HostGraph {
-  int64_t n = 0;
-  int m = 0, m0 = 0;
-  int max_level = -1;  // HnswIndex.java:97
-  int64_t entry = -1;
-  std::vector<int32_t> top;
-  std::vector<int64_t> base;
-  std::vector<std::vector<uint32_t>> rows;
-  std::vector<uint8_t> has;
-  std::unique_ptr<std::mutex[]> locks;
-  static constexpr size_t STRIPES = 8192;
-  std::mutex meta;
-
-  void init(int64_t n_, int m_, const std::vector<int32_t> &tops) {
-    n = n_;
-    m = m_;
-    m0 = 2 * m_;
-    top = tops;
-    base.assign((size_t)n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) base[(size_t)i + 1] = base[(size_t)i] + top[(size_t)i] + 1;
-    rows.assign((size_t)base[(size_t)n], {});
-    has.assign((size_t)base[(size_t)n], 0);
-    locks.reset(new std::mutex[STRIPES]);
-  }
-  std::mutex &lock_of(uint32_t item) { return locks[item % STRIPES]; }
-  // getConnectionListForRead: a copy of the list, empty when the key is absent
-  std::vector<uint32_t> read(int level, uint32_t item) {
-    if (level > top[item]) return {};
-    std::lock_guard<std::mutex> lk(lock_of(item));
-    return rows[(size_t)(base[item] + level)];
-  }
-  bool exists(int level, uint32_t item) const { return level <= top[item] && has[(size_t)(base[item] + level)]; }
-  void put_locked(int level, uint32_t item, std::vector<uint32_t> list) {  // caller holds lock_of(item)
-    rows[(size_t)(base[item] + level)] = std::move(list);
-    has[(size_t)(base[item] + level)] = 1;
-  }
-  void put(int level, uint32_t item, std::vector<uint32_t> list) {
-    std::lock_guard<std::mutex> lk(lock_of(item));
-    put_locked(level, item, std::move(list));
-  }
-};
-
-// stored rows on the host, fp16-rounded, each 64-element block transposed ([e][j] instead of [j][e]) so that
-// the 8 partial sums of the fixed summation order are the lanes of one SIMD accumulator
-struct HostVectors {
-  std::vector<float> t;
-  int dpad = 0, metric = 0;
-  void load(const std::vector<float> &rows, int64_t n, int dpad_, int metric_) {
-    dpad = dpad_;
-    metric = metric_;
-    t.resize(rows.size());
-    for (int64_t i = 0; i < n; ++i)
-      for (int b = 0; b < dpad / 64; ++b)
-        for (int j = 0; j < 8; ++j)
-          for (int e = 0; e < 8; ++e) t[(size_t)i * dpad + b * 64 + e * 8 + j] = rows[(size_t)i * dpad + b * 64 + j * 8 + e];
-  }
-  float distance(uint32_t a, uint32_t b) const {
-    const float *q = t.data() + (size_t)a * dpad, *y = t.data() + (size_t)b * dpad;
-    float p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (metric == HNSW_METRIC_L2) {
-      for (int k = 0; k < dpad; k += 8)
-        for (int j = 0; j < 8; ++j) {
-          const float d = q[k + j] - y[k + j];
-          p[j] = p[j] + d * d;
-        }
-    } else {
-      for (int k = 0; k < dpad; k += 8)
-        for (int j = 0; j < 8; ++j) p[j] = p[j] + q[k + j] * y[k + j];
-    }
-    const float r0 = p[0] + p[1], r2 = p[2] + p[3], r4 = p[4] + p[5], r6 = p[6] + p[7];
-    return finish_distance(metric, (r0 + r2) + (r4 + r6));
-  }
-};
-
-// DistancedItemQueue on the host
-struct JQueue {
-  std::vector<HEntry> q;
-  int n = 0;
-  bool minq;
-  uint32_t origin;
-  explicit JQueue(bool mq, uint32_t o) : minq(mq), origin(o) {}
-  void add(HEntry e) {
-    if ((int)q.size() <= n) q.resize((size_t)n + 64);
-    if (minq) pq_add<true>(q.data(), n, e);
-    else pq_add<false>(q.data(), n, e);
-  }
-  HEntry poll() { return minq ? pq_poll<true>(q.data(), n) : pq_poll<false>(q.data(), n); }
-  JQueue reverse() const {  // DistancedItemQueue.reverse: re-add in array (iterator) order
-    JQueue r(!minq, origin);
-    for (int i = 0; i < n; ++i) r.add(q[(size_t)i]);
-    return r;
-  }
-};
-
-struct Builder {  // one per host thread
-  HostGraph &g;
-  const HostVectors &v;
-  int ef_construction;
-  std::vector<uint32_t> stamp;  // visited set, epoch-stamped
-  uint32_t epoch = 0;
-
-  uint32_t best_entry(uint32_t entry, uint32_t item, int max_layer, int selected) {  // HnswIndex.java:447-475
-    uint32_t cur = entry;
-    if (selected < max_layer) {
-      float cur_dist = v.distance(item, cur);
-      for (int level = max_layer; level > selected; --level) {
-        bool changed = true;
-        while (changed) {
-          changed = false;
-          for (uint32_t nn : g.read(level, cur)) {
-            const float t = v.distance(item, nn);
-            if (t < cur_dist) {
-              cur_dist = t;
-              cur = nn;
-              changed = true;
-            }
-          }
-        }
-      }
-    }
-    return cur;
-  }
-
-  JQueue search_layer(uint32_t item, uint32_t entry, int ef, int level) {  // HnswIndex.java:571-623, isUpdate = false
-    JQueue cq(true, item);
-    cq.add(HEntry{v.distance(item, entry), entry});
-    JQueue wq = cq.reverse();
-    ++epoch;
-    stamp[entry] = epoch;
-    float lower = wq.q[0].dist;
-    while (cq.n > 0) {
-      const HEntry cand = cq.q[0];
-      if (cand.dist > lower) break;
-      cq.poll();
-      for (uint32_t nn : g.read(level, cand.node)) {
-        if (stamp[nn] == epoch) continue;
-        stamp[nn] = epoch;
-        const float dist = v.distance(item, nn);
-        if (wq.n < ef || dist < wq.q[0].dist) {
-          cq.add(HEntry{dist, nn});
-          wq.add(HEntry{dist, nn});
-          if (wq.n > ef) wq.poll();
-          lower = wq.q[0].dist;
-        }
-      }
-    }
-    return wq;
-  }
-
-  std::vector<uint32_t> select(const JQueue &cands, int max_conn) {  // HnswIndex.java:479-526
-    const uint32_t base = cands.origin;
-    std::vector<uint32_t> res;
-    if (cands.n <= max_conn) {
-      bool removed = false;  // List.remove(Object): first occurrence only
-      for (int i = 0; i < cands.n; ++i) {
-        if (!removed && cands.q[(size_t)i].node == base) {
-          removed = true;
-          continue;
-        }
-        res.push_back(cands.q[(size_t)i].node);
-      }
-      return res;
-    }
-    JQueue minq = cands.reverse();
-    while (minq.n > 0) {
-      if ((int)res.size() >= max_conn) break;
-      const HEntry c = minq.poll();
-      if (c.node == base) continue;
-      bool include = true;
-      for (uint32_t e : res) {
-        if (v.distance(e, c.node) < c.dist) {
-          include = false;
-          break;
-        }
-      }
-      if (include) res.push_back(c.node);
-    }
-    return res;
-  }
-
-  uint32_t connect(uint32_t item, const JQueue &cands, int level) {  // mutuallyConnectNewElement, isUpdate = false
-    const std::vector<uint32_t> neighbours = select(cands, g.m);
-    g.put(level, item, neighbours);
-    const int M = level == 0 ? g.m0 : g.m;
-    for (uint32_t nn : neighbours) {
-      if (nn == item) continue;
-      std::lock_guard<std::mutex> lk(g.lock_of(nn));  // the neighbour's write lock (:406-435)
-      std::vector<uint32_t> conn = g.rows[(size_t)(g.base[nn] + level)];
-      if ((int)conn.size() < M) {
-        conn.push_back(item);
-      } else {
-        JQueue q(false, nn);
-        for (uint32_t t : conn) q.add(HEntry{v.distance(nn, t), t});
-        q.add(HEntry{v.distance(nn, item), item});
-        conn = select(q, M);
-      }
-      g.put_locked(level, nn, std::move(conn));
-    }
-    return neighbours.empty() ? item : neighbours[0];
-  }
-
-  void insert(uint32_t item, int cur_level) {  // HnswIndex.java:137-200
-    int64_t entry;
-    int max_layer;
-    bool hold_meta = false;
-    g.meta.lock();
-    entry = g.entry;
-    max_layer = g.max_level;
-    if (cur_level > max_layer) hold_meta = true;  // the global lock: this insert may move the entry point (:173-183)
-    else g.meta.unlock();
-    if (entry >= 0) {
-      uint32_t cur = (uint32_t)entry;
-      if (cur_level < max_layer) cur = best_entry(cur, item, max_layer, cur_level);
-      for (int level = std::min(cur_level, max_layer); level >= 0; --level) {
-        const JQueue cands = search_layer(item, cur, ef_construction, level);
-        cur = connect(item, cands, level);
-      }
-    }
-    if (hold_meta) {  // HnswMeta starts at (-1, empty): the first item always takes this branch
-      g.max_level = cur_level;
-      g.entry = item;
-      g.meta.unlock();
-    }
-  }
-};
-
-int upload_graph(hnsw_index *ix, const HostGraph &g) {
-  const int64_t n = ix->n;
+// the graph of a new handle: its four arrays to the device, its four small ones kept on the host.  A buffer of no rows
+// holds one zeroed row, so no kernel is ever handed an allocation shorter than a row.
+int upload_graph(hnsw_index *ix, hnsw_graph::FlatGraph &&g) {
+  auto put = [](Buf &b, const auto &v, size_t least) {
+    hipError_t e = b.reserve(std::max(v.size(), least) * 4);
+    if (e == hipSuccess) e = v.empty() ? hipMemset(b.p, 0, least * 4) : hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice);
+    return e;
+  };
+  HTRY(put(ix->adj0, g.adj0, (size_t)ix->m0 + 1));
+  HTRY(put(ix->upper_slot, g.upper_slot, 1));
+  HTRY(put(ix->upper_base, g.upper_base, 1));
+  HTRY(put(ix->upper_adj, g.upper_adj, (size_t)ix->m + 1));
   ix->entry = g.entry;
-  ix->max_level = std::max(g.max_level, 0);
-  ix->level0.assign((size_t)n, {});
-  ix->has0.assign((size_t)n, 0);
-  std::vector<uint32_t> adj0((size_t)std::max<int64_t>(n, 1) * (ix->m0 + 1), 0);
-  for (int64_t i = 0; i < n; ++i) {
-    const auto &l = g.rows[(size_t)g.base[(size_t)i]];
-    ix->level0[(size_t)i] = l;
-    ix->has0[(size_t)i] = g.has[(size_t)g.base[(size_t)i]];
-    adj0[(size_t)i * (ix->m0 + 1)] = (uint32_t)l.size();
-    std::copy(l.begin(), l.end(), adj0.begin() + (size_t)i * (ix->m0 + 1) + 1);
-  }
-  // upper levels: slot per node with storage above level 0, rows = its top level
-  ix->upper_slot_h.assign((size_t)std::max<int64_t>(n, 1), -1);
-  ix->upper_base_h.assign(1, 0);
-  int top_all = 0;
-  for (int64_t i = 0; i < n; ++i)
-    if (g.top[(size_t)i] > 0) {
-      ix->upper_slot_h[(size_t)i] = (int32_t)ix->upper_base_h.size() - 1;
-      ix->upper_base_h.push_back(ix->upper_base_h.back() + g.top[(size_t)i]);
-      top_all = std::max(top_all, g.top[(size_t)i]);
-    }
-  const int64_t rows = ix->upper_base_h.back();
-  std::vector<uint32_t> uadj((size_t)std::max<int64_t>(rows, 1) * (ix->m + 1), 0);
-  const size_t n_slots = ix->upper_base_h.size() - 1;
-  ix->upper.assign((size_t)top_all, std::vector<std::vector<uint32_t>>(n_slots));
-  ix->has_upper.assign(n_slots, {});
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t sl = ix->upper_slot_h[(size_t)i];
-    if (sl < 0) continue;
-    ix->has_upper[(size_t)sl].assign((size_t)g.top[(size_t)i], 0);
-    for (int l = 1; l <= g.top[(size_t)i]; ++l) {
-      const auto &list = g.rows[(size_t)(g.base[(size_t)i] + l)];
-      ix->upper[(size_t)l - 1][(size_t)sl] = list;
-      ix->has_upper[(size_t)sl][(size_t)l - 1] = g.has[(size_t)(g.base[(size_t)i] + l)];
-      uint32_t *row = uadj.data() + (size_t)(ix->upper_base_h[(size_t)sl] + l - 1) * (ix->m + 1);
-      row[0] = (uint32_t)list.size();
-      std::copy(list.begin(), list.end(), row + 1);
-    }
-  }
-  HTRY(ix->adj0.reserve(adj0.size() * 4));
-  HTRY(hipMemcpy(ix->adj0.p, adj0.data(), adj0.size() * 4, hipMemcpyHostToDevice));
-  HTRY(ix->upper_slot.reserve(ix->upper_slot_h.size() * 4));
-  HTRY(hipMemcpy(ix->upper_slot.p, ix->upper_slot_h.data(), ix->upper_slot_h.size() * 4, hipMemcpyHostToDevice));
-  HTRY(ix->upper_base.reserve(ix->upper_base_h.size() * 4));
-  HTRY(hipMemcpy(ix->upper_base.p, ix->upper_base_h.data(), ix->upper_base_h.size() * 4, hipMemcpyHostToDevice));
-  HTRY(ix->upper_adj.reserve(uadj.size() * 4));
-  HTRY(hipMemcpy(ix->upper_adj.p, uadj.data(), uadj.size() * 4, hipMemcpyHostToDevice));
+  ix->max_level = g.max_level;
+  ix->upper_slot_h = std::move(g.upper_slot);
+  ix->upper_base_h = std::move(g.upper_base);
+  ix->has0 = std::move(g.has0);
+  ix->has_up = std::move(g.has_up);
   return HNSW_OK;
 }
 
@@ -1759,39 +1422,11 @@ int hnsw_index_build(int32_t device, int32_t metric, int64_t n, int32_t d, const
   std::unique_ptr<hnsw_index> ix;
   int rc = create_index(device, metric, n, d, vectors, ids, max_m, ix, nullptr);
   if (rc) return rc;
-  std::vector<int32_t> tops((size_t)n, 0);
-  for (int64_t e = 0; e < n_entries; ++e) {
-    if (entry_level[e] < 0 || entry_level[e] > max_level || entry_item[e] < 0 || entry_item[e] >= n)
-      return fail(HNSW_EINVAL, "graph entry out of range");
-    tops[(size_t)entry_item[e]] = std::max(tops[(size_t)entry_item[e]], entry_level[e]);
-  }
-  // Rows also for every layer a node can be REACHED on without a key of its own there -- the entry point on layers up to
-  // maxLevel, a neighbour on its list's layer: empty rows, which searches read as the absent list they are, and which an
-  // append (whose walks read and whose back links write the rows of every node they reach) needs to exist.
-  if (entry_point >= 0) tops[(size_t)entry_point] = std::max(tops[(size_t)entry_point], max_level);
-  for (int64_t e = 0; e < n_entries && entry_neighbours; ++e) {
-    if (entry_offsets[e + 1] < entry_offsets[e] || entry_offsets[e + 1] - entry_offsets[e] > 2 * (int64_t)max_m) continue;  // (refused below)
-    for (int64_t j = entry_offsets[e]; j < entry_offsets[e + 1]; ++j)
-      if (entry_neighbours[j] >= 0 && entry_neighbours[j] < n)
-        tops[(size_t)entry_neighbours[j]] = std::max(tops[(size_t)entry_neighbours[j]], entry_level[e]);
-  }
-  HostGraph g;
-  g.init(n, max_m, tops);
-  g.entry = entry_point < 0 ? -1 : entry_point;
-  g.max_level = max_level;
-  for (int64_t e = 0; e < n_entries; ++e) {
-    const int level = entry_level[e];
-    const int64_t item = entry_item[e];
-    const int64_t b = entry_offsets[e], en = entry_offsets[e + 1];
-    if (en < b || en - b > (level == 0 ? g.m0 : g.m)) return fail(HNSW_EINVAL, "neighbour list longer than the level allows");
-    std::vector<uint32_t> list;
-    for (int64_t j = b; j < en; ++j) {
-      if (!entry_neighbours || entry_neighbours[j] < 0 || entry_neighbours[j] >= n) return fail(HNSW_EINVAL, "neighbour out of range");
-      list.push_back((uint32_t)entry_neighbours[j]);
-    }
-    g.put(level, (uint32_t)item, std::move(list));
-  }
-  rc = upload_graph(ix.get(), g);
+  hnsw_graph::FlatGraph g;
+  if (const char *bad = hnsw_graph::from_entries(n, max_m, entry_point, max_level, n_entries, entry_level, entry_item, entry_offsets,
+                                                 entry_neighbours, g))
+    return fail(HNSW_EINVAL, bad);
+  rc = upload_graph(ix.get(), std::move(g));
   if (rc) return rc;
   *out = ix.release();
   return HNSW_OK;
@@ -1832,31 +1467,8 @@ static int build_insert_impl(int32_t device, int32_t metric, int64_t n, int32_t 
   hv.load(rows, n, ix->dpad, metric);
   rows.clear();
   rows.shrink_to_fit();
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, std::max<int64_t>(1, n / 64)));
-  if (nt == 1) {
-    Builder b{g, hv, ef_construction, std::vector<uint32_t>((size_t)n, 0), 0};
-    for (int64_t i = 0; i < n; ++i) b.insert((uint32_t)i, levels[(size_t)i]);
-  } else {
-    // the first items go in one by one (an entry point must exist), the rest concurrently
-    const int64_t warm = std::min<int64_t>(n, 256);
-    {
-      Builder b{g, hv, ef_construction, std::vector<uint32_t>((size_t)n, 0), 0};
-      for (int64_t i = 0; i < warm; ++i) b.insert((uint32_t)i, levels[(size_t)i]);
-    }
-    std::atomic<int64_t> next(warm);
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-      pool.emplace_back([&]() {
-        Builder b{g, hv, ef_construction, std::vector<uint32_t>((size_t)n, 0), 0};
-        for (;;) {
-          const int64_t i = next.fetch_add(1);
-          if (i >= n) break;
-          b.insert((uint32_t)i, levels[(size_t)i]);
-        }
-      });
-    for (auto &th : pool) th.join();
-  }
-  rc = upload_graph(ix.get(), g);
+  insert_all(g, hv, ef_construction, levels, n_threads);
+  rc = upload_graph(ix.get(), flat_graph(g));
   if (rc) return rc;
   *out = ix.release();
   return HNSW_OK;
@@ -1984,7 +1596,7 @@ static int insert_rows(hnsw_index *ix, int64_t n, const float *vectors, const in
   unsigned long long bs[4] = {0, 0, 0, 0};
   HTRY(hipMemcpy(bs, ix->b_bstats.p, sizeof(bs), hipMemcpyDeviceToHost));
   ix->broken = false;
-  // ---- the host side: O(n) of new rows; the lists themselves are read back only when exported (refresh_host) ----
+  // ---- the host side: the new rows' slots and the keys their wiring made (an export reads the lists from the device) ----
   ix->build_truncated = (int64_t)bs[0];
   ix->build_prunes = (int64_t)bs[1];
   ix->build_dropped = (int64_t)bs[2];
@@ -1996,21 +1608,11 @@ static int insert_rows(hnsw_index *ix, int64_t n, const float *vectors, const in
   ix->upper_slot_h.resize((size_t)n_old);
   ix->upper_slot_h.insert(ix->upper_slot_h.end(), new_slot.begin(), new_slot.end());
   ix->upper_base_h.insert(ix->upper_base_h.end(), new_base.begin(), new_base.end());
-  ix->level0.resize((size_t)(n_old + n));
-  ix->has0.resize((size_t)n_old);
-  int top_all = (int)ix->upper.size();
   for (int64_t i = 0; i < n; ++i) {
     ix->has0.push_back(wired_top[(size_t)i] >= 0 ? 1 : 0);
-    if (lv[(size_t)i] > 0) {
-      std::vector<uint8_t> h((size_t)lv[(size_t)i], 0);
-      for (int l = 1; l <= lv[(size_t)i]; ++l) h[(size_t)l - 1] = l <= wired_top[(size_t)i] ? 1 : 0;
-      ix->has_upper.push_back(std::move(h));
-      top_all = std::max(top_all, lv[(size_t)i]);
-    }
+    for (int l = 1; l <= lv[(size_t)i]; ++l) ix->has_up.push_back(l <= wired_top[(size_t)i] ? 1 : 0);
   }
-  ix->upper.resize((size_t)top_all);
-  for (auto &layer : ix->upper) layer.resize((size_t)n_slots);
-  ix->host_stale = true;
+  ix->exported_fresh = false;
   return HNSW_OK;
 }
 
@@ -2039,7 +1641,7 @@ static int build_insert_gpu_impl(int32_t device, int32_t metric, int64_t n, int3
   std::vector<int32_t> levels;
   rc = draw_levels(seed, 0, n, max_m, given_levels, levels);
   if (rc) return rc;
-  rc = upload_graph(ix.get(), HostGraph());  // no rows, no entry point
+  rc = upload_graph(ix.get(), hnsw_graph::FlatGraph());  // no rows, no entry point
   if (rc) return rc;
   ix->keyed = ids != nullptr;
   rc = insert_rows(ix.get(), n, vectors, ids, levels, ef_construction, batch);
@@ -2100,31 +1702,30 @@ static int append_keys_check(hnsw_index *ix, int64_t n, const int64_t *ids) {
   return HNSW_OK;
 }
 
-// the host copy of the graph behind the device's: every list from the device; a key exists where the host recorded one (loaded,
-// or wired by a build or an append) or where a list is not empty (a back link made it)
-static int refresh_host(const hnsw_index *cix) {
-  if (!cix->host_stale) return HNSW_OK;
-  hnsw_index *ix = const_cast<hnsw_index *>(cix);
+// the graph as an export emits it, in ix->exported: every list from the device, the tables and the flags from the handle.  Kept
+// until an append or an update changes the lists, so that hnsw_index_graph_size and hnsw_index_graph share one read
+// (profiles/README.md, host_graph: a second read costs more than the parent's whole first export did)
+static int read_graph(const hnsw_index *ix) {
   if (ix->broken) return fail(HNSW_EDEVICE, BROKEN);
+  if (ix->exported_fresh) return HNSW_OK;
+  hnsw_graph::FlatGraph &g = ix->exported;
   HTRY(hipSetDevice(ix->device));
-  const int64_t n = ix->n;
-  std::vector<uint32_t> adj0((size_t)n * (ix->m0 + 1));
-  if (n > 0) HTRY(hipMemcpy(adj0.data(), ix->adj0.p, adj0.size() * 4, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; ++i) {
-    const uint32_t *row = &adj0[(size_t)i * (ix->m0 + 1)];
-    ix->level0[(size_t)i].assign(row + 1, row + 1 + row[0]);
-    ix->has0[(size_t)i] |= row[0] > 0 ? 1 : 0;
-  }
-  const int64_t urows = ix->upper_base_h.back();
-  std::vector<uint32_t> uadj((size_t)urows * (ix->m + 1));
-  if (urows > 0) HTRY(hipMemcpy(uadj.data(), ix->upper_adj.p, uadj.size() * 4, hipMemcpyDeviceToHost));
-  for (size_t s = 0; s + 1 < ix->upper_base_h.size(); ++s)
-    for (int l = 1; l <= ix->upper_base_h[s + 1] - ix->upper_base_h[s]; ++l) {
-      const uint32_t *row = uadj.data() + (size_t)(ix->upper_base_h[s] + l - 1) * (ix->m + 1);
-      ix->upper[(size_t)l - 1][s].assign(row + 1, row + 1 + row[0]);
-      ix->has_upper[s][(size_t)l - 1] |= row[0] > 0 ? 1 : 0;
-    }
-  ix->host_stale = false;
+  g.n = ix->n;
+  g.m = ix->m;
+  g.m0 = ix->m0;
+  g.upper_slot = ix->upper_slot_h;
+  g.upper_base = ix->upper_base_h;
+  g.adj0.resize((size_t)g.n * (g.m0 + 1));
+  g.upper_adj.resize((size_t)g.upper_base.back() * (g.m + 1));
+  if (!g.adj0.empty()) HTRY(hipMemcpy(g.adj0.data(), ix->adj0.p, g.adj0.size() * 4, hipMemcpyDeviceToHost));
+  if (!g.upper_adj.empty()) HTRY(hipMemcpy(g.upper_adj.data(), ix->upper_adj.p, g.upper_adj.size() * 4, hipMemcpyDeviceToHost));
+  // A key, once seen, stays a key, like an entry of the reference's map: a list that an export found non-empty keeps its key
+  // on the handle even if an update empties the list later.  This is the one thing an export writes.
+  for (int64_t i = 0; i < g.n; ++i) ix->has0[(size_t)i] |= g.adj0[(size_t)i * (g.m0 + 1)] > 0;
+  for (size_t r = 0; r < ix->has_up.size(); ++r) ix->has_up[r] |= g.upper_adj[r * (g.m + 1)] > 0;
+  g.has0 = ix->has0;
+  g.has_up = ix->has_up;
+  ix->exported_fresh = true;
   return HNSW_OK;
 }
 
@@ -2225,8 +1826,8 @@ static int update_rounds(hnsw_index *ix, const std::vector<uint32_t> &P, const s
     const int32_t sl = ix->upper_slot_h[p];
     const int stor = sl < 0 ? 0 : ix->upper_base_h[(size_t)sl + 1] - ix->upper_base_h[(size_t)sl];
     uint64_t fm = ix->has0[p] ? 1ull : 0ull;
-    for (int l = 1; l <= stor && sl >= 0; ++l)
-      if (ix->has_upper[(size_t)sl][(size_t)l - 1]) fm |= 1ull << l;
+    for (int l = 1; l <= stor && l < 64; ++l)  // (a layer above 63 cannot be named in pkeys either: 6 bits hold the layer)
+      if (ix->has_up[(size_t)(ix->upper_base_h[(size_t)sl] + l - 1)]) fm |= 1ull << l;
     fmask[(size_t)t] = fm;
     const int stop = std::min(stor, ix->max_level);
     pair_off[(size_t)t + 1] = pair_off[(size_t)t] + (int64_t)(stop + 1) * ix->m;
@@ -2319,7 +1920,7 @@ static int update_rounds(hnsw_index *ix, const std::vector<uint32_t> &P, const s
   unsigned long long bs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   HTRY(hipMemcpy(bs, ix->b_bstats.p, sizeof(bs), hipMemcpyDeviceToHost));
   ix->broken = false;
-  ix->host_stale = true;
+  ix->exported_fresh = false;
   ix->upd_rounds = n_rounds;
   ix->upd_empty = (int64_t)bs[3];
   ix->upd_relinks = (int64_t)bs[4];
@@ -2432,19 +2033,9 @@ int hnsw_index_build_stats(const hnsw_index_t *ix, int64_t *rounds, int64_t *uns
 int hnsw_index_graph_size(const hnsw_index_t *ix, int64_t *n_entries, int64_t *n_neighbours, int64_t *entry_point,
                           int32_t *max_level) try {
   if (!ix) return fail(HNSW_EINVAL, "NULL index");
-  if (int rc = refresh_host(ix)) return rc;
+  if (int rc = read_graph(ix)) return rc;
   int64_t ne = 0, nn = 0;
-  for (int64_t i = 0; i < ix->n; ++i)
-    if (ix->has0[(size_t)i]) {
-      ne++;
-      nn += (int64_t)ix->level0[(size_t)i].size();
-    }
-  for (size_t l = 0; l < ix->upper.size(); ++l)
-    for (size_t s = 0; s < ix->upper[l].size(); ++s)
-      if (l < ix->has_upper[s].size() && ix->has_upper[s][l]) {
-        ne++;
-        nn += (int64_t)ix->upper[l][s].size();
-      }
+  hnsw_graph::count_entries(ix->exported, &ne, &nn);
   if (n_entries) *n_entries = ne;
   if (n_neighbours) *n_neighbours = nn;
   if (entry_point) *entry_point = ix->entry;
@@ -2455,23 +2046,8 @@ int hnsw_index_graph_size(const hnsw_index_t *ix, int64_t *n_entries, int64_t *n
 int hnsw_index_graph(const hnsw_index_t *ix, int32_t *entry_level, int64_t *entry_item, int64_t *entry_offsets,
                      int64_t *entry_neighbours) try {
   if (!ix || !entry_level || !entry_item || !entry_offsets) return fail(HNSW_EINVAL, "NULL argument");
-  if (int rc = refresh_host(ix)) return rc;
-  int64_t e = 0, pos = 0;
-  entry_offsets[0] = 0;
-  auto emit = [&](int level, int64_t item, const std::vector<uint32_t> &list) {
-    entry_level[e] = level;
-    entry_item[e] = item;
-    for (uint32_t v : list) entry_neighbours[pos++] = v;
-    entry_offsets[++e] = pos;
-  };
-  for (int64_t i = 0; i < ix->n; ++i)
-    if (ix->has0[(size_t)i]) emit(0, i, ix->level0[(size_t)i]);
-  std::vector<int64_t> slot_item(ix->has_upper.size(), -1);
-  for (int64_t i = 0; i < ix->n; ++i)
-    if (ix->upper_slot_h[(size_t)i] >= 0) slot_item[(size_t)ix->upper_slot_h[(size_t)i]] = i;
-  for (size_t l = 0; l < ix->upper.size(); ++l)
-    for (size_t s = 0; s < ix->upper[l].size(); ++s)
-      if (l < ix->has_upper[s].size() && ix->has_upper[s][l]) emit((int)l + 1, slot_item[s], ix->upper[l][s]);
+  if (int rc = read_graph(ix)) return rc;
+  hnsw_graph::emit_entries(ix->exported, entry_level, entry_item, entry_offsets, entry_neighbours);
   return HNSW_OK;
 } ABI_CATCH
 
