@@ -101,7 +101,7 @@ typedef struct sann_index_info {
   int64_t n_clusters;      /* cluster lists held (including empty ones) */
   int64_t n_postings;      /* postings held by this shard */
   int64_t n_postings_total;/* postings in the lists as given (all shards) */
-  int64_t device_bytes;
+  int64_t device_bytes;    /* postings, ranks, offsets, norms and the id column (8 B per posting, persistent indexes) */
   int32_t n_partitions, shard_id, n_shards, max_list_len;
 } sann_index_info_t;
 
@@ -109,7 +109,10 @@ typedef struct sann_index_info {
  * (ApproximateCosineSimilarity.scala:32,102). */
 typedef struct sann_batch_stats {
   int64_t postings_scanned;  /* sum over queries of sum_c min(len_c, M) within this shard */
-  int64_t algorithmic_bytes; /* P_q*16 + n*12 + k_out*16 summed over queries */
+  /* P_q*16 + n*12 + k_out*16 summed over queries.  The formula is the workload's, not the kernel's: a
+   * cosine batch whose unit kernel gathers the 8-byte id column moves half of P_q*16, so a rate computed from this
+   * number (bench.py's roofline.achieved) is then an EFFECTIVE rate, twice the posting bytes actually moved. */
+  int64_t algorithmic_bytes;
   int32_t n_units;           /* (query, partition) work units launched */
   int32_t n_fallback_units;  /* units re-run on the general (global-memory) path */
   int32_t n_requeried;       /* queries whose first-pass top-k could not be proven exact */
@@ -302,9 +305,16 @@ int sann_debug_phase_cycles(sann_batch_t *batch, int32_t enable, double *avg16);
 /* Measurement only: the fast unit kernel's memory side on its own (same grid, descriptors and posting gather, a
  * checksum instead of the arithmetic), averaged over `reps` launches after a batch has run.  mode 0 = one workgroup
  * per unit, as the unit kernel; mode 1 = persistent workgroups (wgs_per_cu per CU) that load the next unit's postings
- * before they consume the current one.  *checksum is the same for both modes. */
+ * before they consume the current one.  *checksum is the same for both modes.  Modes 2 and 3 are mode 0 over the index's
+ * id column (a checksum of their own): one 8-byte load per posting, and aligned 16-byte pairs of ids with half the slots. */
 int sann_debug_gather_probe(sann_batch_t *batch, int32_t mode, int32_t wgs_per_cu, int32_t reps, double *ms_avg,
                             uint64_t *checksum);
+/* Debug: which gather a batch's unit kernel uses (any may be NULL).  *present: the batch's index has an id column;
+ * *ordinary: its build found every posting's (float)score strictly between 1e-15f and 1e15f; *used_by_last_run: the last
+ * sann_batch_run launched the id form of the unit kernel (cosine forms only, SANN_ID_COLUMN != 0). */
+int sann_debug_id_column(sann_batch_t *batch, int32_t *present, int32_t *ordinary, int32_t *used_by_last_run);
+/* Debug: sann_index_get_list's tweet ids, read from the id column instead of the postings (an error without a column). */
+int sann_debug_index_id_column(const sann_index_t *index, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, int64_t *n);
 /* Debug: per-unit arrays of the last run ([nq * n_partitions] each; any may be NULL): distinct tweets accumulated,
  * candidates emitted, UNIT_* flags, postings scanned. */
 int sann_debug_unit_arrays(sann_batch_t *batch, int32_t *unit_unique, int32_t *cand_cnt, uint32_t *unit_flags, int32_t *unit_T);

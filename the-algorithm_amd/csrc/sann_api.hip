@@ -284,6 +284,7 @@ struct sann_batch {
   int64_t alg_bytes_host = 0;   // host path: n_scan * 12 summed over queries
   bool use_fast = false;
   FastParams fast{};
+  bool id_form_ran = false;  // the last run's unit kernel was the id form (sann_debug_id_column)
   sann_batch_stats_t stats{};
   bool ran = false;
   bool slow_tail_ran = false;  // the last sann_batch_finish re-ran units on the general path (results changed after the first merge)
@@ -468,6 +469,10 @@ static int index_build_impl(const sann_index_options_t *opts, int32_t n_lists, c
     delete ix;
     return fail(SANN_EDEVICE, std::string("index upload: ") + hipGetErrorString(e));
   }
+  if (const int rc = sann_build_id_column(ix)) {
+    delete ix;
+    return rc;
+  }
   *out = ix;
   return SANN_OK;
 }
@@ -491,7 +496,7 @@ int sann_index_info(const sann_index_t *ix, sann_index_info_t *info) try {
   info->n_clusters = (int64_t)ix->cluster_ids.size();
   info->n_postings = ix->n_postings;
   info->n_postings_total = ix->n_postings_total;
-  info->device_bytes = (int64_t)(ix->postings.bytes + ix->ranks.bytes + ix->sub_offsets.bytes + ix->norms.bytes);
+  info->device_bytes = (int64_t)(ix->postings.bytes + ix->ranks.bytes + ix->sub_offsets.bytes + ix->norms.bytes + ix->ids.bytes);
   info->n_partitions = ix->P;
   info->shard_id = ix->shard_id;
   info->n_shards = ix->n_shards;
@@ -499,9 +504,9 @@ int sann_index_info(const sann_index_t *ix, sann_index_info_t *info) try {
   return SANN_OK;
 } ABI_CATCH
 
-int sann_index_get_list(const sann_index_t *ix, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, double *scores,
-                        int32_t *ranks, int64_t *n) try {
-  if (!ix || !n) return fail(SANN_EINVAL, "NULL argument");
+// A cluster's list in rank order, read back from the device: from `postings`, or (ids only) from the id column.
+static int index_get_list(const sann_index_t *ix, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, double *scores,
+                          int32_t *ranks, int64_t *n, bool from_id_column) {
   *n = 0;
   int row = ix->row_of(cluster_id);
   if (row < 0) return SANN_OK;
@@ -512,7 +517,13 @@ int sann_index_get_list(const sann_index_t *ix, int32_t cluster_id, int64_t cap,
   HIP_TRY(hipSetDevice(ix->device));
   std::vector<Posting> p((size_t)len);
   std::vector<uint32_t> r((size_t)len);
-  HIP_TRY(hipMemcpy(p.data(), ix->postings.as<Posting>() + b, (size_t)len * sizeof(Posting), hipMemcpyDeviceToHost));
+  if (from_id_column) {
+    std::vector<int64_t> col((size_t)len);
+    HIP_TRY(hipMemcpy(col.data(), ix->ids.as<int64_t>() + b, (size_t)len * 8, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < len; i++) p[(size_t)i] = Posting{col[(size_t)i], 0.0};
+  } else {
+    HIP_TRY(hipMemcpy(p.data(), ix->postings.as<Posting>() + b, (size_t)len * sizeof(Posting), hipMemcpyDeviceToHost));
+  }
   HIP_TRY(hipMemcpy(r.data(), ix->ranks.as<uint32_t>() + b, (size_t)len * sizeof(uint32_t), hipMemcpyDeviceToHost));
   // sub-lists are concatenated partition by partition; give them back in list (rank) order
   std::vector<int64_t> order((size_t)len);
@@ -525,6 +536,12 @@ int sann_index_get_list(const sann_index_t *ix, int32_t cluster_id, int64_t cap,
     if (ranks) ranks[i] = (int32_t)r[o];
   }
   return SANN_OK;
+}
+
+int sann_index_get_list(const sann_index_t *ix, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, double *scores,
+                        int32_t *ranks, int64_t *n) try {
+  if (!ix || !n) return fail(SANN_EINVAL, "NULL argument");
+  return index_get_list(ix, cluster_id, cap, tweet_ids, scores, ranks, n, false);
 } ABI_CATCH
 
 int sann_index_destroy(sann_index_t *ix) try {
@@ -567,6 +584,7 @@ int batch_reset(sann_batch *b, hipStream_t st, int64_t now_ms, int32_t nq, const
   // ---- O(nq) pass over the arguments: validation, the scan regions' upper bounds, k, M ----------------------------
   int kmax = 1;
   bool any_norms = false;
+  bool all_cosine = true;  // every config is one of the two cosine forms without norms: what the id form serves
   int64_t max_emb = 0, total_ub = 0;
   int max_ub = 0;
   double apriori_mean = 0.0;  // largest expected unit size over the queries (see the geometry note below)
@@ -580,6 +598,7 @@ int batch_reset(sann_batch *b, hipStream_t st, int64_t now_ms, int32_t nq, const
     }
     int k = cfg.max_num_results < 1000 ? cfg.max_num_results : 1000;
     kmax = std::max(kmax, k);
+    all_cosine = all_cosine && (cfg.ann_algorithm == SANN_ALG_COSINE || cfg.ann_algorithm == SANN_ALG_COSINE_NO_SOURCE_NORM);
     if (cfg.ann_algorithm == SANN_ALG_OFFLINE_LOG_COSINE || cfg.ann_algorithm == SANN_ALG_OFFLINE_COSINE) {
       if (!ix->norms.p) return fail(SANN_EINVAL, "offline scoring needs an index built with sann_index_build_with_norms");
       if (variant == SANN_VARIANT_LEGACY) return fail(SANN_EINVAL, "offline scoring is not a form of the legacy variant");
@@ -748,6 +767,13 @@ int batch_reset(sann_batch *b, hipStream_t st, int64_t now_ms, int32_t nq, const
   b->fast.k_local = 0;
   b->fast.max_n_scan = max_ub;
   b->fast.use_norms = any_norms ? 1 : 0;
+  // The id form of the unit kernel: cosine forms only, on an index that has the id column and found every score
+  // ordinary when it built it.  SANN_ID_COLUMN=0 keeps the 16-byte gather (read per batch: tests run both ways).
+  {
+    const char *ov = getenv("SANN_ID_COLUMN");
+    const bool off = ov && ov[0] == '0' && ov[1] == '\0';
+    b->fast.id_form = (n_configs > 0 && all_cosine && !any_norms && ix->ids.p && ix->scores_ordinary && !off) ? 1 : 0;
+  }
 
   if (b->device_prep) {
     // ---- device path: upload the packed inputs, prepare on the GPU ------------------------------------------------
@@ -1048,7 +1074,9 @@ static int batch_run(sann_batch_t *b, void *hip_stream, bool chained, sann_batch
       if (b->profiling) HIP_TRY(hipEventRecord(b->ev[3], st));
       e = launch_unit_fast(b->ix->view(), b->view(), b->fast, b->n_units, st);
       if (e != hipSuccess) return fail(SANN_EDEVICE, std::string("launch_unit_fast: ") + hipGetErrorString(e));
+      b->id_form_ran = b->fast.id_form != 0;
     } else {
+      b->id_form_ran = false;
       std::vector<int32_t> none;
       int rc = run_general(b, none, st);
       if (rc != SANN_OK) return rc;
@@ -1392,6 +1420,21 @@ int sann_debug_gather_probe(sann_batch_t *b, int32_t mode, int32_t wgs_per_cu, i
   *checksum = x;
   *ms_avg = total / reps;
   return SANN_OK;
+} ABI_CATCH
+
+int sann_debug_id_column(sann_batch_t *b, int32_t *present, int32_t *ordinary, int32_t *used_by_last_run) try {
+  if (!b) return fail(SANN_EINVAL, "batch is NULL");
+  if (present) *present = b->ix->ids.p ? 1 : 0;
+  if (ordinary) *ordinary = b->ix->scores_ordinary ? 1 : 0;
+  if (used_by_last_run) *used_by_last_run = (b->ran && b->id_form_ran) ? 1 : 0;
+  return SANN_OK;
+} ABI_CATCH
+
+int sann_debug_index_id_column(const sann_index_t *ix, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, int64_t *n) try {
+  if (!ix || !n) return fail(SANN_EINVAL, "NULL argument");
+  *n = 0;
+  if (!ix->ids.p) return fail(SANN_EINVAL, "the index has no id column");
+  return index_get_list(ix, cluster_id, cap, tweet_ids, nullptr, nullptr, n, true);
 } ABI_CATCH
 
 int sann_debug_unit_arrays(sann_batch_t *b, int32_t *unit_unique, int32_t *cand_cnt, uint32_t *unit_flags, int32_t *unit_T) try {

@@ -418,7 +418,44 @@ GenParams gen_params(const sann_synth_params_t *sp) {
   return g;
 }
 
+// The id column of a finished index: one pass over `postings` that writes the ids (n_pad >= n entries: the padding is
+// zeroed) and reports whether any score falls outside the range the cosine forms of the unit kernel trust -- the same
+// bit-pattern test as theirs: 1e-15f < (float)score < 1e15f; negatives, NaN and inf fall outside.
+__global__ __launch_bounds__(256) void id_column_kernel(const Posting *postings, int64_t n, int64_t n_pad, int64_t *ids,
+                                                        unsigned int *not_ordinary) {
+  constexpr uint32_t LO = 0x26901d7du, HI = 0x58635fa9u;  // 1e-15f, 1e15f
+  bool odd = false;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_pad; i += (int64_t)gridDim.x * 256) {
+    if (i < n) {
+      const Posting p = postings[i];
+      ids[i] = p.id;
+      odd = odd || !((__float_as_uint((float)p.score) - (LO + 1u)) < (HI - LO - 1u));
+    } else {
+      ids[i] = 0;
+    }
+  }
+  if (__ballot(odd) != 0ull && (threadIdx.x & 63) == 0) atomicOr(not_ordinary, 1u);
+}
+
 }  // namespace
+
+int sann_build_id_column(sann_index *ix) {
+  const int64_t n = ix->n_postings;
+  const int64_t n_pad = std::max<int64_t>((n + 1) / 2 * 2, 2);
+  HIP_TRY(hipSetDevice(ix->device));
+  DevBuf d_flag;
+  HIP_TRY(d_flag.alloc(4));
+  HIP_TRY(hipMemset(d_flag.p, 0, 4));
+  HIP_TRY(ix->ids.alloc((size_t)n_pad * 8));
+  const int64_t blocks = std::min<int64_t>((n_pad + 255) / 256, 1 << 16);
+  hipLaunchKernelGGL(id_column_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, ix->postings.as<Posting>(), n, n_pad,
+                     ix->ids.as<int64_t>(), d_flag.as<unsigned int>());
+  HIP_TRY(hipGetLastError());
+  unsigned int flag = 0;
+  HIP_TRY(hipMemcpy(&flag, d_flag.p, 4, hipMemcpyDeviceToHost));
+  ix->scores_ordinary = flag == 0;
+  return SANN_OK;
+}
 
 extern "C" {
 
@@ -569,6 +606,7 @@ int sann_index_build_synthetic(const sann_index_options_t *opts, const sann_synt
                      ix->postings.as<Posting>(), ix->ranks.as<uint32_t>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
+  if (const int rc = sann_build_id_column(ix)) return rc;
   guard.p = nullptr;
   *out = ix;
   return SANN_OK;
@@ -688,6 +726,7 @@ int sann_index_build_from_postings(const sann_index_options_t *opts, int32_t n_l
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipDeviceSynchronize());
+  if (const int rc = sann_build_id_column(ix)) return rc;
   guard.p = nullptr;
   *out = ix;
   return SANN_OK;
@@ -695,6 +734,8 @@ int sann_index_build_from_postings(const sann_index_options_t *opts, int32_t n_l
 
 // An index from lists that are ALREADY on the device and in list order (the cluster-id-range deployment's receiver: the
 // postings the other GPUs sent for this GPU's tweets).  Order inside a list is kept as given; position = rank.
+// Such an index lives for one batch: it gets no id column (a pass over its postings that one step would not earn back)
+// and its batches keep the 16-byte gather.
 int sann_index_build_from_device_postings(const sann_index_options_t *opts, int32_t n_lists, const int32_t *cluster_ids,
                                           const int64_t *list_offsets, const void *d_postings, sann_index_t **out) try {
   if (!out) return fail(SANN_EINVAL, "out is NULL");

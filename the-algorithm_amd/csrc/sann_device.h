@@ -4,6 +4,8 @@
 //
 //   postings[n_postings]        {int64 tweet_id; double score}  16 B, AoS so that one lane = one
 //                               global_load_dwordx4 and a wave instruction covers 1 KiB contiguous
+//   ids[n_postings]             int64: the tweet ids alone, same positions (persistent indexes; +8 B per posting).  The
+//                               cosine forms' unit kernel takes everything it needs of a posting from its id
 //   ranks[n_postings]           uint32: position of the posting in the cluster's full list as the
 //                               store returned it (the `i` of ApproximateCosineSimilarity.scala:87)
 //   sub_offsets[n_rows*P + 1]   uint32 CSR: sub-list (row, p) = postings of cluster `row` whose
@@ -53,6 +55,9 @@ struct IndexView {
   const uint32_t *ranks;
   const uint32_t *sub_offsets;
   const double *norms;  // [n_postings] sum of squares of the posting's tweet's FULL embedding, or NULL (online index)
+  // [n_postings] the tweet ids of `postings`, same positions, or NULL (absent): what the unit kernel's cosine forms gather
+  // instead of the 16-byte postings (8 B per posting; padded to an even count, so an aligned pair may always be read)
+  const int64_t *ids;
   int32_t n_rows;
   int32_t P;      // partitions (power of two)
   int32_t log2P;

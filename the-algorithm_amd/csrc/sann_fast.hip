@@ -18,7 +18,8 @@
 //                   KEY of a single-cluster candidate: (s w) / sqrt(s s) = w, so such a candidate needs no arithmetic)
 //   2. gather       one 16-B global load per posting, consecutive lanes = consecutive postings of a sub-list; all of a
 //                   thread's loads are issued (inline asm: hipcc otherwise waits after each) before the single wait;
-//                   age window and source-tweet filters (:90-91)
+//                   age window and source-tweet filters (:90-91).  The cosine forms on an index with an id column gather
+//                   the 8-byte tweet id alone (the template's IDF): nothing else of a posting is looked at there
 //   3. cluster cut  (cosine forms) the cut is a property of the descriptors: read from the descriptor kernel's output
 //   3a/b. duplicates  a tweet can sit in several scanned clusters (all its postings are in this unit by construction of
 //                   the partition hash).  Each posting ORs four hash bits into one 64-bit word of a blocked Bloom
@@ -199,8 +200,14 @@ __device__ inline void unit_overflowed(int unit, unsigned long long reason) {
   LATE_ARG(overflow_units)[o] = unit;
 }
 
-template <int WG, int U, int NS = NSCAN_MAX, int ABL = 0, bool NORMS = false>
+// IDF = the id form of the cosine forms (FastParams::id_form; every query of the batch has alg 2 or 4 and no norms, and
+// the index vouches that all its scores are ordinary): phase 2 gathers the 8-byte tweet ids of the index's id column
+// instead of the 16-byte postings.  The score half served one test in those forms, the range test of phase 4 -- a
+// property of the index, settled when the column was built -- so s32[] does not exist and half the gather's bytes are
+// never moved.  Who needs a posting's fp64 score (the match list of a flagged unit, the merge kernel) reads the posting.
+template <int WG, int U, int NS = NSCAN_MAX, int ABL = 0, bool NORMS = false, bool IDF = false>
 __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <= 6 ? 8 : U <= 8 ? 5 : U <= 12 ? 3 : 2)) void unit_fast_kernel(IndexView ix, BatchView b, int k_local_floor, int n_blocks_q8) {
+  static_assert(!IDF || (ABL == 0 && !NORMS), "the id form is built for the product's online kernel only");
   constexpr int SCAP = FAST_SCAP;
   constexpr int BW = bloom_log2(WG * U);  // log2 of the Bloom filter's 64-bit words
   constexpr int BLOOM_ALLOC = 1 << BW;
@@ -325,14 +332,14 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
   // fp64 arithmetic.  With the 16-byte form resident, six slots did not fit 80 registers and hipcc kept two of them
   // in scratch memory, re-reading them in every later phase.
   float nrm32[NORMS ? U : 1];  // offline forms: the tweet's full norm, fp32
-  float s32[U];   // posting score, fp32
+  float s32[IDF ? 1 : U];  // posting score, fp32 (the id form has none)
   int seq[U];     // cluster sequence number; bit 16 = group representative (low bits: match-list entry); < 0 = no candidate here
   int live = 0;
   uint32_t hsh[U];  // table_hash of the tweet id (Bloom word and bits): lives until the duplicate phase has looked at it
 #pragma unroll
   for (int u = 0; u < U; u++) {
     seq[u] = -1;
-    s32[u] = 0.f;
+    if constexpr (!IDF) s32[u] = 0.f;
     hsh[u] = 0u;
   }
   {
@@ -342,8 +349,10 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
     // The loads are written as inline asm and waited for by hand.  Left to hipcc, the six 16-byte loads of a thread
     // were given OVERLAPPING destination registers (the id half of one under the score half of the next) with an
     // `s_waitcnt vmcnt(0)` + register copy behind every one of them: six serial trips to memory instead of one.
+    // (id form: the same slots, the same clamping and the same single wait, on 8-byte loads from the id column)
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 raw[U];
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    std::conditional_t<IDF, u32x2, u32x4> raw[U];
     // Every slot loads, unconditionally (a slot the unit does not reach re-reads the unit's last posting: one cache
     // line for the whole wave): the asm outputs then have no other definition they would have to be merged with --
     // a merge is a register copy placed right behind the load, i.e. a read of registers the load has not written yet.
@@ -354,8 +363,13 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
         const uint32_t jj = j < Tg ? j : Tg - 1;
         const int c = (int)s_map[jj];
         seq[u] = (j < Tg) ? c : -1;
-        const Posting *src = ix.postings + (s_off[c] + jj);
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(raw[u]) : "v"(src) : "memory");
+        if constexpr (IDF) {
+          const int64_t *src = ix.ids + (s_off[c] + jj);
+          asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(raw[u]) : "v"(src) : "memory");
+        } else {
+          const Posting *src = ix.postings + (s_off[c] + jj);
+          asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(raw[u]) : "v"(src) : "memory");
+        }
       }
     STAMP(2);  // posting loads issued
     if constexpr (U == 3) asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]) : : "memory");
@@ -380,7 +394,6 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
         // and dropped the -1 for postings outside the age window.
         const bool have = seq[u] >= 0;
         const long long idv = (long long)(((unsigned long long)raw[u].y << 32) | raw[u].x);
-        const double scv = __longlong_as_double((long long)(((unsigned long long)raw[u].w << 32) | raw[u].z));
         const bool excluded = h.excl_enabled != 0 && idv == h.src_excl;  // :90
         const bool in_window = idv >= h.earliest && idv <= h.latest;     // :91
         const bool keep = have && !excluded && in_window;
@@ -395,7 +408,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
           }
         }
         seq[u] = keep_n ? seq[u] : -1;
-        s32[u] = (float)scv;
+        if constexpr (!IDF) s32[u] = (float)__longlong_as_double((long long)(((unsigned long long)raw[u].w << 32) | raw[u].z));
         live += __popcll(__ballot(keep_n));  // wave count, identical in all lanes
         hsh[u] = table_hash(idv, HB);
       }
@@ -688,19 +701,25 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
           k32[u] = lv ? (__float_as_uint(a) | 0x80000000u) : 0u;
         }
       }
-    } else if (h.alg == 2 || h.alg == 4) {
+    } else if (IDF || h.alg == 2 || h.alg == 4) {
+      // (id form: that every query of the batch is a cosine form is the launcher's promise -- checked, not trusted: a unit
+      // of any other form goes to the general path)
+      if constexpr (IDF) bad = !(h.alg == 2 || h.alg == 4);
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const bool lv = seq[u] >= 0;
         const uint32_t wk = s_wkey[seq[u] & (NS - 1)];  // (dead slots and representatives read some entry: unused)
         // the shortcut is only trusted for ordinary positive magnitudes (s32^2 within the fp32 range, w / l2norm too):
-        // 1e-15 < s32 < 1e15 as one unsigned compare of the bit pattern (negatives, NaN and inf fall outside)
+        // 1e-15 < s32 < 1e15 as one unsigned compare of the bit pattern (negatives, NaN and inf fall outside).  The id form
+        // runs only on an index whose every posting passed this very test when the id column was built.
         constexpr uint32_t LO = 0x26901d7du, HI = 0x58635fa9u;  // 1e-15f, 1e15f
-        const bool ordinary = (__float_as_uint(s32[u]) - (LO + 1u)) < (HI - LO - 1u);
+        bool ordinary = true;
+        if constexpr (!IDF) ordinary = (__float_as_uint(s32[u]) - (LO + 1u)) < (HI - LO - 1u);
         bad = bad || ((uint32_t)seq[u] < 0x10000u && !(ordinary && wk != 0u));
         k32[u] = lv ? wk : 0u;
       }
-    } else if (h.alg == 1) {
+    } else if constexpr (!IDF) {  // (the other forms' keys are made of the score: no part of the id form)
+    if (h.alg == 1) {
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const bool lv = seq[u] >= 0;
@@ -729,6 +748,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
         bad = bad || (lv && !(seq[u] & 0x10000) && !forced && !(a > 1e-30f && a < 1e30f && sv > 1e-15f && sv < 1e15f));
         k32[u] = lv ? (forced ? FORCED_KEY : (__float_as_uint(a) | 0x80000000u)) : 0u;
       }
+    }
     }
     if (!overflow && s_ctl[CTL_NFLAG] != 0) {  // uniform: only units that resolved duplicates can hold representatives
       const float invl2 = h.inv_l2_32, invln = h.inv_ln_32;
@@ -960,6 +980,12 @@ static hipError_t launch_one(const IndexView &ix, const BatchView &b, const Fast
       hipLaunchKernelGGL((unit_fast_kernel<WG, U, 64, 0, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
     else
       hipLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX, 0, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+  } else if (fp.id_form) {
+    if (!ix.ids) return hipErrorInvalidValue;  // (set only for an index that has the column)
+    if (fp.max_n_scan <= 64)
+      hipLaunchKernelGGL((unit_fast_kernel<WG, U, 64, 0, false, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+    else
+      hipLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX, 0, false, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
   } else if (fp.max_n_scan <= 64)
     hipLaunchKernelGGL((unit_fast_kernel<WG, U, 64>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
   else

@@ -63,6 +63,11 @@ int sann_candidates_pooled(sann_index_t *index, int32_t variant, int64_t now_ms,
                            int32_t n_configs, const int64_t *scan_offsets, const int32_t *scan_cluster_ids, int64_t *out_ids,
                            double *out_scores, int32_t out_stride, int32_t *out_counts, int32_t *out_map_sizes);
 
+struct sann_index;
+// Builds ix->ids and ix->scores_ordinary from ix->postings (one pass on the device; sann_corpus.hip).  Called last by
+// the builders of persistent indexes.
+int sann_build_id_column(sann_index *ix);
+
 struct sann_index {
   int device = 0;
   int P = 1, log2P = 0, shard_id = 0, n_shards = 1;
@@ -71,6 +76,11 @@ struct sann_index {
   int64_t n_postings = 0, n_postings_total = 0;
   int32_t max_list_len = 0;
   sann_host::DevBuf postings, ranks, sub_offsets, norms;
+  // The id column (IndexView::ids) of a persistent index, and what its build pass found out about the scores on the
+  // way: every posting's (float)score lies strictly between 1e-15f and 1e15f -- the range test the cosine forms of the
+  // unit kernel apply to a posting's score, and the only thing they take from it.  Both set by sann_build_id_column.
+  sann_host::DevBuf ids;
+  bool scores_ordinary = false;
   // cut cache: for a given maxTopTweetsPerCluster M, the number of postings with rank < M in every
   // (row, partition) sub-list.  M is a service-level constant in practice, so this is built once
   // (one binary search per sub-list, on the device) and reused by every batch.
@@ -107,6 +117,7 @@ struct sann_index {
     v.ranks = ranks.as<uint32_t>();
     v.sub_offsets = sub_offsets.as<uint32_t>();
     v.norms = norms.as<double>();
+    v.ids = ids.as<int64_t>();
     v.n_rows = (int32_t)cluster_ids.size();
     v.P = P;
     v.log2P = log2P;

@@ -65,6 +65,9 @@ struct FastParams {
   int k_local;        // floor on the entries a unit must offer before it may withhold the rest
   int max_n_scan;     // largest number of scanned clusters of any query of the batch
   int use_norms;      // some query of the batch scores with the index's norms column (offline forms)
+  // every query of the batch is a cosine form without norms (alg 2 or 4) and the index has an id column whose build found
+  // all scores ordinary: the unit kernel gathers 8-byte ids instead of 16-byte postings (unit_fast_kernel's IDF)
+  int id_form;
 };
 hipError_t launch_cut(const IndexView &ix, int M, uint32_t *out, hipStream_t stream);
 hipError_t launch_desc(const IndexView &ix, const BatchView &b, int n_units, int max_n_scan, int k_local_floor, hipStream_t stream);

@@ -41,8 +41,29 @@ __device__ inline unsigned long long wave_xor(unsigned long long v) {
 }
 }  // namespace
 
-// (a) one workgroup per unit, as the unit kernel
-template <int WG, int U>
+// One hand-written wait for all of a thread's loads (N registers sets written by inline-asm loads), as the unit kernel's.
+template <class R, int N>
+__device__ inline void wait_loads(R (&raw)[N]) {
+  static_assert(N == 2 || N == 3 || N == 4 || N == 6 || N == 8, "probe geometries");
+  if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw[0]), "+v"(raw[1]) : : "memory");
+  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]) : : "memory");
+  else if constexpr (N == 6)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]), "+v"(raw[4]), "+v"(raw[5]) : : "memory");
+  else {
+#pragma unroll
+    for (int u0 = 0; u0 < N; u0 += 4)
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw[u0]), "+v"(raw[u0 + 1]), "+v"(raw[u0 + 2]), "+v"(raw[u0 + 3]) : : "memory");
+  }
+}
+
+// (a) one workgroup per unit, as the unit kernel.  FORM: what is gathered per posting --
+//   0  the 16-byte posting (what unit_fast_kernel's 16-byte form reads);
+//   1  the 8-byte id from the id column, one global_load_dwordx2 per posting, all of a thread's loads before one wait;
+//   2  the id column in 16-byte pieces: a lane loads the ALIGNED pair of ids that holds posting 2i of the unit and takes
+//      half as many slots.  (A measurement of the access shape: where posting 2i + 1 starts another sub-list, or 2i sits
+//      at an odd position, its neighbour in memory is loaded instead -- a real kernel would need a second load there,
+//      about one pair in ten at 25 postings per sub-list.)
+template <int WG, int U, int FORM = 0>
 __global__ __launch_bounds__(WG) void probe_unit_kernel(IndexView ix, BatchView b, unsigned long long *out) {
   __shared__ uint32_t s_begin[NSCAN_MAX_P], s_pre[NSCAN_MAX_P];
   __shared__ uint8_t s_map[WG * U];
@@ -59,18 +80,57 @@ __global__ __launch_bounds__(WG) void probe_unit_kernel(IndexView ix, BatchView 
   T = T < (uint32_t)(WG * U) ? T : (uint32_t)(WG * U);
   build_map<WG, U>(ix, b, q, p, h, s_begin, s_pre, s_map, T);
   __syncthreads();
-  Posting pst[U];
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    const uint32_t j = (uint32_t)(u * WG + tid);
-    const uint32_t jj = j < T ? j : (T ? T - 1 : 0);
-    const int c = (int)s_map[jj];
-    pst[u] = T ? ix.postings[s_begin[c] + (jj - s_pre[c])] : Posting{0, 0.0};
-  }
   unsigned long long acc = 0;
+  if constexpr (FORM == 0) {
+    Posting pst[U];
 #pragma unroll
-  for (int u = 0; u < U; u++)
-    if ((uint32_t)(u * WG + tid) < T) acc ^= (unsigned long long)pst[u].id ^ (unsigned long long)__double_as_longlong(pst[u].score);
+    for (int u = 0; u < U; u++) {
+      const uint32_t j = (uint32_t)(u * WG + tid);
+      const uint32_t jj = j < T ? j : (T ? T - 1 : 0);
+      const int c = (int)s_map[jj];
+      pst[u] = T ? ix.postings[s_begin[c] + (jj - s_pre[c])] : Posting{0, 0.0};
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      if ((uint32_t)(u * WG + tid) < T) acc ^= (unsigned long long)pst[u].id ^ (unsigned long long)__double_as_longlong(pst[u].score);
+  } else if constexpr (FORM == 1) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    if (T != 0u) {  // (uniform)
+      u32x2 raw[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const uint32_t j = (uint32_t)(u * WG + tid);
+        const uint32_t jj = j < T ? j : T - 1;
+        const int c = (int)s_map[jj];
+        const int64_t *src = ix.ids + (s_begin[c] + (jj - s_pre[c]));
+        asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(raw[u]) : "v"(src) : "memory");
+      }
+      wait_loads(raw);
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if ((uint32_t)(u * WG + tid) < T) acc ^= ((unsigned long long)raw[u].y << 32) | raw[u].x;
+    }
+  } else {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int NP = (U + 1) / 2;  // pair slots
+    if (T != 0u) {  // (uniform)
+      u32x4 raw[NP];
+#pragma unroll
+      for (int u = 0; u < NP; u++) {
+        const uint32_t j = 2u * (uint32_t)(u * WG + tid);
+        const uint32_t jj = j < T ? j : T - 1;
+        const int c = (int)s_map[jj];
+        // (the column is padded to an even number of ids: the aligned pair of any held position may be read)
+        const int64_t *src = ix.ids + ((s_begin[c] + (jj - s_pre[c])) & ~1u);
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(raw[u]) : "v"(src) : "memory");
+      }
+      wait_loads(raw);
+#pragma unroll
+      for (int u = 0; u < NP; u++)
+        if (2u * (uint32_t)(u * WG + tid) < T)
+          acc ^= (((unsigned long long)raw[u].y << 32) | raw[u].x) ^ (((unsigned long long)raw[u].w << 32) | raw[u].z);
+    }
+  }
   acc = wave_xor(acc);
   if ((tid & 63) == 0) atomicXor(&out[unit], acc);
 }
@@ -139,10 +199,13 @@ hipError_t launch_gather_probe(const IndexView &ix, const BatchView &b, int unit
   const int nq8 = (b.nq + 7) / 8 * 8;
   const int n_blocks = nq8 * ix.P;
   if (n_blocks <= 0) return hipSuccess;
+  if ((mode == 2 || mode == 3) && !ix.ids) return hipErrorInvalidValue;  // (the id forms need the column)
   const int grid_p = ((256 * wgs_per_cu + 7) / 8) * 8;
 #define PROBE(WG, U)                                                                                                  \
   do {                                                                                                                \
     if (mode == 0) hipLaunchKernelGGL((probe_unit_kernel<WG, U>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, out);     \
+    else if (mode == 2) hipLaunchKernelGGL((probe_unit_kernel<WG, U, 1>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, out); \
+    else if (mode == 3) hipLaunchKernelGGL((probe_unit_kernel<WG, U, 2>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, out); \
     else hipLaunchKernelGGL((probe_persistent_kernel<WG, U>), dim3(grid_p < n_blocks ? grid_p : n_blocks), dim3(WG), 0, stream, ix, b, out, n_blocks); \
   } while (0)
   switch (unit_capacity) {

@@ -184,6 +184,8 @@ _PROTOS = {
     "sann_debug_plan_slow_tail": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sann_debug_gather_probe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "sann_debug_unit_arrays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sann_debug_id_column": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sann_debug_index_id_column": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     "sann_debug_phase_cycles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
     "sann_batch_destroy": (C.c_int, [C.c_void_p]),
     "sann_get_tweet_candidates": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -428,6 +430,16 @@ class ClusterTweetIndex:
             _check(lib.sann_index_get_list(self._h, cluster_id, n.value, _ptr(t), _ptr(s), _ptr(r), C.byref(n)))
         return t, s, r
 
+    def id_column_list(self, cluster_id: int) -> np.ndarray:
+        """sann_debug_index_id_column: get_list's tweet ids, read from the index's id column (SannError without one)."""
+        lib = load_library()
+        n = C.c_int64()
+        _check(lib.sann_debug_index_id_column(self._h, cluster_id, 0, None, C.byref(n)))
+        t = np.empty(n.value, np.int64)
+        if n.value:
+            _check(lib.sann_debug_index_id_column(self._h, cluster_id, n.value, _ptr(t), C.byref(n)))
+        return t
+
     def close(self):
         if self._h:
             load_library().sann_index_destroy(self._h)
@@ -563,6 +575,13 @@ class QueryBatch:
         f = np.zeros((self.nq, P), np.uint32)
         _check(load_library().sann_debug_unit_arrays(self._h, _ptr(u), _ptr(c), _ptr(f), _ptr(t)))
         return t, u, c, f
+
+    def id_column(self) -> Tuple[bool, bool, bool]:
+        """sann_debug_id_column: (the index has an id column, its build found every score ordinary, the last run() used
+        the id form of the unit kernel)."""
+        p, o, u = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(load_library().sann_debug_id_column(self._h, C.byref(p), C.byref(o), C.byref(u)))
+        return bool(p.value), bool(o.value), bool(u.value)
 
     def overflow_reasons(self) -> np.ndarray:
         """sann_debug_overflow_reasons: units flagged UNIT_OVERFLOW by reason (1 scanned clusters, 2 postings, 3 match
