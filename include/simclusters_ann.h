@@ -313,6 +313,11 @@ int sann_debug_gather_probe(sann_batch_t *batch, int32_t mode, int32_t wgs_per_c
  * *ordinary: its build found every posting's (float)score strictly between 1e-15f and 1e15f; *used_by_last_run: the last
  * sann_batch_run launched the id form of the unit kernel (cosine forms only, SANN_ID_COLUMN != 0). */
 int sann_debug_id_column(sann_batch_t *batch, int32_t *present, int32_t *ordinary, int32_t *used_by_last_run);
+/* Debug: the geometry of a batch's unit kernel (either may be NULL).  *waves_of_last_run: waves per unit of the unit kernel
+ * the last sann_batch_run launched -- 2 for the two-wave units of the id form at capacity 1536 (SANN_UNIT_WAVES=4 keeps
+ * the four-wave units there), else 1, 2 or 4 by the capacity; 0 if no run launched the fast path.  *unit_capacity: the
+ * postings a unit holds, as chosen when the batch was prepared. */
+int sann_debug_unit_waves(sann_batch_t *batch, int32_t *waves_of_last_run, int32_t *unit_capacity);
 /* Debug: sann_index_get_list's tweet ids, read from the id column instead of the postings (an error without a column). */
 int sann_debug_index_id_column(const sann_index_t *index, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, int64_t *n);
 /* Debug: per-unit arrays of the last run ([nq * n_partitions] each; any may be NULL): distinct tweets accumulated,

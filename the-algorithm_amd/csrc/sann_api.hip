@@ -285,6 +285,7 @@ struct sann_batch {
   bool use_fast = false;
   FastParams fast{};
   bool id_form_ran = false;  // the last run's unit kernel was the id form (sann_debug_id_column)
+  int unit_waves_ran = 0;    // waves per unit of the last run's unit kernel; 0 = it ran none (sann_debug_unit_waves)
   sann_batch_stats_t stats{};
   bool ran = false;
   bool slow_tail_ran = false;  // the last sann_batch_finish re-ran units on the general path (results changed after the first merge)
@@ -774,6 +775,14 @@ int batch_reset(sann_batch *b, hipStream_t st, int64_t now_ms, int32_t nq, const
     const bool off = ov && ov[0] == '0' && ov[1] == '\0';
     b->fast.id_form = (n_configs > 0 && all_cosine && !any_norms && ix->ids.p && ix->scores_ordinary && !off) ? 1 : 0;
   }
+  // The two-wave units, unit_fast_kernel<128, 12>: the id form at capacity 1536, the one place that instantiation exists.
+  // Settled where the capacity is (both paths below).  SANN_UNIT_WAVES=4 keeps the four-wave <256, 6>; 2 asks for what is
+  // the default anyway and has no effect where the form does not exist (read per batch, like SANN_ID_COLUMN).
+  auto choose_unit_waves = [&]() {
+    const char *ov = getenv("SANN_UNIT_WAVES");
+    const bool four = ov && ov[0] == '4' && ov[1] == '\0';
+    b->fast.two_wave = (b->fast.id_form && b->fast.unit_capacity == 1536 && !four) ? 1 : 0;
+  };
 
   if (b->device_prep) {
     // ---- device path: upload the packed inputs, prepare on the GPU ------------------------------------------------
@@ -789,6 +798,7 @@ int batch_reset(sann_batch *b, hipStream_t st, int64_t now_ms, int32_t nq, const
     if (hint > 0) ucap = std::min(ucap, geometry_for((double)hint + 2.0 * std::sqrt((double)hint)));
     if (const char *ov = getenv("SANN_UNIT_CAP")) ucap = atoi(ov);  // tuning / test override
     b->fast.unit_capacity = ucap;
+    choose_unit_waves();
     HIP_TRY(ix->ensure_device_cluster_ids());
     if (nq > 0) {
       HIP_TRY(b->d_stage.reserve(L.bytes));
@@ -877,6 +887,7 @@ int batch_reset(sann_batch *b, hipStream_t st, int64_t now_ms, int32_t nq, const
     if (const char *ov = getenv("SANN_UNIT_CAP")) ucap = atoi(ov);
     b->fast.unit_capacity = ucap;
     b->fast.max_n_scan = max_n_scan;
+    choose_unit_waves();
   }
   if (nq > 0) {
     HIP_TRY(hipMemcpyAsync(b->hdr.p, b->h_hdr.data(), (size_t)nq * sizeof(QueryHdr), hipMemcpyHostToDevice, st));
@@ -1075,8 +1086,11 @@ static int batch_run(sann_batch_t *b, void *hip_stream, bool chained, sann_batch
       e = launch_unit_fast(b->ix->view(), b->view(), b->fast, b->n_units, st);
       if (e != hipSuccess) return fail(SANN_EDEVICE, std::string("launch_unit_fast: ") + hipGetErrorString(e));
       b->id_form_ran = b->fast.id_form != 0;
+      // (launch_unit_fast's geometries: <64, 4>, <128, 4>, then 256 threads)
+      b->unit_waves_ran = b->fast.two_wave ? 2 : b->fast.unit_capacity <= 256 ? 1 : b->fast.unit_capacity <= 512 ? 2 : 4;
     } else {
       b->id_form_ran = false;
+      b->unit_waves_ran = 0;
       std::vector<int32_t> none;
       int rc = run_general(b, none, st);
       if (rc != SANN_OK) return rc;
@@ -1427,6 +1441,13 @@ int sann_debug_id_column(sann_batch_t *b, int32_t *present, int32_t *ordinary, i
   if (present) *present = b->ix->ids.p ? 1 : 0;
   if (ordinary) *ordinary = b->ix->scores_ordinary ? 1 : 0;
   if (used_by_last_run) *used_by_last_run = (b->ran && b->id_form_ran) ? 1 : 0;
+  return SANN_OK;
+} ABI_CATCH
+
+int sann_debug_unit_waves(sann_batch_t *b, int32_t *waves_of_last_run, int32_t *unit_capacity) try {
+  if (!b) return fail(SANN_EINVAL, "batch is NULL");
+  if (waves_of_last_run) *waves_of_last_run = b->ran ? b->unit_waves_ran : 0;
+  if (unit_capacity) *unit_capacity = b->fast.unit_capacity;
   return SANN_OK;
 } ABI_CATCH
 

@@ -12,7 +12,8 @@
 // unit_fast_kernel   one workgroup = one unit; the unit's postings live in REGISTERS (U per thread: an fp32 copy of
 //               the score, the cluster's sequence number and a hash of the id -- the fp64 posting is read again only for
 //               survivors, by the MERGE kernel).  What bounds it is the time a workgroup holds its slot -- a chain of
-//               dependent memory trips -- at eight workgroups per CU (<= 64 VGPRs, 20 KB LDS, <= 80 SGPRs):
+//               dependent memory trips -- at eight workgroups per CU (<= 64 VGPRs, 20 KB LDS, <= 80 SGPRs); the id form
+//               at 1536 postings runs as TWO-wave units, fourteen per CU (56 VGPRs, 11.3 KB LDS: see two_wave_unit):
 //   1. descriptors  header, (start, prefix) row, cluster weights and posting count in ONE trip; byte map flat posting
 //                   index -> cluster; per-cluster constants (fp64 weight, fp32 weight, and for the cosine forms the fp32
 //                   KEY of a single-cluster candidate: (s w) / sqrt(s s) = w, so such a candidate needs no arithmetic)
@@ -205,15 +206,24 @@ __device__ inline void unit_overflowed(int unit, unsigned long long reason) {
 // instead of the 16-byte postings.  The score half served one test in those forms, the range test of phase 4 -- a
 // property of the index, settled when the column was built -- so s32[] does not exist and half the gather's bytes are
 // never moved.  Who needs a posting's fp64 score (the match list of a flagged unit, the merge kernel) reads the posting.
+// The TWO-WAVE unit of the benchmark's 1536-posting capacity, <128, 12> in the id form (FastParams::two_wave): fixed per-wave
+// work is paid twice per unit instead of four times, two waves meet at a barrier sooner than four, and with the 8 KB
+// filter (bloom_bits6) and without the fp32 weights the id form never reads, a unit needs 11.3 KB of LDS: fourteen units
+// per CU (seven waves per SIMD) where <256, 6> holds eight.
+template <int WG, int U, bool IDF> constexpr bool two_wave_unit = IDF && WG == 128 && U == 12;
 template <int WG, int U, int NS = NSCAN_MAX, int ABL = 0, bool NORMS = false, bool IDF = false>
-__global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <= 6 ? 8 : U <= 8 ? 5 : U <= 12 ? 3 : 2)) void unit_fast_kernel(IndexView ix, BatchView b, int k_local_floor, int n_blocks_q8) {
+__global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <= 6 ? 8 : U <= 8 ? 5 : U <= 12 ? 3 : 2)) void unit_fast_kernel(IndexView ix, BatchView b, int k_local_floor, int n_blocks_q8) {
   static_assert(!IDF || (ABL == 0 && !NORMS), "the id form is built for the product's online kernel only");
   constexpr int SCAP = FAST_SCAP;
-  constexpr int BW = bloom_log2(WG * U);  // log2 of the Bloom filter's 64-bit words
+  constexpr bool B8K = two_wave_unit<WG, U, IDF>;  // the 8 KB filter: six bits of a word, made of all 32 hash bits
+  constexpr int BW = B8K ? BLOOM8K_LOG2 : bloom_log2(WG * U);  // log2 of the Bloom filter's 64-bit words
   constexpr int BLOOM_ALLOC = 1 << BW;
-  constexpr int HB = BLOOM_POS_BITS + BW;  // hash bits: 4 x 5 bit positions, then the word index
-  constexpr int FBLOOM_WORDS = BW >= 11 ? 64 : 256;  // (beside the 16 KB Bloom filter: 64, so that eight workgroups fit a CU)
-  constexpr int FB = BW >= 11 ? 6 : 8;
+  constexpr int HB = B8K ? 32 : BLOOM_POS_BITS + BW;  // hash bits: 4 x 5 bit positions, then the word index (8 KB form: all)
+  constexpr int FBLOOM_WORDS = (B8K || BW >= 11) ? 64 : 256;  // (beside the 16 KB Bloom filter: 64, so that eight workgroups fit a CU)
+  constexpr int FB = (B8K || BW >= 11) ? 6 : 8;
+  // a posting's word of the filter (the top BW hash bits) and its bits in that word and in the flagged filter's
+  auto bloom_word = [](uint32_t hv) { return B8K ? hv >> (32 - BW) : hv >> BLOOM_POS_BITS; };
+  auto bloom_mask = [](uint32_t hv) { return B8K ? bloom_bits6(hv) : bloom_bits(hv); };
   constexpr int MCAP = (WG * U <= 1024) ? 64 : 128;
   constexpr int SHORT_NM = 12;  // match lists up to here are settled by every wave for itself; the sorted path starts above
   __shared__ unsigned long long s_bloom[BLOOM_ALLOC];
@@ -222,7 +232,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
   __shared__ uint32_t s_off[NS];
   __shared__ uint8_t s_map[WG * U];  // flat posting index -> cluster sequence number
   __shared__ double s_w[NS];
-  __shared__ float s_w32[NS];
+  __shared__ float s_w32[B8K ? 1 : NS];  // (fp32 weights: the keys of the other forms; the id form reads none)
   __shared__ uint32_t s_wkey[NS];  // cosine forms: the fp32 key of a single-cluster candidate of the cluster (0 = untrusted)
   __shared__ unsigned long long s_fbloom[FBLOOM_WORDS];
   // The survivor list, the radix histogram / lane maxima and the match list of the duplicate phase are first touched
@@ -292,7 +302,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
         const double w = wq[c];
         s_off[c] = v.x - v.y;
         s_w[c] = w;
-        s_w32[c] = (float)w;
+        if constexpr (!B8K) s_w32[c] = (float)w;
         s_wkey[c] = cosine_cluster_key(h.alg, w, inv_l2_32);
       }
       // every posting of this cluster records its cluster in the flat map (an oversized unit stops at the map's end;
@@ -422,8 +432,8 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
       seen[u] = 0ull;
       if ((uint32_t)(u * WG) < Tg && seq[u] >= 0) {
         const uint32_t hv = hsh[u];
-        const unsigned long long bits = bloom_bits(hv);
-        seen[u] = ~atomicOr(&s_bloom[hv >> BLOOM_POS_BITS], bits) & bits;  // bits of this posting that were NOT set before
+        const unsigned long long bits = bloom_mask(hv);
+        seen[u] = ~atomicOr(&s_bloom[bloom_word(hv)], bits) & bits;  // bits of this posting that were NOT set before
       }
     }
 #pragma unroll
@@ -431,7 +441,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
       if ((uint32_t)(u * WG) < Tg && seq[u] >= 0 && seen[u] == 0ull) {
         // possibly seen before: mark the id's bits in the (sparse) "flagged" filter
         const uint32_t hv = hsh[u];
-        const unsigned long long bits = bloom_bits(hv);
+        const unsigned long long bits = bloom_mask(hv);
         atomicOr(&s_fbloom[hv >> (HB - FB)], bits);
         s_ctl[CTL_NFLAG] = 1;
       }
@@ -477,7 +487,7 @@ __global__ __launch_bounds__(WG, (WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <=
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t hv = hsh[u];
-      const unsigned long long bits = bloom_bits(hv);
+      const unsigned long long bits = bloom_mask(hv);
       const bool hit = seq[u] >= 0 && (s_fbloom[hv >> (HB - FB)] & bits) == bits;
       mi[u] = -1;
       if constexpr (ONE_TRIP) pm[u] = Posting{0, 0.0};
@@ -993,6 +1003,19 @@ static hipError_t launch_one(const IndexView &ix, const BatchView &b, const Fast
   return hipGetLastError();
 }
 
+// the two-wave unit of 1536 postings exists in the id form only (FastParams::two_wave is never set without id_form)
+static hipError_t launch_two_wave(const IndexView &ix, const BatchView &b, const FastParams &fp, hipStream_t stream) {
+  const int nq8 = (b.nq + 7) / 8 * 8;
+  const int n_blocks = nq8 * ix.P;
+  if (b.desc_stride != desc_row_stride(fp.max_n_scan)) return hipErrorInvalidValue;
+  if (!fp.id_form || fp.use_norms || !ix.ids) return hipErrorInvalidValue;
+  if (fp.max_n_scan <= 64)
+    hipLaunchKernelGGL((unit_fast_kernel<128, 12, 64, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+  else
+    hipLaunchKernelGGL((unit_fast_kernel<128, 12, NSCAN_MAX, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+  return hipGetLastError();
+}
+
 // The same descriptors, one WORKGROUP per query (P <= 32): the n_scan x P sub-lists of a query are resolved by 256
 // threads in three dependent trips to memory -- the header; the scan rows of up to DESC_SLOTS sub-lists per thread
 // (and the weights the key sort reads); their starts and cuts, partition-contiguous (coalesced) reads of the offset
@@ -1298,7 +1321,7 @@ hipError_t launch_unit_fast(const IndexView &ix, const BatchView &b, const FastP
     case 512: return launch_one<128, 4>(ix, b, fp, stream);
     case 768: return launch_one<256, 3>(ix, b, fp, stream);
     case 1024: return launch_one<256, 4>(ix, b, fp, stream);
-    case 1536: return launch_one<256, 6>(ix, b, fp, stream);
+    case 1536: return fp.two_wave ? launch_two_wave(ix, b, fp, stream) : launch_one<256, 6>(ix, b, fp, stream);
     case 2048: return launch_one<256, 8>(ix, b, fp, stream);
     case 3072: return launch_one<256, 12>(ix, b, fp, stream);
     case 4096: return launch_one<256, 16>(ix, b, fp, stream);

@@ -68,6 +68,9 @@ struct FastParams {
   // every query of the batch is a cosine form without norms (alg 2 or 4) and the index has an id column whose build found
   // all scores ordinary: the unit kernel gathers 8-byte ids instead of 16-byte postings (unit_fast_kernel's IDF)
   int id_form;
+  // the id form at unit_capacity 1536 runs as two-wave units, unit_fast_kernel<128, 12>, not as <256, 6> (SANN_UNIT_WAVES=4
+  // keeps the four-wave units); 0 wherever that instantiation does not exist
+  int two_wave;
 };
 hipError_t launch_cut(const IndexView &ix, int M, uint32_t *out, hipStream_t stream);
 hipError_t launch_desc(const IndexView &ix, const BatchView &b, int n_units, int max_n_scan, int k_local_floor, hipStream_t stream);

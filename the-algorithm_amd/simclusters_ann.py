@@ -185,6 +185,7 @@ _PROTOS = {
     "sann_debug_gather_probe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "sann_debug_unit_arrays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sann_debug_id_column": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sann_debug_unit_waves": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sann_debug_index_id_column": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     "sann_debug_phase_cycles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
     "sann_batch_destroy": (C.c_int, [C.c_void_p]),
@@ -582,6 +583,13 @@ class QueryBatch:
         p, o, u = C.c_int32(), C.c_int32(), C.c_int32()
         _check(load_library().sann_debug_id_column(self._h, C.byref(p), C.byref(o), C.byref(u)))
         return bool(p.value), bool(o.value), bool(u.value)
+
+    def unit_waves(self) -> Tuple[int, int]:
+        """sann_debug_unit_waves: (waves per unit of the unit kernel the last run() launched -- 2 for the two-wave units
+        of the id form at capacity 1536, 0 if it launched none --, the batch's unit capacity)."""
+        w, c = C.c_int32(), C.c_int32()
+        _check(load_library().sann_debug_unit_waves(self._h, C.byref(w), C.byref(c)))
+        return int(w.value), int(c.value)
 
     def overflow_reasons(self) -> np.ndarray:
         """sann_debug_overflow_reasons: units flagged UNIT_OVERFLOW by reason (1 scanned clusters, 2 postings, 3 match

@@ -27,6 +27,8 @@ avg = (C.c_double * 16)()
 assert lib.sann_debug_phase_cycles(qb._h, 0, avg) == 0
 names = ["total", "desc+scan", "issue loads", "wait loads+filter+bloom", "dup resolve", "approx+minmax", "threshold",
          "compact", "exact+emit"]
+if hasattr(qb, "unit_waves"):  # (SANN_UNIT_WAVES=4 keeps the four-wave units where the two-wave form exists)
+    print("unit kernel: waves per unit %d, unit capacity %d" % qb.unit_waves())
 print("P", P, "units counted", int(avg[15]))
 for i, n in enumerate(names):
     print(f"  {n:28s} {avg[i]:10.0f} clk")
