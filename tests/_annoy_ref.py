@@ -6,20 +6,14 @@ import heapq
 
 import numpy as np
 
-from _ivf_ref import ATOL, COSINE, L2, RTOL, clear_positions, distances, prepare  # noqa: F401
+from _ivf_ref import ATOL, COSINE, L2, RTOL, clear_positions, distances, low_dimensional, prepare  # noqa: F401
+from _refine_ref import rerank
 
 SPLIT, LEAF, FALLBACK = 0, 1, 1
 
 # the input of the quality test: measured without a device (see test_annoy_gpu.test_quality), run on one there
 QUALITY = dict(n=4000, d=64, nq=64, n_trees=20, k=10, seed=11)
 QUALITY_NUMPY_SEEDS = tuple(range(8))
-
-
-def low_dimensional(rng, n, d, r=3, eps=0.3):
-    """The rows of tests/test_refine_gpu.py (_low_dimensional): r latent dimensions under a random linear map plus eps N(0,1)
-    per component, whose distances spread instead of concentrating."""
-    basis = rng.standard_normal((r, d)) / np.sqrt(r)
-    return (rng.standard_normal((n, r)) @ basis + eps * rng.standard_normal((n, d))).astype(np.float32)
 
 
 def pad8(x):
@@ -123,21 +117,9 @@ def walk_all(fa, qprep, budget):
 
 def rescore(metric, rows, ids, cands, queries, k):
     """Each query's candidates sorted by (float64 distance, id, position): per query (ids, distances, positions) of length
-    min(k, candidates) and the (k+1)-th distance (inf if none).  rows and queries prepared."""
-    rows = np.asarray(rows, np.float64)
-    ids = np.asarray(ids, np.int64)
-    out = []
-    for q in range(len(queries)):
-        pos = np.asarray(cands[q], np.int64)
-        if len(pos) == 0:
-            out.append((np.zeros(0, np.int64), np.zeros(0), np.zeros(0, np.int64), np.inf))
-            continue
-        dq = distances(metric, np.asarray(queries[q:q + 1], np.float64), rows[pos])[0]
-        order = np.lexsort((pos, ids[pos], dq))
-        nxt = dq[order[k]] if len(order) > k else np.inf
-        order = order[:k]
-        out.append((ids[pos][order], dq[order], pos[order], nxt))
-    return out
+    min(k, candidates) and the (k+1)-th distance (inf if none).  rows and queries prepared.  The re-rank's restatement
+    (_refine_ref.rerank), every list whole."""
+    return rerank(metric, rows, ids, cands, [len(c) for c in cands], queries, k)
 
 
 def check_answers(res, got_ids, got_dist, got_cnt, k):

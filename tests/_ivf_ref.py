@@ -6,6 +6,13 @@ L2, COSINE, INNER_PRODUCT = 0, 1, 2
 RTOL, ATOL = 1e-5, 1e-5  # the project's tolerance for this arithmetic (tests/test_dense_gpu.py)
 
 
+def low_dimensional(rng, n, d, r=3, eps=0.3):
+    """Rows whose distances spread instead of concentrating: r latent dimensions under a random linear map plus eps N(0,1)
+    per component.  The rows of tests/test_refine_gpu.py and tests/test_annoy_gpu.py."""
+    basis = rng.standard_normal((r, d)) / np.sqrt(r)
+    return (rng.standard_normal((n, r)) @ basis + eps * rng.standard_normal((n, d))).astype(np.float32)
+
+
 def prepare(metric, x):
     """What the index stores / a query becomes: Cosine rows L2-normalised (fp32 division by the fp32 norm), then fp16."""
     x = np.atleast_2d(np.asarray(x, np.float32))

@@ -295,3 +295,26 @@ def test_quality():
     print(f"recall@10 {got:.4f}, bar {bar:.4f}")
     assert got >= bar
     ix.close()
+
+
+def test_answers_as_before_the_shared_row_score():
+    """The annoy_* blocks of tests/golden/row_score_baseline.npz (written by make_row_score_baseline.py before walk_kernel,
+    score_kernel and select_kernel took their loads, distance and emit from csrc/row_score.h): d in {3, 100, 200, 1024}, both
+    metrics, k = 10, and one search that hands the selection more than 1024 candidates; answers, pops and collected byte
+    for byte.  The digests of the forest and of the stored rows are host code: they are compared first, so that a host-side
+    difference is not taken for a kernel's."""
+    import importlib.util
+    import os
+
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_row_score_baseline", os.path.join(golden, "make_row_score_baseline.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    base = np.load(os.path.join(golden, "row_score_baseline.npz"))
+    want = {n: base[n] for n in base.files if n.startswith("annoy_")}
+    got, handed = gen.annoy_answers(load_package())
+    assert sorted(got) == sorted(want) and len(got) == (2 + 5) * len(gen.ANNOY_DIMS) * len(gen.ANNOY_METRICS) + 5
+    for name in sorted(got, key=lambda n: (not n.endswith("_sha256"), n)):
+        assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
+    assert np.all(handed["annoy_%d_%s_%d_%d" % gen.ANNOY_WIDE[:4]] > 1024)
+    assert all(want[n].any() for n in want if n.endswith("_dist"))

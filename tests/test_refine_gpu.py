@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import _refine_ref as ref
+from _ivf_ref import low_dimensional as _low_dimensional
 from _refine_ref import QUALITY, QUALITY_SEED
 
 pytestmark = pytest.mark.gpu
@@ -36,11 +37,6 @@ COMBOS = [(1, 1), (10, 1), (10, 8), (100, 10), (256, 4)]  # (k, k_factor); the l
 
 def _metric(pkg, name):
     return getattr(pkg.dense_ann.DistanceMetric, name)
-
-
-def _low_dimensional(rng, n, d, r=3, eps=0.3):
-    basis = rng.standard_normal((r, d)) / np.sqrt(r)
-    return (rng.standard_normal((n, r)) @ basis + eps * rng.standard_normal((n, d))).astype(np.float32)
 
 
 def _numpy_base(metric, y, rng):
@@ -370,3 +366,21 @@ def test_refined_search_answers_as_before_the_shared_core(pkg):
     for name in sorted(got):
         assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
     assert any(want[n].any() for n in want if n.endswith("_dist"))
+
+
+def test_rerank_answers_as_before_the_shared_row_score(pkg):
+    """The refine_* blocks of tests/golden/row_score_baseline.npz (written by make_row_score_baseline.py before rerank_kernel
+    took its distance, sort and emit from csrc/row_score.h and survivor_topk.h): OPQ bases over rows of 100, 200 and 1024
+    components, every metric, (k, k_factor) = (1, 1), (10, 8) and the full sort (256, 4), byte for byte."""
+    path = os.path.join(ROOT, "tests", "golden", "make_row_score_baseline.py")
+    spec = importlib.util.spec_from_file_location("make_row_score_baseline", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    base = np.load(os.path.join(ROOT, "tests", "golden", "row_score_baseline.npz"))
+    want = {n: base[n] for n in base.files if n.startswith("refine_")}
+    got, handed = gen.refine_answers(pkg)
+    assert sorted(got) == sorted(want) and len(got) == 3 * len(gen.REFINE_DIMS) * len(gen.REFINE_METRICS) * len(gen.SEARCHES)
+    for name in sorted(got):
+        assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
+    assert all(np.all(cnt == 1024) for name, cnt in handed.items() if name.endswith("_256_4"))
+    assert all(want[n].any() for n in want if n.endswith("_dist"))

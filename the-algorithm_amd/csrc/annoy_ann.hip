@@ -14,11 +14,11 @@
 //     does not depend on which lane won which table slot.  Every loop is bounded: pops by the node count, probes by the
 //     table size.  A query whose heap would outgrow the first launch's capacity is flagged and walked again with room for
 //     every node (a node enters the queue at most once), so no answer depends on the capacity.
-//   * score_kernel: refine_ann.hip's distance, restated (one wave per candidate row, four rows in flight); the distance goes
-//     with the row's rank in (id, position) order into a 64-bit key, unique per candidate.
+//   * score_kernel: row_score.h's distance, the one refine_ann.hip re-ranks by (one wave per candidate row, four rows in
+//     flight); the distance goes with the row's rank in (id, position) order into a 64-bit key, unique per candidate.
 //   * select_kernel: one workgroup per query.  Up to 1024 candidates are sorted in LDS (sort_keys_desc of survivor_topk.h
 //     over the complemented keys); more than that first find the k-th smallest key by 8 radix passes over an LDS histogram
-//     and gather the k keys at or below it.  No floating-point atomics anywhere.
+//     and gather the k keys at or below it.  row_score.h's emit writes the answer.  No floating-point atomics anywhere.
 // No kernel waits on another workgroup.  A forest reaches the device only through annoy_forest_load's validation or the
 // builder.
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@
 #include "abi_guard.h"
 #include "annoy_forest.h"
 #include "device_buf.h"
-#include "survivor_topk.h"  // f2key, key2f, sort_keys_desc, half8
+#include "row_score.h"  // load_query, load_pieces, wave_sum_f32, score_rows, emit_sorted; survivor_topk.h's f2key, key2f, sort_keys_desc
 
 namespace {
 
@@ -49,7 +49,6 @@ using annoy_host::fail;
 #define ABI_CATCH catch (...) { return abi_guard::caught(fail, IVF_ENOMEM, IVF_EINTERNAL); }
 
 constexpr uint32_t EMPTY = 0xffffffffu;
-constexpr int ROWS_IN_FLIGHT = 4;
 constexpr int SELECT_LDS = 1024;                       // keys sorted in LDS: ANNOY_MAX_K
 constexpr int64_t DEFAULT_QUEUE = 16384;               // first launch: room for the roots and this many more entries
 constexpr int64_t DEFAULT_BUDGET = 512ll << 20;        // scratch of one launch
@@ -111,8 +110,8 @@ __device__ __forceinline__ unsigned long long heap_pop(unsigned long long *h, ui
   return top;
 }
 
-// One wave per query, four waves per workgroup.  NP: pieces of 8 halves per lane (1: stride <= 512, 2: stride <= 1024).
-// The margin's arithmetic is the header's; the file is compiled with -ffp-contract=off.
+// One wave per query, four waves per workgroup, NP as row_score.h has it.  The margin's arithmetic is the header's (the
+// pieces and the lane sums' tree are row_score.h's; the multiply-add is here); the file is compiled with -ffp-contract=off.
 template <int NP>
 __global__ __launch_bounds__(256) void walk_kernel(WalkArgs a) {
   const int lane = threadIdx.x & 63;
@@ -121,14 +120,7 @@ __global__ __launch_bounds__(256) void walk_kernel(WalkArgs a) {
   const int q = a.qlist ? a.qlist[w] : w;
   const int pieces = a.stride >> 3;
   float qf[NP][8];
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int p = lane + 64 * j;
-    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (p < pieces) v = *(const half8 *)(a.q16 + (size_t)q * a.stride + p * 8);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qf[j][i] = (float)v[i];
-  }
+  load_query<NP>(a.q16 + (size_t)q * a.stride, pieces, qf);
   unsigned long long *heap = a.heap + (size_t)w * a.heap_cap;
   uint32_t *table = a.table + (size_t)q * a.table_cap;
   int32_t *cand = a.cand + (size_t)q * a.cand_cap;
@@ -180,17 +172,14 @@ __global__ __launch_bounds__(256) void walk_kernel(WalkArgs a) {
       }
       collected += (uint32_t)count;
     } else {  // a split: the margin, then two pushes
-      const _Float16 *nrm = a.normals + (size_t)nd.w * a.stride;
+      half8 v[NP];
+      load_pieces<NP>(a.normals + (size_t)nd.w * a.stride, true, pieces, v);
       float acc = 0.0f;
 #pragma unroll
-      for (int j = 0; j < NP; ++j) {
-        const int p = lane + 64 * j;
-        half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (p < pieces) v = *(const half8 *)(nrm + p * 8);
+      for (int j = 0; j < NP; ++j)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc += (float)v[e] * qf[j][e];
-      }
-      for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        for (int e = 0; e < 8; ++e) acc += (float)v[j][e] * qf[j][e];
+      acc = wave_sum_f32(acc);
       const float mg = a.l2 ? acc + a.offsets[nd.w] : acc;
       if (lane == 0) {
         if (size + 2 > a.heap_cap) {
@@ -225,7 +214,7 @@ struct ScoreArgs {
 };
 
 // grid (queries, waves' blocks): wave v of a query scores candidates v * 4 .. v * 4 + 3, then strides on.  The distance of a
-// (query, row) pair is refine_ann.h's, in its order.
+// (query, row) pair is row_score.h's, the re-rank's.
 template <int NP>
 __global__ __launch_bounds__(256) void score_kernel(ScoreArgs a) {
   const int lane = threadIdx.x & 63, q = blockIdx.x;
@@ -233,53 +222,22 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs a) {
   const int pieces = a.stride >> 3;
   const int c = min(max(a.cnt[q], 0), (int)a.cand_cap);
   float qf[NP][8];
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int p = lane + 64 * j;
-    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (p < pieces) v = *(const half8 *)(a.q16 + (size_t)q * a.stride + p * 8);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qf[j][i] = (float)v[i];
-  }
+  load_query<NP>(a.q16 + (size_t)q * a.stride, pieces, qf);
   const int32_t *cp = a.cand + (size_t)q * a.cand_cap;
   unsigned long long *kp = a.keys + (size_t)q * a.cand_cap;
   for (int i0 = wave * ROWS_IN_FLIGHT; i0 < c; i0 += waves * ROWS_IN_FLIGHT) {
-    half8 x[ROWS_IN_FLIGHT][NP];
     int64_t pos[ROWS_IN_FLIGHT];
+    float dist[ROWS_IN_FLIGHT];
 #pragma unroll
     for (int u = 0; u < ROWS_IN_FLIGHT; ++u) {
-      const int i = i0 + u;
-      int64_t p = i < c ? (int64_t)cp[i] : -1;
-      if (p >= (int64_t)a.n) p = -1;
-      pos[u] = p;
-#pragma unroll
-      for (int j = 0; j < NP; ++j) {
-        const int pc = lane + 64 * j;
-        half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (p >= 0 && pc < pieces) v = *(const half8 *)(a.rows + (size_t)p * a.stride + pc * 8);
-        x[u][j] = v;
-      }
+      const int64_t p = i0 + u < c ? (int64_t)cp[i0 + u] : -1;
+      pos[u] = p < (int64_t)a.n ? p : -1;
     }
+    score_rows<NP>(a.rows, a.stride, pieces, pos, qf, a.l2, dist);
 #pragma unroll
-    for (int u = 0; u < ROWS_IN_FLIGHT; ++u) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int j = 0; j < NP; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xv = (float)x[u][j][e];
-          if (a.l2) {
-            const float df = qf[j][e] - xv;
-            acc += df * df;
-          } else {
-            acc += qf[j][e] * xv;
-          }
-        }
-      for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o, 64);
-      const float dist = a.l2 ? sqrtf(acc) : 1.0f - acc;
+    for (int u = 0; u < ROWS_IN_FLIGHT; ++u)
       if (lane == 0 && i0 + u < c)
-        kp[i0 + u] = pos[u] >= 0 ? ((unsigned long long)f2key(dist) << 32) | a.rank[pos[u]] : ~0ull;
-    }
+        kp[i0 + u] = pos[u] >= 0 ? ((unsigned long long)f2key(dist[u]) << 32) | a.rank[pos[u]] : ~0ull;
   }
 }
 
@@ -352,20 +310,7 @@ __global__ __launch_bounds__(256) void select_kernel(SelectArgs a) {
   for (uint32_t i = held + t; i < n2; i += 256) keys[i] = 0;  // the complement of the largest key: sorts last
   __syncthreads();
   sort_keys_desc(keys, n2);
-  for (int i = t; i < a.k; i += 256) {
-    float dist = 0.0f;
-    int64_t id = 0;
-    if ((uint32_t)i < m) {
-      const unsigned long long key = ~keys[i];
-      if (key != ~0ull) {
-        dist = key2f((uint32_t)(key >> 32));
-        id = a.ids_sorted[(uint32_t)key];
-      }
-    }
-    a.out_dist[(size_t)q * a.k + i] = dist;
-    a.out_ids[(size_t)q * a.k + i] = id;
-  }
-  if (t == 0) a.out_counts[q] = (int32_t)m;
+  emit_sorted(keys, m, a.k, a.ids_sorted, a.out_dist + (size_t)q * a.k, a.out_ids + (size_t)q * a.k, a.out_counts + q);
 }
 
 }  // namespace

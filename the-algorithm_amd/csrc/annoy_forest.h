@@ -69,8 +69,9 @@ inline uint16_t float_to_half(float f) {
   return (uint16_t)(s | (q + ((rem > 0x1000u || (rem == 0x1000u && (q & 1u))) ? 1u : 0u)));
 }
 
-// The margin of include/annoy_ann.h over rows already widened to fp32 and padded to `stride` (a multiple of 8, <= 1024).
-// Compiled with -ffp-contract=off: a multiply, then an add.
+// The margin of include/annoy_ann.h over rows already widened to fp32 and padded to `stride` (a multiple of 8, <= 1024): the
+// host's emulation of the order that row_score.h states for the device (pieces l and l + 64 per lane, components 0..7, the
+// xor tree).  Compiled with -ffp-contract=off: a multiply, then an add.
 inline float margin(const float *normal, const float *q, int stride, float offset, bool l2) {
   float acc[64];
   for (int l = 0; l < 64; ++l) acc[l] = 0.0f;

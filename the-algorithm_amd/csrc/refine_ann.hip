@@ -13,9 +13,10 @@
 //   * A search asks the base's select step for positions (ivfpq_internal::search_positions) at k' = k * k_factor, then
 //     rerank_kernel: one workgroup per query, the prepared query in registers (a lane holds its one or two pieces of 8
 //     components as fp32), one wave per candidate row, four rows in flight per wave -- a gather of k' rows of 2 d bytes,
-//     bound by latency and bandwidth; MFMA has no place in it.  The lane sums meet in a fixed xor tree.  The distance goes
-//     with the candidate's rank in (id, position) order into a 64-bit LDS key; a bitonic sort of at most 1024 keys, as
-//     pq_select_kernel sorts its survivors, gives the answer in (distance, id, position) order.  No atomics at all.
+//     bound by latency and bandwidth; MFMA has no place in it.  That distance is row_score.h's, which annoy_ann.hip
+//     shares.  It goes with the candidate's rank in (id, position) order into a 64-bit LDS key, stored complemented;
+//     survivor_topk.h's sort_keys_desc over at most 1024 of them, as pq_select_kernel sorts its survivors, gives the answer
+//     in (distance, id, position) order, and row_score.h's emit writes it.  No atomics at all.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +35,7 @@
 #include "faiss_restore.h"
 #include "ivf_error.h"  // g_err, fail, ITRY, ABI_CATCH
 #include "ivf_kernels.h"
+#include "row_score.h"  // load_query, score_rows, emit_sorted
 
 namespace {
 
@@ -52,7 +54,6 @@ namespace {
 
 constexpr int MAX_STORE_D = 1024;
 constexpr int MAX_CAND = MAX_K;  // k * k_factor: the base's largest k
-constexpr int ROWS_IN_FLIGHT = 4;
 
 struct RerankArgs {
   const _Float16 *rows;        // the store, [n][stride]
@@ -68,96 +69,39 @@ struct RerankArgs {
   int32_t *out_counts;         // [nq]
 };
 
-// One workgroup per query, 256 threads.  NP: pieces of 8 halves per lane (1: stride <= 512, 2: stride <= 1024).
-// The arithmetic of a (query, row) pair is the one refine_ann.h states; the file is compiled with -ffp-contract=off.
+// One workgroup per query, 256 threads, NP as row_score.h has it.  Wave w scores candidates 4 w .. 4 w + 3, then strides on;
+// a candidate's key goes, complemented, to its own slot of the LDS list.
 template <int NP>
 __global__ __launch_bounds__(256) void rerank_kernel(RerankArgs a) {
   __shared__ unsigned long long keys[MAX_CAND];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, q = blockIdx.x;
+  const int t = threadIdx.x, w = t >> 6, q = blockIdx.x;
   const int pieces = a.stride >> 3;
-  const bool l2 = a.metric == IVF_METRIC_L2;
   const int c = min(max(a.cnt[q], 0), a.width);
-  int n2 = 64;
-  while (n2 < c) n2 <<= 1;
-  for (int i = t; i < n2; i += 256) keys[i] = ~0ull;
+  uint32_t n2 = 64;
+  while (n2 < (uint32_t)c) n2 <<= 1;
+  for (uint32_t i = t; i < n2; i += 256) keys[i] = 0;  // the complement of the largest key: sorts last
   float qf[NP][8];
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int p = lane + 64 * j;
-    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (p < pieces) v = *(const half8 *)(a.q16 + (size_t)q * a.stride + p * 8);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qf[j][i] = (float)v[i];
-  }
+  load_query<NP>(a.q16 + (size_t)q * a.stride, pieces, qf);
   __syncthreads();
   const int32_t *cp = a.pos + (size_t)q * a.width;
   for (int i0 = w * ROWS_IN_FLIGHT; i0 < c; i0 += 4 * ROWS_IN_FLIGHT) {  // (i0 and c are the same for every lane of a wave)
-    half8 x[ROWS_IN_FLIGHT][NP];
-    bool live[ROWS_IN_FLIGHT];
+    int64_t pos[ROWS_IN_FLIGHT];
+    float dist[ROWS_IN_FLIGHT];
 #pragma unroll
     for (int u = 0; u < ROWS_IN_FLIGHT; ++u) {
-      const int i = i0 + u;
-      const int64_t p = i < c ? (int64_t)cp[i] : -1;
-      live[u] = p >= 0 && p < a.n;
-#pragma unroll
-      for (int j = 0; j < NP; ++j) {
-        const int pc = lane + 64 * j;
-        half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (live[u] && pc < pieces) v = *(const half8 *)(a.rows + (size_t)p * a.stride + pc * 8);
-        x[u][j] = v;
-      }
+      const int64_t p = i0 + u < c ? (int64_t)cp[i0 + u] : -1;
+      pos[u] = p < a.n ? p : -1;
     }
+    score_rows<NP>(a.rows, a.stride, pieces, pos, qf, a.metric == IVF_METRIC_L2, dist);
 #pragma unroll
-    for (int u = 0; u < ROWS_IN_FLIGHT; ++u) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int j = 0; j < NP; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xv = (float)x[u][j][e];
-          if (l2) {
-            const float df = qf[j][e] - xv;
-            acc += df * df;
-          } else {
-            acc += qf[j][e] * xv;
-          }
-        }
-      for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o, 64);
-      const float dist = l2 ? sqrtf(acc) : 1.0f - acc;
-      if (lane == 0 && live[u]) keys[i0 + u] = ((unsigned long long)f2key(dist) << 32) | a.rank[(size_t)q * a.width + i0 + u];
-    }
+    for (int u = 0; u < ROWS_IN_FLIGHT; ++u)
+      if ((t & 63) == 0 && pos[u] >= 0)
+        keys[i0 + u] = ~(((unsigned long long)f2key(dist[u]) << 32) | a.rank[(size_t)q * a.width + i0 + u]);
   }
   __syncthreads();
-  // ascending bitonic sort of n2 keys (the padding keys are the largest)
-  for (int size = 2; size <= n2; size <<= 1)
-    for (int str = size >> 1; str > 0; str >>= 1) {
-      for (int i = t; i < n2 / 2; i += 256) {
-        const int lo = 2 * i - (i & (str - 1));
-        const int hi = lo + str;
-        const bool asc = (lo & size) == 0;
-        const unsigned long long x = keys[lo], y = keys[hi];
-        if ((x > y) == asc) {
-          keys[lo] = y;
-          keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  const int m = min(c, a.k);
-  for (int i = t; i < a.k; i += 256) {
-    float dist = 0.0f;
-    int64_t id = 0;
-    if (i < m) {
-      const unsigned long long key = keys[i];
-      if (key != ~0ull) {  // (a candidate outside the store: cannot happen with the base's own positions)
-        dist = key2f((uint32_t)(key >> 32));
-        id = a.ids_sorted[(uint32_t)key];
-      }
-    }
-    a.out_dist[(size_t)q * a.k + i] = dist;
-    a.out_ids[(size_t)q * a.k + i] = id;
-  }
-  if (t == 0) a.out_counts[q] = m;
+  sort_keys_desc(keys, n2);
+  // (a key left at 0 among the first c: a candidate outside the store, which cannot happen with the base's own positions)
+  emit_sorted(keys, (uint32_t)min(c, a.k), a.k, a.ids_sorted, a.out_dist + (size_t)q * a.k, a.out_ids + (size_t)q * a.k, a.out_counts + q);
 }
 
 }  // namespace

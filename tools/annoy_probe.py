@@ -8,7 +8,8 @@ rows and 30 queries), --corpus lowdim takes rows with 3 latent dimensions instea
   kind hnsw    ef, ms, qps, recall
   kind brute   ms, qps
 recall is |found & true| / k against the exhaustive search, averaged, as the Runner counts it.  build_s is the host build of
-the forest with --threads threads.  Run under a time limit, e.g.
+the forest with --threads threads.  --phases-only leaves the exhaustive search out (it takes no rows wider than 512) and
+with it recall and HNSW: the Annoy lines alone, at any --dim.  Run under a time limit, e.g.
   timeout -k 10 600 python tools/annoy_probe.py --n 100000 --nq 1024 > profiles/annoy_probe_100k.jsonl"""
 import argparse
 import json
@@ -38,6 +39,7 @@ def main():
     ap.add_argument("--corpus", default="runner", choices=["runner", "lowdim"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-hnsw", action="store_true")
+    ap.add_argument("--phases-only", action="store_true", help="no exhaustive search, no recall, no HNSW: the Annoy lines alone")
     a = ap.parse_args()
     pkg = load_package()
     cosine = pkg.dense_ann.DistanceMetric.Cosine
@@ -51,11 +53,13 @@ def main():
         x, q = y[:a.n], y[a.n:]
     common = {"corpus": a.corpus, "n": a.n, "d": a.dim, "nq": a.nq, "k": a.k}
 
-    dense = pkg.dense_ann.BruteForceIndex.build(cosine, x, np.arange(1, a.n + 1))
-    dense.search(q, a.k)
-    s, truth = best_time(lambda: dense.search(q, a.k), a.reps)
-    dense.close()
-    print(json.dumps(dict(common, kind="brute", ms=round(s * 1e3, 3), qps=round(a.nq / s, 1))), flush=True)
+    truth = None
+    if not a.phases_only:
+        dense = pkg.dense_ann.BruteForceIndex.build(cosine, x, np.arange(1, a.n + 1))
+        dense.search(q, a.k)
+        s, truth = best_time(lambda: dense.search(q, a.k), a.reps)
+        dense.close()
+        print(json.dumps(dict(common, kind="brute", ms=round(s * 1e3, 3), qps=round(a.nq / s, 1))), flush=True)
 
     t0 = time.perf_counter()
     forest = pkg.annoy_ann.AnnoyForest.build(cosine, x, a.trees, threads=a.threads)
@@ -73,11 +77,11 @@ def main():
                               qps=round(a.nq / s, 1), walk_ms=round(st["walk_ms"], 3), score_ms=round(st["score_ms"], 3),
                               select_ms=round(st["select_ms"], 3), pops=round(float(st["pops"].mean()), 1),
                               candidates=round(float(ccnt.mean()), 1), rerun=st["rerun"], slices=st["slices"],
-                              recall=round(recall_of(ids, cnt, truth[0], truth[2]), 4))), flush=True)
+                              recall=round(recall_of(ids, cnt, truth[0], truth[2]), 4) if truth else None)), flush=True)
     ix.close()
     forest.close()
 
-    if not a.no_hnsw:
+    if not a.no_hnsw and not a.phases_only:
         t0 = time.perf_counter()
         hn = pkg.hnsw_ann.Hnsw.build(cosine, x, np.arange(1, a.n + 1), max_m=16, ef_construction=200, n_threads=16)
         hbuild_s = time.perf_counter() - t0

@@ -9,6 +9,8 @@ training rows, niter and seed and against the exhaustive index, on the same rows
   recall                 recall@k against dann_search (|found & true| / |true|, averaged); pq_recall and flat_recall are those
                          of ivfpq_search and ivf_search at the same (k, nprobe), pq_qps / flat_qps their rates
 Corpora and nlist as tools/ivf_probe.py; --nlist overrides.  --opq D_OUT puts the OPQ transform in front of the base.
+--phases-only leaves the yardsticks out (the exhaustive index, IVF-Flat and the plain base: none of them takes rows wider
+than 512) and with them recall and the *_qps beside: what is left is refine_qps, base_ms and rerank_ms, at any --dim.
 
 Nobody has run this on a card yet: whoever does writes the numbers into DESIGN.md section 5 and profiles/.  Run each setting
 under its own time limit, e.g.
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--sigma", type=float, default=1.0)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--metric", default="L2")
+    ap.add_argument("--phases-only", action="store_true", help="no yardsticks and no recall: the phase times alone")
     a = ap.parse_args()
     pkg = load_package()
     m = getattr(pkg.dense_ann.DistanceMetric, a.metric)
@@ -57,12 +60,13 @@ def main():
     nprobes = [int(s) for s in a.nprobes.split(",")]
     k_factors = [int(s) for s in a.k_factors.split(",")]
 
-    dense = pkg.dense_ann.BruteForceIndex.build(m, x)
     truth, dense_s = {}, {}
-    for k in ks:
-        dense.search(q, k)
-        dense_s[k], truth[k] = best_time(lambda: dense.search(q, k), a.reps)
-    dense.close()
+    if not a.phases_only:
+        dense = pkg.dense_ann.BruteForceIndex.build(m, x)
+        for k in ks:
+            dense.search(q, k)
+            dense_s[k], truth[k] = best_time(lambda: dense.search(q, k), a.reps)
+        dense.close()
 
     def train_base():
         if a.opq:
@@ -71,7 +75,7 @@ def main():
 
     # the two yardsticks of the same run: IVF-Flat and the plain base
     beside = {}
-    for name, make in (("flat", lambda: pkg.ivf_ann.FaissIvfFlat.train(m, nlist, x[:n_train], niter=a.niter, seed=1)), ("pq", train_base)):
+    for name, make in () if a.phases_only else (("flat", lambda: pkg.ivf_ann.FaissIvfFlat.train(m, nlist, x[:n_train], niter=a.niter, seed=1)), ("pq", train_base)):
         ix = make()
         t0 = time.perf_counter()
         ix.add(x)
@@ -105,9 +109,11 @@ def main():
                     "n_train": n_train, "niter": a.niter, "sigma": a.sigma, "nq": len(q), "k": k, "nprobe": nprobe, "k_factor": kf,
                     "train_s": round(train_s, 3), "add_s": round(add_s, 3), "bytes_per_row": ix.bytes_per_row(),
                     "refine_qps": round(len(q) / s, 1), "refine_ms": round(s * 1e3, 3), "base_ms": round(st["base_ms"], 3),
-                    "rerank_ms": round(st["rerank_ms"], 3), "gathered_mb": round(len(q) * k * kf * 2 * d / 1e6, 3),
-                    "dense_qps": round(len(q) / dense_s[k], 1), "recall": round(recall_of(ids, cnt, truth[k][0], truth[k][2]), 4)}
-                line.update(beside[(k, nprobe)])
+                    "rerank_ms": round(st["rerank_ms"], 3), "gathered_mb": round(len(q) * k * kf * 2 * d / 1e6, 3)}
+                if not a.phases_only:
+                    line.update({"dense_qps": round(len(q) / dense_s[k], 1),
+                                 "recall": round(recall_of(ids, cnt, truth[k][0], truth[k][2]), 4)})
+                    line.update(beside[(k, nprobe)])
                 print(json.dumps(line), flush=True)
     ix.close()
 
