@@ -318,6 +318,13 @@ int sann_debug_id_column(sann_batch_t *batch, int32_t *present, int32_t *ordinar
  * the four-wave units there), else 1, 2 or 4 by the capacity; 0 if no run launched the fast path.  *unit_capacity: the
  * postings a unit holds, as chosen when the batch was prepared. */
 int sann_debug_unit_waves(sann_batch_t *batch, int32_t *waves_of_last_run, int32_t *unit_capacity);
+/* Debug: *bits_of_last_run = width of the posting offsets the last sann_batch_run's unit kernel gathered with: 32 for the
+ * two-wave units on an index of fewer than 2^29 postings (a byte offset from the id column's base; SANN_UNIT_OFFSETS=64
+ * keeps 64-bit addresses there), else 64; 0 if no run launched the fast path. */
+int sann_debug_unit_offsets(sann_batch_t *batch, int32_t *bits_of_last_run);
+/* Pure host code (no HIP call): the choice sann_batch_prepare makes for the two-wave units of an index of n_postings
+ * postings -- 32 while every 8-byte position fits a 32-bit byte offset (n_postings < 2^29) and forced_wide is 0, else 64. */
+int32_t sann_unit_offset_bits(uint64_t n_postings, int32_t forced_wide);
 /* Debug: sann_index_get_list's tweet ids, read from the id column instead of the postings (an error without a column). */
 int sann_debug_index_id_column(const sann_index_t *index, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, int64_t *n);
 /* Debug: per-unit arrays of the last run ([nq * n_partitions] each; any may be NULL): distinct tweets accumulated,

@@ -286,6 +286,7 @@ struct sann_batch {
   FastParams fast{};
   bool id_form_ran = false;  // the last run's unit kernel was the id form (sann_debug_id_column)
   int unit_waves_ran = 0;    // waves per unit of the last run's unit kernel; 0 = it ran none (sann_debug_unit_waves)
+  int unit_offsets_ran = 0;  // bits of its gather offsets, 32 or 64; 0 = it ran none (sann_debug_unit_offsets)
   sann_batch_stats_t stats{};
   bool ran = false;
   bool slow_tail_ran = false;  // the last sann_batch_finish re-ran units on the general path (results changed after the first merge)
@@ -782,6 +783,11 @@ int batch_reset(sann_batch *b, hipStream_t st, int64_t now_ms, int32_t nq, const
     const char *ov = getenv("SANN_UNIT_WAVES");
     const bool four = ov && ov[0] == '4' && ov[1] == '\0';
     b->fast.two_wave = (b->fast.id_form && b->fast.unit_capacity == 1536 && !four) ? 1 : 0;
+    // ... and gather through 32-bit byte offsets wherever the id column is short enough for them (SANN_UNIT_OFFSETS=64
+    // keeps 64-bit addresses; read per batch as well)
+    const char *oo = getenv("SANN_UNIT_OFFSETS");
+    const bool forced = oo && oo[0] == '6' && oo[1] == '4' && oo[2] == '\0';
+    b->fast.wide_offsets = unit_offset_bits((uint64_t)ix->n_postings, forced) == 64 ? 1 : 0;
   };
 
   if (b->device_prep) {
@@ -1088,9 +1094,11 @@ static int batch_run(sann_batch_t *b, void *hip_stream, bool chained, sann_batch
       b->id_form_ran = b->fast.id_form != 0;
       // (launch_unit_fast's geometries: <64, 4>, <128, 4>, then 256 threads)
       b->unit_waves_ran = b->fast.two_wave ? 2 : b->fast.unit_capacity <= 256 ? 1 : b->fast.unit_capacity <= 512 ? 2 : 4;
+      b->unit_offsets_ran = (b->fast.two_wave && !b->fast.wide_offsets) ? 32 : 64;  // (only the two-wave units have the narrow form)
     } else {
       b->id_form_ran = false;
       b->unit_waves_ran = 0;
+      b->unit_offsets_ran = 0;
       std::vector<int32_t> none;
       int rc = run_general(b, none, st);
       if (rc != SANN_OK) return rc;
@@ -1450,6 +1458,14 @@ int sann_debug_unit_waves(sann_batch_t *b, int32_t *waves_of_last_run, int32_t *
   if (unit_capacity) *unit_capacity = b->fast.unit_capacity;
   return SANN_OK;
 } ABI_CATCH
+
+int sann_debug_unit_offsets(sann_batch_t *b, int32_t *bits_of_last_run) try {
+  if (!b) return fail(SANN_EINVAL, "batch is NULL");
+  if (bits_of_last_run) *bits_of_last_run = b->ran ? b->unit_offsets_ran : 0;
+  return SANN_OK;
+} ABI_CATCH
+
+int32_t sann_unit_offset_bits(uint64_t n_postings, int32_t forced_wide) { return unit_offset_bits(n_postings, forced_wide != 0); }
 
 int sann_debug_index_id_column(const sann_index_t *ix, int32_t cluster_id, int64_t cap, int64_t *tweet_ids, int64_t *n) try {
   if (!ix || !n) return fail(SANN_EINVAL, "NULL argument");

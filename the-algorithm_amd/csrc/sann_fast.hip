@@ -13,7 +13,7 @@
 //               the score, the cluster's sequence number and a hash of the id -- the fp64 posting is read again only for
 //               survivors, by the MERGE kernel).  What bounds it is the time a workgroup holds its slot -- a chain of
 //               dependent memory trips -- at eight workgroups per CU (<= 64 VGPRs, 20 KB LDS, <= 80 SGPRs); the id form
-//               at 1536 postings runs as TWO-wave units, fourteen per CU (56 VGPRs, 11.3 KB LDS: see two_wave_unit):
+//               at 1536 postings runs as TWO-wave units, fourteen per CU (60 VGPRs, 11.3 KB LDS: see two_wave_unit):
 //   1. descriptors  header, (start, prefix) row, cluster weights and posting count in ONE trip; byte map flat posting
 //                   index -> cluster; per-cluster constants (fp64 weight, fp32 weight, and for the cosine forms the fp32
 //                   KEY of a single-cluster candidate: (s w) / sqrt(s s) = w, so such a candidate needs no arithmetic)
@@ -208,22 +208,38 @@ __device__ inline void unit_overflowed(int unit, unsigned long long reason) {
 // never moved.  Who needs a posting's fp64 score (the match list of a flagged unit, the merge kernel) reads the posting.
 // The TWO-WAVE unit of the benchmark's 1536-posting capacity, <128, 12> in the id form (FastParams::two_wave): fixed per-wave
 // work is paid twice per unit instead of four times, two waves meet at a barrier sooner than four, and with the 8 KB
-// filter (bloom_bits6) and without the fp32 weights the id form never reads, a unit needs 11.3 KB of LDS: fourteen units
+// filter (bloom_product) and without the fp32 weights the id form never reads, a unit needs 11.3 KB of LDS: fourteen units
 // per CU (seven waves per SIMD) where <256, 6> holds eight.
 template <int WG, int U, bool IDF> constexpr bool two_wave_unit = IDF && WG == 128 && U == 12;
-template <int WG, int U, int NS = NSCAN_MAX, int ABL = 0, bool NORMS = false, bool IDF = false>
+// W64 (two-wave units only): the gather's addresses are 64-bit, as in every other form.  The two-wave default builds a
+// 32-bit BYTE offset per posting and leaves the id column's base in scalar registers (FastParams::wide_offsets).
+template <int WG, int U, int NS = NSCAN_MAX, int ABL = 0, bool NORMS = false, bool IDF = false, bool W64 = false>
 __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 : NORMS ? (U <= 8 ? 5 : 2) : U <= 6 ? 8 : U <= 8 ? 5 : U <= 12 ? 3 : 2)) void unit_fast_kernel(IndexView ix, BatchView b, int k_local_floor, int n_blocks_q8) {
   static_assert(!IDF || (ABL == 0 && !NORMS), "the id form is built for the product's online kernel only");
+  static_assert(!W64 || two_wave_unit<WG, U, IDF>, "only the two-wave units have a narrow form to opt out of");
   constexpr int SCAP = FAST_SCAP;
-  constexpr bool B8K = two_wave_unit<WG, U, IDF>;  // the 8 KB filter: six bits of a word, made of all 32 hash bits
+  // the 8 KB filter: six bits of a word, word and bits the two halves of one product (bloom_product).  The two-wave units
+  // are also where round 12 cut issue slots per posting slot: everything under `if constexpr (B8K)` below.
+  constexpr bool B8K = two_wave_unit<WG, U, IDF>;
+  constexpr bool NARROW = B8K && !W64;  // 32-bit gather offsets
   constexpr int BW = B8K ? BLOOM8K_LOG2 : bloom_log2(WG * U);  // log2 of the Bloom filter's 64-bit words
   constexpr int BLOOM_ALLOC = 1 << BW;
   constexpr int HB = B8K ? 32 : BLOOM_POS_BITS + BW;  // hash bits: 4 x 5 bit positions, then the word index (8 KB form: all)
   constexpr int FBLOOM_WORDS = (B8K || BW >= 11) ? 64 : 256;  // (beside the 16 KB Bloom filter: 64, so that eight workgroups fit a CU)
   constexpr int FB = (B8K || BW >= 11) ? 6 : 8;
   // a posting's word of the filter (the top BW hash bits) and its bits in that word and in the flagged filter's
-  auto bloom_word = [](uint32_t hv) { return B8K ? hv >> (32 - BW) : hv >> BLOOM_POS_BITS; };
-  auto bloom_mask = [](uint32_t hv) { return B8K ? bloom_bits6(hv) : bloom_bits(hv); };
+  // What a slot carries in hsh[] is table_hash of its id -- the 8 KB form: bloom_fold of it, one multiply short of that.
+  // bloom_key makes of it the hash (word: its top BW bits; flagged filter's word: its top FB) and the posting's bits.
+  struct BloomKey { uint32_t hv; unsigned long long bits; };
+  auto bloom_carry = [](long long idv) { return B8K ? bloom_fold(idv) : table_hash(idv, HB); };
+  auto bloom_key = [](uint32_t carried) {
+    if constexpr (B8K) {
+      const unsigned long long p = bloom_product(carried);
+      return BloomKey{(uint32_t)p, bloom_product_bits((uint32_t)(p >> 32))};
+    } else {
+      return BloomKey{carried, bloom_bits(carried)};
+    }
+  };
   constexpr int MCAP = (WG * U <= 1024) ? 64 : 128;
   constexpr int SHORT_NM = 12;  // match lists up to here are settled by every wave for itself; the sorted path starts above
   __shared__ unsigned long long s_bloom[BLOOM_ALLOC];
@@ -373,7 +389,11 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
         const uint32_t jj = j < Tg ? j : Tg - 1;
         const int c = (int)s_map[jj];
         seq[u] = (j < Tg) ? c : -1;
-        if constexpr (IDF) {
+        if constexpr (NARROW) {
+          // (the launcher's promise: 8 * n_postings < 2^32; the column's base is uniform and stays in scalar registers)
+          const uint32_t off = (s_off[c] + jj) << 3;
+          asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(raw[u]) : "v"(off), "s"(ix.ids) : "memory");
+        } else if constexpr (IDF) {
           const int64_t *src = ix.ids + (s_off[c] + jj);
           asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(raw[u]) : "v"(src) : "memory");
         } else {
@@ -397,6 +417,55 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
       for (int u = 0; u < U; u++) x_ ^= ((unsigned long long)(raw[u].y ^ raw[u].w) << 32) | (raw[u].x ^ raw[u].z ^ (unsigned)seq[u]);
       ABLATE(7, x_);
     }
+    }
+    if constexpr (B8K) {
+      // ---- filters and 3a in ONE pass over the slots, branch-free per slot (round 12: this kernel is paced by instruction
+      // issue).  A dead slot (windowed out, excluded, past the unit's end) issues the atomic too, with a ZERO mask, to the
+      // word of whatever id it loaded: no exec bracket around the atomic, and the mask is made once, of the product the
+      // slot carries on.  The live count is the popcount of the keep mask itself.  A posting was possibly seen before
+      // when it is live and none of its bits was new; that is rare (0.3 postings per unit), so all it leaves behind is a
+      // bit of `again`, and the flagged filter's ORs stand behind ONE branch per wave.  THOSE stay under a per-slot
+      // bracket: as zero-mask atomics of every slot they were 12 x 128 atomics on 64 words in each flagged unit -- the
+      // step lost what the rest of this pass had gained, and the duplicate-heavy corpus, all of whose units are flagged,
+      // ran 10 % slower (profiles/NOTES.md, round 12).
+      uint32_t again = 0u;  // bit u: slot u's posting was possibly seen before
+      if (Tg != 0u) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          if ((uint32_t)(u * WG) < Tg) {  // (uniform)
+            // (the filters of the other forms' loop below; selects for the same reason)
+            const long long idv = (long long)(((unsigned long long)raw[u].y << 32) | raw[u].x);
+            const bool excluded = h.excl_enabled != 0 && idv == h.src_excl;  // :90
+            const bool in_window = idv >= h.earliest && idv <= h.latest;     // :91
+            const bool keep = seq[u] >= 0 && !excluded && in_window;
+            seq[u] = keep ? seq[u] : -1;
+            hsh[u] = bloom_carry(idv);
+            // wave count, identical in all lanes: of a fresh compare (hipcc makes a ballot of `keep` itself, or of anything
+            // it can trace back to it, out of a select and a compare; the empty asm hides the trace)
+            asm volatile("" : "+v"(seq[u]));
+            live += __popcll(__builtin_amdgcn_ballot_w64(seq[u] >= 0));
+            const BloomKey key = bloom_key(hsh[u]);
+            const unsigned long long bits = keep ? key.bits : 0ull;
+            const unsigned long long fresh = ~atomicOr(&s_bloom[key.hv >> (HB - BW)], bits) & bits;  // bits that were NOT set before
+            if (keep && fresh == 0ull) {
+              again |= 1u << u;
+              asm volatile("" : "+v"(again));  // (stays a branch: as a select it would be two vector instructions in every slot)
+            }
+          }
+        }
+      }
+      if (__builtin_amdgcn_ballot_w64(again != 0u) != 0ull) {  // (uniform per wave)
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          if ((again >> u) & 1u) {
+            const BloomKey key = bloom_key(hsh[u]);
+            atomicOr(&s_fbloom[key.hv >> (HB - FB)], key.bits);
+          }
+        }
+        if (again != 0u) s_ctl[CTL_NFLAG] = 1;
+      }
+    } else {
+    if (Tg != 0u) {
 #pragma unroll
     for (int u = 0; u < U; u++) {
       if ((uint32_t)(u * WG) < Tg) {
@@ -431,20 +500,19 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
     for (int u = 0; u < U; u++) {
       seen[u] = 0ull;
       if ((uint32_t)(u * WG) < Tg && seq[u] >= 0) {
-        const uint32_t hv = hsh[u];
-        const unsigned long long bits = bloom_mask(hv);
-        seen[u] = ~atomicOr(&s_bloom[bloom_word(hv)], bits) & bits;  // bits of this posting that were NOT set before
+        const BloomKey key = bloom_key(hsh[u]);
+        seen[u] = ~atomicOr(&s_bloom[key.hv >> (HB - BW)], key.bits) & key.bits;  // bits of this posting that were NOT set before
       }
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
       if ((uint32_t)(u * WG) < Tg && seq[u] >= 0 && seen[u] == 0ull) {
         // possibly seen before: mark the id's bits in the (sparse) "flagged" filter
-        const uint32_t hv = hsh[u];
-        const unsigned long long bits = bloom_mask(hv);
-        atomicOr(&s_fbloom[hv >> (HB - FB)], bits);
+        const BloomKey key = bloom_key(hsh[u]);
+        atomicOr(&s_fbloom[key.hv >> (HB - FB)], key.bits);
         s_ctl[CTL_NFLAG] = 1;
       }
+    }
     }
     if ((tid & 63) == 0 && live) atomicAdd(&s_ctl[CTL_LIVE], live);
   }
@@ -486,9 +554,8 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
     };
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      const uint32_t hv = hsh[u];
-      const unsigned long long bits = bloom_mask(hv);
-      const bool hit = seq[u] >= 0 && (s_fbloom[hv >> (HB - FB)] & bits) == bits;
+      const BloomKey key = bloom_key(hsh[u]);
+      const bool hit = seq[u] >= 0 && (s_fbloom[key.hv >> (HB - FB)] & key.bits) == key.bits;
       mi[u] = -1;
       if constexpr (ONE_TRIP) pm[u] = Posting{0, 0.0};
       if (hit) {
@@ -1009,7 +1076,14 @@ static hipError_t launch_two_wave(const IndexView &ix, const BatchView &b, const
   const int n_blocks = nq8 * ix.P;
   if (b.desc_stride != desc_row_stride(fp.max_n_scan)) return hipErrorInvalidValue;
   if (!fp.id_form || fp.use_norms || !ix.ids) return hipErrorInvalidValue;
-  if (fp.max_n_scan <= 64)
+  // (the narrow form's byte offsets are 32-bit: never on an index it was not chosen for)
+  if (!fp.wide_offsets && unit_offsets_wide(ix.n_postings)) return hipErrorInvalidValue;
+  if (fp.wide_offsets) {
+    if (fp.max_n_scan <= 64)
+      hipLaunchKernelGGL((unit_fast_kernel<128, 12, 64, 0, false, true, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+    else
+      hipLaunchKernelGGL((unit_fast_kernel<128, 12, NSCAN_MAX, 0, false, true, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+  } else if (fp.max_n_scan <= 64)
     hipLaunchKernelGGL((unit_fast_kernel<128, 12, 64, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
   else
     hipLaunchKernelGGL((unit_fast_kernel<128, 12, NSCAN_MAX, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);

@@ -71,7 +71,13 @@ struct FastParams {
   // the id form at unit_capacity 1536 runs as two-wave units, unit_fast_kernel<128, 12>, not as <256, 6> (SANN_UNIT_WAVES=4
   // keeps the four-wave units); 0 wherever that instantiation does not exist
   int two_wave;
+  // the two-wave units gather with 64-bit addresses (unit_fast_kernel's W64), not with a 32-bit byte offset from the id
+  // column's base: set where unit_offsets_wide() says so, or by SANN_UNIT_OFFSETS=64; meaningless without two_wave
+  int wide_offsets;
 };
+// Whether 8-byte positions of an index of n_postings do NOT all fit a 32-bit byte offset (host and launcher agree on this).
+constexpr bool unit_offsets_wide(uint64_t n_postings) { return n_postings >= (1ull << 29); }
+constexpr int unit_offset_bits(uint64_t n_postings, bool forced_wide) { return (forced_wide || unit_offsets_wide(n_postings)) ? 64 : 32; }
 hipError_t launch_cut(const IndexView &ix, int M, uint32_t *out, hipStream_t stream);
 hipError_t launch_desc(const IndexView &ix, const BatchView &b, int n_units, int max_n_scan, int k_local_floor, hipStream_t stream);
 hipError_t launch_unit_ablation(const IndexView &ix, const BatchView &b, const FastParams &fp, int abl, hipStream_t stream);

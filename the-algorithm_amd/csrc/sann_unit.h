@@ -14,7 +14,7 @@ constexpr int NSCAN_MAX = 128;   // scanned clusters a fast unit can describe
 // Per-unit side tables are sized by the unit's posting capacity (WG*U) so that small units keep
 // LDS small and occupancy high:
 //   blocked Bloom filter  capacity/2 64-bit words (>= 256), 4 bits per posting (two per 32-bit half): ~0.005 % false flags
-//                         (the two-wave units of 1536 postings: 1024 words, 6 bits per posting -- bloom_bits6 below)
+//                         (the two-wave units of 1536 postings: 1024 words, 6 bits per posting -- bloom_product below)
 //   "flagged" filter      256 words (64 beside the 16 KB and the 8 KB filter)
 //   match list            64 entries up to 1024 postings, 128 above
 constexpr float APPROX_EPS = 4e-6f;  // bound on |approx/exact - 1| of the fp32 pre-filter (actual < 1e-6)
@@ -107,7 +107,7 @@ __device__ inline uint32_t cluster_cut_from_key(uint32_t kc) { return kc > 0x800
 // longer); two per half flag one in seventeen, and the halves are built by 32-bit shifts (8 instructions, not 13).
 // (Round 10 simulated it again, with table_hash and with ideal hashes: 1264 distinct ids in 2048 words get a false flag in
 // 2.4-3.2 % of the units; the same four bits in 1024 words in 10-11 %: halving the filter needs more bits per posting,
-// which is bloom_bits6 below.  Measured at the benchmark's shape: 10,752-10,766 of 32,768 units flagged with this filter,
+// which is bloom_product below.  Measured at the benchmark's shape: 10,752-10,766 of 32,768 units flagged with this filter,
 // nearly all of them by tweets that do sit in two scanned clusters; 10,862 with the 8 KB one.)
 __device__ inline unsigned long long bloom_bits(uint32_t hv) {
   const uint32_t lo = (1u << (hv & 31)) | (1u << ((hv >> 5) & 31));
@@ -119,21 +119,29 @@ constexpr int BLOOM_POS_BITS = 20;
 constexpr int bloom_log2(int capacity) { return capacity <= 512 ? 8 : capacity <= 1024 ? 9 : 11; }
 
 // The 8 KB filter of the two-wave units (1536 postings over 1024 words): SIX bits of one 64-bit word, three in either
-// half -- still ONE returning atomic per posting.  hv carries all 32 hash bits there: the word is its top ten, and the
-// thirty position bits are a second multiplicative hash of hv itself (equal ids have equal hv, so equal words and bits: no
-// false negative; distinct hv behave as independent).  Simulated at 1264 distinct ids per unit: 2.9-3.2 % of the units get
-// a false flag, against 2.4-3.2 % for the four bits in 2048 words above and 10-11 % for four bits in 1024 words.
+// half -- still ONE returning atomic per posting -- made of ONE multiply per posting.  The kernel is paced by instruction
+// issue (profiles/NOTES.md, round 12) and a 32-bit multiply holds the vector pipe four times as long as a shift; round 10
+// made the bits with a second multiplicative hash of table_hash (two multiplies and a shift-xor per posting, and again
+// wherever the mask was rebuilt).  bloom_product is the full 64-bit product of table_hash's fold of the id with
+// table_hash's constant (one v_mad_u64_u32): its LOW half is table_hash(id, 32) -- the word is its top ten bits, the flagged
+// filter's word its top six --, its HIGH half is the thirty position bits: bit j of it is bit 32 + j of the product,
+// below the carries of all of the fold.  Equal ids have equal folds, so equal words and bits: no false negative.
+// tools/bloom_sim.py, 1264 distinct ids per unit: 2.9-3.3 % of the units get a false flag (round 10's bits: 2.8-3.5 % in
+// the same runs; four bits in 2048 words, above: 2.4-3.2 %; four bits in 1024 words: 10-11 %).
 // (Two words with one bit per half each flag as few -- 1.9-2.6 % -- but need two atomics to different addresses, and
 // nothing orders those between two postings of one tweet: A first in word 1 and B first in word 2 leaves each of them
 // seeing one word set, neither is flagged, and the tweet is scored twice.  One atomic cannot be split like that.)
-__device__ inline unsigned long long bloom_bits6(uint32_t hv) {
-  uint32_t g = hv * 0x85EBCA6Bu;
-  g ^= g >> 13;
-  const uint32_t lo = (1u << ((g >> 2) & 31)) | (1u << ((g >> 7) & 31)) | (1u << ((g >> 12) & 31));
-  const uint32_t hi = (1u << ((g >> 17) & 31)) | (1u << ((g >> 22) & 31)) | (1u << (g >> 27));
+constexpr int BLOOM8K_LOG2 = 10;
+__device__ inline uint32_t bloom_fold(long long id) {
+  uint32_t x = (uint32_t)((uint64_t)id ^ ((uint64_t)id >> 32));
+  return x ^ (x >> 15);
+}
+__device__ inline unsigned long long bloom_product(uint32_t fold) { return (unsigned long long)fold * 0x9E3779B1u; }
+__device__ inline unsigned long long bloom_product_bits(uint32_t h) {  // h = the product's high half
+  const uint32_t lo = (1u << (h & 31)) | (1u << ((h >> 5) & 31)) | (1u << ((h >> 10) & 31));
+  const uint32_t hi = (1u << ((h >> 15) & 31)) | (1u << ((h >> 20) & 31)) | (1u << ((h >> 25) & 31));
   return ((unsigned long long)hi << 32) | lo;
 }
-constexpr int BLOOM8K_LOG2 = 10;
 
 // CTL_LIVE: live postings (final behind the gather's barrier); CTL_FOLD: those of them that folded into a representative
 // of their tweet (the duplicate phase); live tweets = CTL_LIVE - CTL_FOLD

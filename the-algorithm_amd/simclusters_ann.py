@@ -186,6 +186,8 @@ _PROTOS = {
     "sann_debug_unit_arrays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sann_debug_id_column": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sann_debug_unit_waves": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sann_debug_unit_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "sann_unit_offset_bits": (C.c_int32, [C.c_uint64, C.c_int32]),
     "sann_debug_index_id_column": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     "sann_debug_phase_cycles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
     "sann_batch_destroy": (C.c_int, [C.c_void_p]),
@@ -590,6 +592,13 @@ class QueryBatch:
         w, c = C.c_int32(), C.c_int32()
         _check(load_library().sann_debug_unit_waves(self._h, C.byref(w), C.byref(c)))
         return int(w.value), int(c.value)
+
+    def unit_offsets(self) -> int:
+        """sann_debug_unit_offsets: bits of the posting offsets the last run()'s unit kernel gathered with (32: the two-wave
+        units' byte offsets from the id column's base; 64; 0 if it launched none)."""
+        w = C.c_int32()
+        _check(load_library().sann_debug_unit_offsets(self._h, C.byref(w)))
+        return int(w.value)
 
     def overflow_reasons(self) -> np.ndarray:
         """sann_debug_overflow_reasons: units flagged UNIT_OVERFLOW by reason (1 scanned clusters, 2 postings, 3 match
