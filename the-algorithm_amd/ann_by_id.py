@@ -14,6 +14,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from . import binding as _binding
 from .dense_ann import BruteForceIndex
 from .hnsw_ann import Hnsw, HnswParams
 from .simclusters_ann import load_library
@@ -36,20 +37,8 @@ class AnnByIdError(RuntimeError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_ann_by_id_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._ann_by_id_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise AnnByIdError(f"ann_by_id error {rc}: {lib.ann_by_id_last_error().decode()}")
+_lib = _binding.binder(PROTOS, "ann_by_id", load_library)
+_check = _binding.checker(AnnByIdError, "ann_by_id", "ann_by_id_last_error")
 
 
 def _keys(keys, what: str) -> np.ndarray:
@@ -61,8 +50,10 @@ def _keys(keys, what: str) -> np.ndarray:
     return np.ascontiguousarray(a, np.int64)
 
 
-class EmbeddingStore:
+class EmbeddingStore(_binding.Handle):
     """EmbeddingProducer resident in HBM: fp32 rows under unique int64 keys (ann_store_build).  Immutable once built."""
+
+    _destroy, _lib = "ann_store_destroy", staticmethod(_lib)
 
     def __init__(self, handle, n: int, d: int):
         self._h, self.n, self.d = handle, n, d
@@ -91,17 +82,6 @@ class EmbeddingStore:
         lib = _lib()
         _check(lib, lib.ann_store_get(self._h, k.shape[0], k.ctypes.data, out.ctypes.data, found.ctypes.data))
         return out, found.astype(bool)
-
-    def close(self) -> None:
-        if self._h:
-            _lib().ann_store_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class QueryableById:

@@ -7,6 +7,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .simclusters_ann import SimClustersANNConfig, load_library, sann_config_t
 
 
@@ -53,24 +54,9 @@ class CodecError(ValueError):
         self.code = code
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_codec_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._codec_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise CodecError(rc, lib.ann_codec_last_error().decode())
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
+_lib = _binding.binder(PROTOS, "codec", load_library)
+_check = _binding.checker(CodecError, "ann_codec", "ann_codec_last_error", with_code=True)
+_p = _binding.ptr
 
 
 def _encode(call) -> bytes:

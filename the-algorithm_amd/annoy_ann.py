@@ -18,6 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .dense_ann import DistanceMetric
 from .ivf_ann import IvfError, _rows
 from .simclusters_ann import load_library
@@ -61,20 +62,8 @@ class AnnoyError(IvfError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_annoy_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._annoy_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise AnnoyError(f"annoy_ann error {rc}: {lib.annoy_last_error().decode()}")
+_lib = _binding.binder(PROTOS, "annoy", load_library)
+_check = _binding.checker(AnnoyError, "annoy_ann", "annoy_last_error")
 
 
 def _metric(metric) -> DistanceMetric:
@@ -107,9 +96,11 @@ def prepare(metric, rows: np.ndarray) -> np.ndarray:
     return out
 
 
-class AnnoyForest:
+class AnnoyForest(_binding.Handle):
     """The forest in its flat host form: build() it from rows or load() it from arrays; the arrays are properties.  Host
     only: no device is touched."""
+
+    _destroy, _lib = "annoy_forest_destroy", staticmethod(_lib)
 
     def __init__(self, handle, owned: bool = True, keeper=None):
         self._h, self._owned, self._keeper = handle, owned, keeper
@@ -180,20 +171,11 @@ class AnnoyForest:
     def items(self) -> np.ndarray:
         return self._get("annoy_forest_get_items", (self.info()["n_items"],), np.int32)
 
-    def close(self) -> None:
-        if self._h and self._owned:
-            _lib().annoy_forest_destroy(self._h)
-        self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class AnnoyQueryable:
+class AnnoyQueryable(_binding.Handle):
     """The Annoy index resident in HBM, immutable: from_forest() or build(), then query / queryWithDistance / search."""
+
+    _destroy, _lib = "annoy_index_destroy", staticmethod(_lib)
 
     def __init__(self, handle, metric: DistanceMetric, d: int, n_trees: int):
         self._h, self.metric, self.d, self.n_trees = handle, metric, d, n_trees
@@ -205,13 +187,9 @@ class AnnoyQueryable:
         v = _rows(rows, i["d"])
         if v.shape[0] != i["n"]:
             raise ValueError(f"the forest was built over {i['n']} rows, got {v.shape[0]}")
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per row")
+        idp = _binding.ids_or_none(ids, v.shape[0], "row")
         h = C.c_void_p()
-        _check(lib, lib.annoy_index_from_forest(device, forest._h, v.ctypes.data, idp.ctypes.data if idp is not None else None,
+        _check(lib, lib.annoy_index_from_forest(device, forest._h, v.ctypes.data, _binding.ptr(idp),
                                                 C.byref(h)))
         return cls(h, i["metric"], i["d"], i["n_trees"])
 
@@ -221,14 +199,10 @@ class AnnoyQueryable:
         lib = _lib()
         metric = _metric(metric)
         v = _rows(rows)
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per row")
+        idp = _binding.ids_or_none(ids, v.shape[0], "row")
         h = C.c_void_p()
         _check(lib, lib.annoy_index_build(device, int(metric), v.shape[1], v.shape[0], v.ctypes.data,
-                                          idp.ctypes.data if idp is not None else None, n_trees, leaf_size, seed, threads, C.byref(h)))
+                                          _binding.ptr(idp), n_trees, leaf_size, seed, threads, C.byref(h)))
         return cls(h, metric, v.shape[1], n_trees)
 
     def info(self) -> dict:
@@ -248,9 +222,7 @@ class AnnoyQueryable:
         lib = _lib()
         q = _rows(queries, self.d)
         nq = q.shape[0]
-        dist = np.zeros((nq, max(k, 0)), np.float32)
-        ids = np.zeros((nq, max(k, 0)), np.int64)
-        cnt = np.zeros(nq, np.int32)
+        ids, dist, cnt = _binding.result_triple(nq, k, clamp=True)
         _check(lib, lib.annoy_search(self._h, nq, q.ctypes.data, k, -1 if nodes_to_explore is None else int(nodes_to_explore),
                                      dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data))
         return ids, dist, cnt
@@ -307,17 +279,6 @@ class AnnoyQueryable:
     def debug_set_limits(self, first_queue_capacity: int = 0, scratch_budget_bytes: int = 0) -> None:
         lib = _lib()
         _check(lib, lib.annoy_debug_set_limits(self._h, first_queue_capacity, scratch_budget_bytes))
-
-    def close(self) -> None:
-        if self._h:
-            _lib().annoy_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class RawAnnoyIndexBuilder:

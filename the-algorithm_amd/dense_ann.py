@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .simclusters_ann import load_library
 
 
@@ -50,25 +51,15 @@ class DannError(RuntimeError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_dann_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._dann_ready = True
-    return lib
+_lib = _binding.binder(PROTOS, "dann", load_library)
+_check = _binding.checker(DannError, "dense_ann", "dann_last_error")
 
 
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise DannError(f"dense_ann error {rc}: {lib.dann_last_error().decode()}")
-
-
-class BruteForceIndex:
+class BruteForceIndex(_binding.Handle):
     """Exhaustive index resident in HBM, appendable like the reference's in-memory queue (BruteForceIndex.scala:40-64):
     append() adds rows on the device, and a search answers as it would on one build over all rows so far."""
+
+    _destroy, _lib = "dann_index_destroy", staticmethod(_lib)
 
     def __init__(self, handle, metric: DistanceMetric, n: int, d: int):
         self._h, self.metric, self.n, self.d = handle, DistanceMetric(metric), n, d
@@ -81,15 +72,10 @@ class BruteForceIndex:
         v = np.ascontiguousarray(vectors, np.float32)
         if v.ndim != 2:
             raise ValueError("vectors must be [n, d]")
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per vector")
+        idp = _binding.ids_or_none(ids, v.shape[0])
         h = C.c_void_p()
         fn = lib.dann_index_build_exact if exact else lib.dann_index_build
-        _check(lib, fn(device, int(metric), v.shape[0], v.shape[1], v.ctypes.data,
-                       idp.ctypes.data if idp is not None else None, C.byref(h)))
+        _check(lib, fn(device, int(metric), v.shape[0], v.shape[1], v.ctypes.data, _binding.ptr(idp), C.byref(h)))
         return cls(h, metric, v.shape[0], v.shape[1])
 
     @classmethod
@@ -106,12 +92,8 @@ class BruteForceIndex:
         v = np.ascontiguousarray(vectors, np.float32)
         if v.ndim != 2 or v.shape[1] != self.d:
             raise ValueError(f"vectors must be [n, {self.d}], got shape {v.shape}")
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per vector")
-        _check(lib, lib.dann_index_append(self._h, v.shape[0], v.ctypes.data, idp.ctypes.data if idp is not None else None))
+        idp = _binding.ids_or_none(ids, v.shape[0])
+        _check(lib, lib.dann_index_append(self._h, v.shape[0], v.ctypes.data, _binding.ptr(idp)))
         self.n += v.shape[0]
 
     def reserve(self, capacity: int) -> None:
@@ -142,9 +124,7 @@ class BruteForceIndex:
         if q.shape[1] != self.d:
             raise ValueError(f"query dimension {q.shape[1]} != index dimension {self.d}")
         nq = q.shape[0]
-        dist = np.empty((nq, k), np.float32)
-        ids = np.empty((nq, k), np.int64)
-        cnt = np.empty(nq, np.int32)
+        ids, dist, cnt = _binding.result_triple(nq, k)
         _check(lib, lib.dann_search(self._h, nq, q.ctypes.data, k, dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data))
         return ids, dist, cnt
 
@@ -164,17 +144,6 @@ class BruteForceIndex:
         _check(lib, lib.dann_last_timing(self._h, C.byref(a), C.byref(b), C.byref(s)))
         return a.value, b.value, s.value
 
-    def close(self) -> None:
-        if self._h:
-            _lib().dann_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def compose(shard_results: Sequence[Tuple[np.ndarray, np.ndarray, np.ndarray]], k: int):
     """ComposedQueryable.queryWithDistance (ShardApi.scala:71-87) for batched answers: concatenate every
@@ -191,11 +160,7 @@ def compose(shard_results: Sequence[Tuple[np.ndarray, np.ndarray, np.ndarray]], 
     s_ids = np.ascontiguousarray(np.stack([pad(r[0], np.int64) for r in shard_results]))
     s_dist = np.ascontiguousarray(np.stack([pad(r[1], np.float32) for r in shard_results]))
     s_cnt = np.ascontiguousarray(np.stack([np.asarray(r[2], np.int32) for r in shard_results]))
-    ids = np.zeros((nq, k), np.int64)
-    dist = np.zeros((nq, k), np.float32)
-    cnt = np.zeros(nq, np.int32)
-    def ptr(a):
-        return a.ctypes.data_as(C.c_void_p)
-
+    ids, dist, cnt = _binding.result_triple(nq, k)
+    ptr = _binding.ptr
     _check(lib, lib.dann_compose_shards(len(shard_results), nq, k_in, ptr(s_ids), ptr(s_dist), ptr(s_cnt), k, ptr(ids), ptr(dist), ptr(cnt)))
     return ids, dist, cnt

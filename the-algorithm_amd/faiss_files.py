@@ -18,9 +18,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from . import dense_ann, opq_ann, polysemous_ann
 from .dense_ann import DistanceMetric
-from .ivf_ann import FaissIvfFlat, FaissQueryable, IvfError, _rows
+from .ivf_ann import KIND_IVF_FLAT, KIND_IVF_PQ, KIND_OPQ_IVF_PQ, FaissIvfFlat, FaissQueryable, IvfError, _rows  # noqa: F401
 from .ivfpq_ann import KSUB, FaissIvfPq
 from .opq_ann import FaissOpqIvfPq
 from .shard_set import ShardSet
@@ -48,7 +49,6 @@ PROTOS = {
     "faiss_index_ids_mode": (C.c_int, [C.c_int32, C.c_void_p, _P(C.c_int32)]),
 }
 
-KIND_IVF_FLAT, KIND_IVF_PQ, KIND_OPQ_IVF_PQ = 1, 2, 3
 IDS_POSITIONS, IDS_GIVEN, IDS_NONE = 0, 1, 2
 INDEX_FILE_NAME = "faiss.index"
 SUCCESS_FILE_NAME = "_SUCCESS"
@@ -62,20 +62,9 @@ class FaissFileError(IvfError):
         self.code, self.message = code, message
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_faiss_files_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._faiss_files_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise FaissFileError(rc, lib.faiss_last_error().decode())
+_lib = _binding.binder(PROTOS, "faiss_files", load_library)
+_check = _binding.checker(FaissFileError, "faiss_files", "faiss_last_error", with_code=True)
+_FAMILY = {cls.FAISS_KIND: cls for cls in (FaissIvfFlat, FaissIvfPq, FaissOpqIvfPq)}
 
 
 def _path(p) -> bytes:
@@ -83,7 +72,7 @@ def _path(p) -> bytes:
 
 
 def _ptr(a: Optional[np.ndarray]):
-    return None if a is None or a.size == 0 else a.ctypes.data
+    return _binding.ptr(None if a is None or a.size == 0 else a)
 
 
 # ---- the file, host only ------------------------------------------------------------------------------------------------
@@ -162,15 +151,9 @@ def write_index(index, directory) -> None:
     """swigfaiss.write_index + copyToOutputAndCreateSuccess (FaissIndexer.scala:95-110): the index file under a temporary
     name, renamed to faiss.index, then the empty _SUCCESS.  A directory that holds a faiss.index is refused."""
     lib = _lib()
-    if isinstance(index, FaissOpqIvfPq):
-        fn = lib.faiss_opq_index_save_directory
-    elif isinstance(index, FaissIvfPq):
-        fn = lib.faiss_ivfpq_index_save_directory
-    elif isinstance(index, FaissIvfFlat):
-        fn = lib.faiss_ivf_index_save_directory
-    else:
+    if getattr(index, "FAISS_KIND", None) not in _FAMILY:
         raise TypeError(f"write_index: {type(index).__name__} is not one of FaissIvfFlat, FaissIvfPq, FaissOpqIvfPq")
-    _check(lib, fn(index._h, _path(directory)))
+    _check(lib, getattr(lib, f"faiss_{index._prefix}_index_save_directory")(index._h, _path(directory)))
 
 
 def build_and_write_faiss_index(vectors: np.ndarray, ids: Sequence[int], sample_rate: float, factory_string: Optional[str],
@@ -187,7 +170,7 @@ def build_and_write_faiss_index(vectors: np.ndarray, ids: Sequence[int], sample_
 
 
 def _kind_of(index) -> int:
-    return KIND_OPQ_IVF_PQ if isinstance(index, FaissOpqIvfPq) else KIND_IVF_PQ if isinstance(index, FaissIvfPq) else KIND_IVF_FLAT
+    return getattr(index, "FAISS_KIND", KIND_IVF_FLAT)
 
 
 def ids_mode(index) -> int:
@@ -213,21 +196,7 @@ def load_native_index(dimension: int, metric: DistanceMetric, directory, *, devi
     lib = _lib()
     kind, h = C.c_int32(), C.c_void_p()
     _check(lib, lib.faiss_index_load_directory(device, _path(directory), int(dimension), int(metric), C.byref(kind), C.byref(h)))
-    n = C.c_int64()
-    v = [C.c_int32() for _ in range(5)]
-    if kind.value == KIND_IVF_FLAT:
-        from . import ivf_ann
-        il = ivf_ann._lib()
-        ivf_ann._check(il, il.ivf_index_info(h, C.byref(n), C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
-        return FaissIvfFlat(h, DistanceMetric(v[1].value), v[0].value, v[2].value)
-    if kind.value == KIND_IVF_PQ:
-        from . import ivfpq_ann
-        il = ivfpq_ann._lib()
-        ivfpq_ann._check(il, il.ivfpq_index_info(h, C.byref(n), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3])))
-        return FaissIvfPq(h, DistanceMetric(v[1].value), v[0].value, v[2].value, v[3].value)
-    il = opq_ann._lib()
-    opq_ann._check(il, il.opq_index_info(h, C.byref(n), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]), C.byref(v[4])))
-    return FaissOpqIvfPq(h, DistanceMetric(v[2].value), v[0].value, v[1].value, v[3].value, v[4].value)
+    return _FAMILY[kind.value]._from_handle(h)
 
 
 class FaissIndex:

@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .dense_ann import DistanceMetric
 from .simclusters_ann import load_library
 
@@ -40,29 +41,9 @@ class GroupedError(RuntimeError):
         self.code = code
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_gann_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._gann_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise GroupedError(rc, lib.gann_last_error().decode())
-
-
-def _rows(a, d: Optional[int] = None) -> np.ndarray:
-    v = np.ascontiguousarray(a, np.float32)
-    if v.ndim == 1:
-        v = v[None, :]
-    if v.ndim != 2 or (d is not None and v.shape[1] != d):
-        raise ValueError(f"expected rows of dimension {d}, got shape {v.shape}")
-    return v
+_lib = _binding.binder(PROTOS, "gann", load_library)
+_check = _binding.checker(GroupedError, "grouped_ann", "gann_last_error", with_code=True)
+_rows = _binding.rows
 
 
 def key_table(keys: Sequence[str]) -> Tuple[List[str], np.ndarray]:
@@ -92,8 +73,10 @@ def group_rows(entity_ids: Sequence[Optional[int]], embeddings: Sequence[Sequenc
     return out
 
 
-class GroupedIndex:
+class GroupedIndex(_binding.Handle):
     """All groups in one index resident in HBM; search() answers every query from the rows of its own key."""
+
+    _destroy, _lib = "gann_index_destroy", staticmethod(_lib)
 
     def __init__(self, handle, metric: DistanceMetric, d: int, keys: List[str]):
         self._h, self.metric, self.d = handle, DistanceMetric(metric), d
@@ -110,14 +93,10 @@ class GroupedIndex:
         g = np.ascontiguousarray(groups, np.int32)
         if g.shape != (v.shape[0],):
             raise ValueError("one group per vector")
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per vector")
+        idp = _binding.ids_or_none(ids, v.shape[0])
         h = C.c_void_p()
         _check(lib, lib.gann_index_build(device, int(metric), v.shape[1], len(keys), v.shape[0], v.ctypes.data,
-                                         idp.ctypes.data if idp is not None else None, g.ctypes.data, C.byref(h)))
+                                         _binding.ptr(idp), g.ctypes.data, C.byref(h)))
         return cls(h, metric, v.shape[1], list(keys))
 
     @classmethod
@@ -141,9 +120,7 @@ class GroupedIndex:
         g = np.ascontiguousarray(groups, np.int32)
         if g.shape != (nq,):
             raise ValueError("one group per query")
-        dist = np.zeros((nq, k), np.float32)
-        ids = np.zeros((nq, k), np.int64)
-        cnt = np.zeros(nq, np.int32)
+        ids, dist, cnt = _binding.result_triple(nq, k)
         _check(lib, lib.gann_search(self._h, nq, q.ctypes.data, g.ctypes.data, k, dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data))
         return ids, dist, cnt
 
@@ -173,17 +150,6 @@ class GroupedIndex:
                                         C.byref(a), C.byref(b), C.byref(s)))
         return {"tiles": tiles.value, "work_items": work.value, "rounds": rounds.value, "rows_scanned": rows.value,
                 "segment_rows": seg.value, "worklist_ms": a.value, "scan_ms": b.value, "select_ms": s.value}
-
-    def close(self) -> None:
-        if self._h:
-            _lib().gann_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class GroupedQueryable:

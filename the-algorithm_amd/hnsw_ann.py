@@ -14,6 +14,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .dense_ann import DistanceMetric
 from .simclusters_ann import load_library
 
@@ -52,24 +53,9 @@ class HnswError(RuntimeError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_hnsw_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._hnsw_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise HnswError(f"hnsw_ann error {rc}: {lib.hnsw_last_error().decode()}")
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data
+_lib = _binding.binder(PROTOS, "hnsw", load_library)
+_check = _binding.checker(HnswError, "hnsw_ann", "hnsw_last_error")
+_p = _binding.ptr
 
 
 @dataclass
@@ -78,8 +64,10 @@ class HnswParams:
     ef: int
 
 
-class Hnsw:
+class Hnsw(_binding.Handle):
     """Device-resident HNSW index (graph + vectors), appendable like the reference's (Hnsw.append, Hnsw.scala:86-114)."""
+
+    _destroy, _lib = "hnsw_index_destroy", staticmethod(_lib)
 
     def __init__(self, handle, metric, n, d, max_m):
         self._h, self.metric, self.n, self.d, self.max_m = handle, DistanceMetric(metric), n, d, max_m
@@ -215,7 +203,7 @@ class Hnsw:
         if q.shape[1] != self.d:
             raise ValueError(f"query dimension {q.shape[1]} != index dimension {self.d}")
         nq = q.shape[0]
-        dist = np.zeros((nq, k), np.float32); ids = np.zeros((nq, k), np.int64); cnt = np.zeros(nq, np.int32)
+        ids, dist, cnt = _binding.result_triple(nq, k)
         _check(lib, lib.hnsw_search(self._h, nq, _p(q), k, ef, _p(dist), _p(ids), _p(cnt)))
         return ids, dist, cnt
 
@@ -242,14 +230,3 @@ class Hnsw:
         _check(lib, lib.hnsw_last_walk_counters(self._h, C.byref(e), C.byref(f)))
         return dict(distance_evals=a.value, expansions=b.value, spilled_queries=c.value, kernel_ms=d.value, admissions=e.value,
                     largest_candidate_queue=f.value)
-
-    def close(self):
-        if self._h:
-            _lib().hnsw_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -16,6 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .dense_ann import DistanceMetric
 from .simclusters_ann import load_library
 
@@ -37,42 +38,106 @@ PROTOS = {
 }
 
 MAX_COSINE_DISTANCE = 1.0
+# FAISS_KIND_* of include/faiss_files.h
+KIND_IVF_FLAT, KIND_IVF_PQ, KIND_OPQ_IVF_PQ = 1, 2, 3
 
 
 class IvfError(RuntimeError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_ivf_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._ivf_ready = True
-    return lib
+_lib = _binding.binder(PROTOS, "ivf", load_library)
+_check = _binding.checker(IvfError, "ivf_ann", "ivf_last_error")
+_rows = _binding.rows
 
 
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise IvfError(f"ivf_ann error {rc}: {lib.ivf_last_error().decode()}")
+class _IvfFamilyIndex(_binding.Handle):
+    """What FaissIvfFlat, FaissIvfPq and FaissOpqIvfPq share: the calls whose C symbols differ by their prefix alone.  A
+    subclass names its prefix, its module's _lib / _check, the attribute that holds the dimension of incoming rows, its
+    FAISS_KIND_* of include/faiss_files.h and how many int32 fields its *_index_info reports after n."""
+
+    _prefix = ""
+    _check = None
+    _row_dim = "d"
+    _info_fields = 0
+    _STATS = ("coarse_ms", "scan_ms", "select_ms")  # the float fields of *_last_stats
+    FAISS_KIND = 0
+
+    def _call(self, name: str, *args) -> None:
+        lib = self._lib()
+        self._check(lib, getattr(lib, self._prefix + name)(self._h, *args))
+
+    @classmethod
+    def _read_info(cls, handle):
+        """(n, the int32 fields) of *_index_info."""
+        n, v = C.c_int64(), [C.c_int32() for _ in range(cls._info_fields)]
+        lib = cls._lib()
+        cls._check(lib, getattr(lib, cls._prefix + "_index_info")(handle, C.byref(n), *[C.byref(x) for x in v]))
+        return n.value, [x.value for x in v]
+
+    @property
+    def n(self) -> int:
+        return self._read_info(self._h)[0]
+
+    def add(self, vectors: np.ndarray, ids: Optional[Sequence[int]] = None) -> None:
+        """add_with_ids.  ids on every call or on none (ids = positions in the order added)."""
+        v = _rows(vectors, getattr(self, self._row_dim))
+        idp = _binding.ids_or_none(ids, v.shape[0])
+        self._call("_index_add", v.shape[0], v.ctypes.data, _binding.ptr(idp))
+
+    def search(self, queries: np.ndarray, k: int, nprobe: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(ids [nq, k], distances [nq, k], counts [nq]): the k nearest rows (IVF-Flat) or codes (IVF-PQ; OPQ: over the
+        transformed queries) of the nprobe nearest cells' lists, ascending by (distance, id); counts may fall short of k."""
+        q = _rows(queries, getattr(self, self._row_dim))
+        ids, dist, cnt = _binding.result_triple(q.shape[0], k)
+        self._call("_search", q.shape[0], q.ctypes.data, k, nprobe, dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data)
+        return ids, dist, cnt
+
+    def centroids(self) -> np.ndarray:
+        out = np.empty((self.nlist, self.d), np.float32)
+        self._call("_index_get_centroids", out.ctypes.data)
+        return out
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.empty(self.nlist, np.int64)
+        self._call("_index_list_sizes", out.ctypes.data)
+        return out
+
+    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(ids [n], cells [n]) of the rows in the order they were added."""
+        n = self.n
+        ids, cells = np.empty(n, np.int64), np.empty(n, np.int32)
+        self._call("_index_get_assignment", ids.ctypes.data, cells.ctypes.data)
+        return ids, cells
+
+    def last_probes(self) -> np.ndarray:
+        """The cells the last search probed, nearest first: int32 [nq, nprobe] (nprobe after clamping to nlist)."""
+        nq, npr = C.c_int32(), C.c_int32()
+        self._call("_last_probes", C.byref(nq), C.byref(npr), None)
+        out = np.empty((nq.value, npr.value), np.int32)
+        self._call("_last_probes", None, None, out.ctypes.data)
+        return out
+
+    def last_stats(self) -> dict:
+        rows, rounds = C.c_int64(), C.c_int32()
+        ms = [C.c_float() for _ in self._STATS]
+        self._call("_last_stats", C.byref(rows), C.byref(rounds), *[C.byref(x) for x in ms])
+        return {"rows_scanned": rows.value, "rounds": rounds.value, **{name: x.value for name, x in zip(self._STATS, ms)}}
 
 
-def _rows(a, d: Optional[int] = None) -> np.ndarray:
-    v = np.ascontiguousarray(a, np.float32)
-    if v.ndim == 1:
-        v = v[None, :]
-    if v.ndim != 2 or (d is not None and v.shape[1] != d):
-        raise ValueError(f"expected rows of dimension {d}, got shape {v.shape}")
-    return v
-
-
-class FaissIvfFlat:
+class FaissIvfFlat(_IvfFamilyIndex):
     """`IVF<nlist>,Flat` in an id map, resident in HBM: train() or load() the coarse quantizer, add() rows, search()."""
+
+    _prefix, _destroy, _info_fields, FAISS_KIND = "ivf", "ivf_index_destroy", 3, KIND_IVF_FLAT
+    _lib, _check = staticmethod(_lib), staticmethod(_check)
 
     def __init__(self, handle, metric: DistanceMetric, d: int, nlist: int):
         self._h, self.metric, self.d, self.nlist = handle, DistanceMetric(metric), d, nlist
+
+    @classmethod
+    def _from_handle(cls, handle):
+        _, (d, metric, nlist) = cls._read_info(handle)
+        return cls(handle, DistanceMetric(metric), d, nlist)
 
     @classmethod
     def train(cls, metric: DistanceMetric, nlist: int, train_vectors: np.ndarray, *, niter: int = 0, seed: int = 1, device: int = 0):
@@ -90,83 +155,6 @@ class FaissIvfFlat:
         h = C.c_void_p()
         _check(lib, lib.ivf_index_load(device, int(metric), c.shape[1], c.shape[0], c.ctypes.data, C.byref(h)))
         return cls(h, metric, c.shape[1], c.shape[0])
-
-    @property
-    def n(self) -> int:
-        n = C.c_int64()
-        lib = _lib()
-        _check(lib, lib.ivf_index_info(self._h, C.byref(n), None, None, None))
-        return n.value
-
-    def add(self, vectors: np.ndarray, ids: Optional[Sequence[int]] = None) -> None:
-        """add_with_ids.  ids on every call or on none (ids = positions in the order added)."""
-        lib = _lib()
-        v = _rows(vectors, self.d)
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per vector")
-        _check(lib, lib.ivf_index_add(self._h, v.shape[0], v.ctypes.data, idp.ctypes.data if idp is not None else None))
-
-    def search(self, queries: np.ndarray, k: int, nprobe: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(ids [nq, k], distances [nq, k], counts [nq]): the k nearest rows of the nprobe nearest cells' lists, ascending
-        by (distance, id); counts may fall short of k."""
-        lib = _lib()
-        q = _rows(queries, self.d)
-        nq = q.shape[0]
-        dist = np.zeros((nq, k), np.float32)
-        ids = np.zeros((nq, k), np.int64)
-        cnt = np.zeros(nq, np.int32)
-        _check(lib, lib.ivf_search(self._h, nq, q.ctypes.data, k, nprobe, dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data))
-        return ids, dist, cnt
-
-    def centroids(self) -> np.ndarray:
-        out = np.empty((self.nlist, self.d), np.float32)
-        lib = _lib()
-        _check(lib, lib.ivf_index_get_centroids(self._h, out.ctypes.data))
-        return out
-
-    def list_sizes(self) -> np.ndarray:
-        out = np.empty(self.nlist, np.int64)
-        lib = _lib()
-        _check(lib, lib.ivf_index_list_sizes(self._h, out.ctypes.data))
-        return out
-
-    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(ids [n], cells [n]) of the rows in the order they were added."""
-        n = self.n
-        ids, cells = np.empty(n, np.int64), np.empty(n, np.int32)
-        lib = _lib()
-        _check(lib, lib.ivf_index_get_assignment(self._h, ids.ctypes.data, cells.ctypes.data))
-        return ids, cells
-
-    def last_probes(self) -> np.ndarray:
-        """The cells the last search probed, nearest first: int32 [nq, nprobe] (nprobe after clamping to nlist)."""
-        nq, npr = C.c_int32(), C.c_int32()
-        lib = _lib()
-        _check(lib, lib.ivf_last_probes(self._h, C.byref(nq), C.byref(npr), None))
-        out = np.empty((nq.value, npr.value), np.int32)
-        _check(lib, lib.ivf_last_probes(self._h, None, None, out.ctypes.data))
-        return out
-
-    def last_stats(self) -> dict:
-        rows, rounds = C.c_int64(), C.c_int32()
-        a, b, s = C.c_float(), C.c_float(), C.c_float()
-        lib = _lib()
-        _check(lib, lib.ivf_last_stats(self._h, C.byref(rows), C.byref(rounds), C.byref(a), C.byref(b), C.byref(s)))
-        return {"rows_scanned": rows.value, "rounds": rounds.value, "coarse_ms": a.value, "scan_ms": b.value, "select_ms": s.value}
-
-    def close(self) -> None:
-        if self._h:
-            _lib().ivf_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 @dataclass(frozen=True)

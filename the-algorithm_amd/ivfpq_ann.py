@@ -10,12 +10,13 @@ from __future__ import annotations
 
 import ctypes as C
 import re
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Sequence
 
 import numpy as np
 
 from .dense_ann import DistanceMetric
-from .ivf_ann import FaissIvfFlat, IvfError, _rows
+from . import binding as _binding
+from .ivf_ann import KIND_IVF_PQ as _KIND, FaissIvfFlat, IvfError, _IvfFamilyIndex, _rows
 from .simclusters_ann import load_library
 
 _P = C.POINTER
@@ -44,28 +45,45 @@ class IvfPqError(IvfError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_ivfpq_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._ivfpq_ready = True
-    return lib
+_lib = _binding.binder(PROTOS, "ivfpq", load_library)
+_check = _binding.checker(IvfPqError, "ivfpq_ann", "ivfpq_last_error")
 
 
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise IvfPqError(f"ivfpq_ann error {rc}: {lib.ivfpq_last_error().decode()}")
+class _PqCodes:
+    """The exports of the product quantiser, for FaissIvfPq and FaissOpqIvfPq (there `d` is the transform's d_out)."""
+
+    def codebooks(self) -> np.ndarray:
+        """fp32 [M, 256, d / M]."""
+        out = np.empty((self.M, KSUB, self.d // self.M), np.float32)
+        self._call("_index_get_codebooks", out.ctypes.data)
+        return out
+
+    def codes(self) -> np.ndarray:
+        """uint8 [n, M], the rows in the order they were added."""
+        out = np.empty((self.n, self.M), np.uint8)
+        self._call("_index_get_codes", out.ctypes.data)
+        return out
+
+    def bytes_per_row(self) -> int:
+        """Device bytes per row: the code in the order added and in its list, the id (twice: as added and sorted), the
+        cell and the slot's rank (padding of a list's last block aside).  An OPQ matrix is per index, not per row."""
+        return 2 * self.M + 8 + 8 + 4 + 4
 
 
-class FaissIvfPq:
+class FaissIvfPq(_PqCodes, _IvfFamilyIndex):
     """`IVF<nlist>,PQ<M>` (8-bit codes, residuals) in an id map, resident in HBM: train() or load() the coarse quantizer
     and the codebooks, add() rows, search().  The rows themselves are not kept."""
 
+    _prefix, _destroy, _info_fields, FAISS_KIND = "ivfpq", "ivfpq_index_destroy", 4, _KIND
+    _lib, _check = staticmethod(_lib), staticmethod(_check)
+
     def __init__(self, handle, metric: DistanceMetric, d: int, nlist: int, M: int):
         self._h, self.metric, self.d, self.nlist, self.M = handle, DistanceMetric(metric), d, nlist, M
+
+    @classmethod
+    def _from_handle(cls, handle):
+        _, (d, metric, nlist, M) = cls._read_info(handle)
+        return cls(handle, DistanceMetric(metric), d, nlist, M)
 
     @classmethod
     def train(cls, metric: DistanceMetric, nlist: int, M: int, train_vectors: np.ndarray, *, niter: int = 0, seed: int = 1,
@@ -91,102 +109,6 @@ class FaissIvfPq:
         _check(lib, lib.ivfpq_index_load(device, int(metric), c.shape[1], c.shape[0], cb.shape[0], c.ctypes.data, cb.ctypes.data,
                                          C.byref(h)))
         return cls(h, metric, c.shape[1], c.shape[0], cb.shape[0])
-
-    @property
-    def n(self) -> int:
-        n = C.c_int64()
-        lib = _lib()
-        _check(lib, lib.ivfpq_index_info(self._h, C.byref(n), None, None, None, None))
-        return n.value
-
-    def add(self, vectors: np.ndarray, ids: Optional[Sequence[int]] = None) -> None:
-        """add_with_ids.  ids on every call or on none (ids = positions in the order added)."""
-        lib = _lib()
-        v = _rows(vectors, self.d)
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per vector")
-        _check(lib, lib.ivfpq_index_add(self._h, v.shape[0], v.ctypes.data, idp.ctypes.data if idp is not None else None))
-
-    def search(self, queries: np.ndarray, k: int, nprobe: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(ids [nq, k], distances [nq, k], counts [nq]): the k nearest codes of the nprobe nearest cells' lists, ascending
-        by (distance, id); counts may fall short of k."""
-        lib = _lib()
-        q = _rows(queries, self.d)
-        nq = q.shape[0]
-        dist = np.zeros((nq, k), np.float32)
-        ids = np.zeros((nq, k), np.int64)
-        cnt = np.zeros(nq, np.int32)
-        _check(lib, lib.ivfpq_search(self._h, nq, q.ctypes.data, k, nprobe, dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data))
-        return ids, dist, cnt
-
-    def centroids(self) -> np.ndarray:
-        out = np.empty((self.nlist, self.d), np.float32)
-        lib = _lib()
-        _check(lib, lib.ivfpq_index_get_centroids(self._h, out.ctypes.data))
-        return out
-
-    def codebooks(self) -> np.ndarray:
-        """fp32 [M, 256, d / M]."""
-        out = np.empty((self.M, KSUB, self.d // self.M), np.float32)
-        lib = _lib()
-        _check(lib, lib.ivfpq_index_get_codebooks(self._h, out.ctypes.data))
-        return out
-
-    def codes(self) -> np.ndarray:
-        """uint8 [n, M], the rows in the order they were added."""
-        out = np.empty((self.n, self.M), np.uint8)
-        lib = _lib()
-        _check(lib, lib.ivfpq_index_get_codes(self._h, out.ctypes.data))
-        return out
-
-    def list_sizes(self) -> np.ndarray:
-        out = np.empty(self.nlist, np.int64)
-        lib = _lib()
-        _check(lib, lib.ivfpq_index_list_sizes(self._h, out.ctypes.data))
-        return out
-
-    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(ids [n], cells [n]) of the rows in the order they were added."""
-        n = self.n
-        ids, cells = np.empty(n, np.int64), np.empty(n, np.int32)
-        lib = _lib()
-        _check(lib, lib.ivfpq_index_get_assignment(self._h, ids.ctypes.data, cells.ctypes.data))
-        return ids, cells
-
-    def last_probes(self) -> np.ndarray:
-        """The cells the last search probed, nearest first: int32 [nq, nprobe] (nprobe after clamping to nlist)."""
-        nq, npr = C.c_int32(), C.c_int32()
-        lib = _lib()
-        _check(lib, lib.ivfpq_last_probes(self._h, C.byref(nq), C.byref(npr), None))
-        out = np.empty((nq.value, npr.value), np.int32)
-        _check(lib, lib.ivfpq_last_probes(self._h, None, None, out.ctypes.data))
-        return out
-
-    def last_stats(self) -> dict:
-        rows, rounds = C.c_int64(), C.c_int32()
-        a, b, s = C.c_float(), C.c_float(), C.c_float()
-        lib = _lib()
-        _check(lib, lib.ivfpq_last_stats(self._h, C.byref(rows), C.byref(rounds), C.byref(a), C.byref(b), C.byref(s)))
-        return {"rows_scanned": rows.value, "rounds": rounds.value, "coarse_ms": a.value, "scan_ms": b.value, "select_ms": s.value}
-
-    def bytes_per_row(self) -> int:
-        """Device bytes per row: the code in the order added and in its list, the id (twice: as added and sorted), the
-        cell and the slot's rank (padding of a list's last block aside)."""
-        return 2 * self.M + 8 + 8 + 4 + 4
-
-    def close(self) -> None:
-        if self._h:
-            _lib().ivfpq_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _FACTORY = re.compile(r"IVF(\d+),(?:(Flat)|PQ(\d+)(?:x8)?)")

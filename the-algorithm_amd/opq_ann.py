@@ -16,9 +16,10 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from . import ivfpq_ann
 from .dense_ann import DistanceMetric
-from .ivf_ann import IvfError, _rows
+from .ivf_ann import KIND_OPQ_IVF_PQ as _KIND, IvfError, _IvfFamilyIndex, _rows
 from .simclusters_ann import load_library
 
 _P = C.POINTER
@@ -56,20 +57,8 @@ class OpqError(IvfError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_opq_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._opq_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise OpqError(f"opq_ann error {rc}: {lib.opq_last_error().decode()}")
+_lib = _binding.binder(PROTOS, "opq", load_library)
+_check = _binding.checker(OpqError, "opq_ann", "opq_last_error")
 
 
 def procrustes(C_: np.ndarray) -> np.ndarray:
@@ -95,13 +84,22 @@ def debug_correlation(x: np.ndarray, y_hat: np.ndarray, *, device: int = 0) -> n
     return out
 
 
-class FaissOpqIvfPq:
+class FaissOpqIvfPq(ivfpq_ann._PqCodes, _IvfFamilyIndex):
     """`OPQ<M>_<d_out>,IVF<nlist>,PQ<M>` in an id map, resident in HBM: train() or load() the matrix, the coarse quantizer
     and the codebooks, add() rows of d_in components, search().  Rows are transformed on the device and not kept."""
+
+    _prefix, _destroy, _info_fields, FAISS_KIND = "opq", "opq_index_destroy", 5, _KIND
+    _row_dim, _STATS = "d_in", _IvfFamilyIndex._STATS + ("transform_ms",)
+    _lib, _check = staticmethod(_lib), staticmethod(_check)
 
     def __init__(self, handle, metric: DistanceMetric, d_in: int, d_out: int, nlist: int, M: int):
         self._h, self.metric, self.d_in, self.d_out, self.nlist, self.M = handle, DistanceMetric(metric), d_in, d_out, nlist, M
         self.d = d_out  # the dimension of what the exports describe (centroids, codebooks), as FaissIvfPq.d
+
+    @classmethod
+    def _from_handle(cls, handle):
+        _, (d_in, d_out, metric, nlist, M) = cls._read_info(handle)
+        return cls(handle, DistanceMetric(metric), d_in, d_out, nlist, M)
 
     @classmethod
     def train(cls, metric: DistanceMetric, nlist: int, M: int, d_out: int, train_vectors: np.ndarray, *, niter: int = 0,
@@ -128,35 +126,6 @@ class FaissOpqIvfPq:
         _check(lib, lib.opq_index_load(device, int(metric), a.shape[1], a.shape[0], c.shape[0], cb.shape[0], a.ctypes.data,
                                        c.ctypes.data, cb.ctypes.data, C.byref(h)))
         return cls(h, metric, a.shape[1], a.shape[0], c.shape[0], cb.shape[0])
-
-    @property
-    def n(self) -> int:
-        n = C.c_int64()
-        lib = _lib()
-        _check(lib, lib.opq_index_info(self._h, C.byref(n), None, None, None, None, None))
-        return n.value
-
-    def add(self, vectors: np.ndarray, ids: Optional[Sequence[int]] = None) -> None:
-        """add_with_ids.  ids on every call or on none (ids = positions in the order added)."""
-        lib = _lib()
-        v = _rows(vectors, self.d_in)
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per vector")
-        _check(lib, lib.opq_index_add(self._h, v.shape[0], v.ctypes.data, idp.ctypes.data if idp is not None else None))
-
-    def search(self, queries: np.ndarray, k: int, nprobe: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(ids [nq, k], distances [nq, k], counts [nq]) as FaissIvfPq.search, over the transformed queries."""
-        lib = _lib()
-        q = _rows(queries, self.d_in)
-        nq = q.shape[0]
-        dist = np.zeros((nq, k), np.float32)
-        ids = np.zeros((nq, k), np.int64)
-        cnt = np.zeros(nq, np.int32)
-        _check(lib, lib.opq_search(self._h, nq, q.ctypes.data, k, nprobe, dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data))
-        return ids, dist, cnt
 
     def transform(self, x: np.ndarray) -> np.ndarray:
         """What added rows and queries become before the inner index rounds them to fp16: fp32 [n, d_out] (Cosine: the
@@ -188,72 +157,6 @@ class FaissOpqIvfPq:
         lib = _lib()
         _check(lib, lib.opq_training_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(["transform_ms", "pq_ms", "correlation_ms", "procrustes_ms", "inner_ms"], [x.value for x in v]))
-
-    def centroids(self) -> np.ndarray:
-        out = np.empty((self.nlist, self.d_out), np.float32)
-        lib = _lib()
-        _check(lib, lib.opq_index_get_centroids(self._h, out.ctypes.data))
-        return out
-
-    def codebooks(self) -> np.ndarray:
-        """fp32 [M, 256, d_out / M]."""
-        out = np.empty((self.M, KSUB, self.d_out // self.M), np.float32)
-        lib = _lib()
-        _check(lib, lib.opq_index_get_codebooks(self._h, out.ctypes.data))
-        return out
-
-    def codes(self) -> np.ndarray:
-        """uint8 [n, M], the rows in the order they were added."""
-        out = np.empty((self.n, self.M), np.uint8)
-        lib = _lib()
-        _check(lib, lib.opq_index_get_codes(self._h, out.ctypes.data))
-        return out
-
-    def list_sizes(self) -> np.ndarray:
-        out = np.empty(self.nlist, np.int64)
-        lib = _lib()
-        _check(lib, lib.opq_index_list_sizes(self._h, out.ctypes.data))
-        return out
-
-    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(ids [n], cells [n]) of the rows in the order they were added."""
-        n = self.n
-        ids, cells = np.empty(n, np.int64), np.empty(n, np.int32)
-        lib = _lib()
-        _check(lib, lib.opq_index_get_assignment(self._h, ids.ctypes.data, cells.ctypes.data))
-        return ids, cells
-
-    def last_probes(self) -> np.ndarray:
-        """The cells the last search probed, nearest first: int32 [nq, nprobe] (nprobe after clamping to nlist)."""
-        nq, npr = C.c_int32(), C.c_int32()
-        lib = _lib()
-        _check(lib, lib.opq_last_probes(self._h, C.byref(nq), C.byref(npr), None))
-        out = np.empty((nq.value, npr.value), np.int32)
-        _check(lib, lib.opq_last_probes(self._h, None, None, out.ctypes.data))
-        return out
-
-    def last_stats(self) -> dict:
-        rows, rounds = C.c_int64(), C.c_int32()
-        a, b, s, t = C.c_float(), C.c_float(), C.c_float(), C.c_float()
-        lib = _lib()
-        _check(lib, lib.opq_last_stats(self._h, C.byref(rows), C.byref(rounds), C.byref(a), C.byref(b), C.byref(s), C.byref(t)))
-        return {"rows_scanned": rows.value, "rounds": rounds.value, "coarse_ms": a.value, "scan_ms": b.value, "select_ms": s.value,
-                "transform_ms": t.value}
-
-    def bytes_per_row(self) -> int:
-        """Device bytes per row: those of FaissIvfPq (the matrix is per index, not per row)."""
-        return 2 * self.M + 8 + 8 + 4 + 4
-
-    def close(self) -> None:
-        if self._h:
-            _lib().opq_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _FACTORY = re.compile(r"OPQ(\d+)(?:_(\d+))?,IVF(\d+),PQ(\d+)(?:x8)?")

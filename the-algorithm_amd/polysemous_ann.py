@@ -18,6 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from . import ivfpq_ann, opq_ann
 from .dense_ann import DistanceMetric
 from .ivf_ann import MAX_COSINE_DISTANCE, FaissParams, FaissQueryable, IvfError, _rows
@@ -53,22 +54,8 @@ class PolysemousError(IvfError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_polysemous_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        ivfpq_ann._lib()
-        opq_ann._lib()
-        lib._polysemous_ready = True
-    return lib
-
-
-def _check(lib, rc: int, last_error) -> None:
-    if rc != 0:
-        raise PolysemousError(f"polysemous_ann error {rc}: {last_error().decode()}")
+_lib = _binding.binder(PROTOS, "polysemous", load_library, also=(ivfpq_ann._lib, opq_ann._lib))
+_check = _binding.checker(PolysemousError, "polysemous_ann", None)
 
 
 def mix64(x: int) -> int:
@@ -113,28 +100,20 @@ def renumber(codebooks: np.ndarray, perms: np.ndarray) -> np.ndarray:
 def search_ht(index, queries: np.ndarray, k: int, nprobe: int, ht: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """ivfpq_search_ht / opq_search_ht over the handle of a FaissIvfPq / FaissOpqIvfPq or of its Polysemous twin; the handle
     stays with its holder."""
-    if isinstance(index, FaissOpqIvfPq):
-        prefix, d = "opq", index.d_in
-    elif isinstance(index, FaissIvfPq):
-        prefix, d = "ivfpq", index.d
-    else:
+    if getattr(index, "FAISS_KIND", None) not in _TWINS:
         raise TypeError(f"{type(index).__name__} has no product-quantiser codes to filter by")
     lib = _lib()
-    q = _rows(queries, d)
-    nq = q.shape[0]
-    dist = np.zeros((nq, k), np.float32)
-    ids = np.zeros((nq, k), np.int64)
-    cnt = np.zeros(nq, np.int32)
-    fn = getattr(lib, prefix + "_search_ht")
-    _check(lib, fn(index._h, nq, q.ctypes.data, k, nprobe, int(ht), dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data),
-           getattr(lib, prefix + "_last_error"))
+    q = _rows(queries, getattr(index, index._row_dim))
+    ids, dist, cnt = _binding.result_triple(q.shape[0], k)
+    fn = getattr(lib, index._prefix + "_search_ht")
+    _check(lib, fn(index._h, q.shape[0], q.ctypes.data, k, nprobe, int(ht), dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data),
+           getattr(lib, index._prefix + "_last_error"))
     return ids, dist, cnt
 
 
 class _HtSearch:
-    """search(queries, k, nprobe, ht) and the exports of the last filtered search, over the handle of either index type."""
-
-    _prefix = ""
+    """search(queries, k, nprobe, ht) and the exports of the last filtered search, over the handle of either index type
+    (the symbol prefix is the index class's own)."""
 
     def _last_error(self, lib):
         return getattr(lib, self._prefix + "_last_error")
@@ -172,8 +151,6 @@ class _HtSearch:
 class PolysemousIvfPq(_HtSearch, FaissIvfPq):
     """FaissIvfPq with polysemous training and the filtered search."""
 
-    _prefix = "ivfpq"
-
     @classmethod
     def train(cls, metric: DistanceMetric, nlist: int, M: int, train_vectors: np.ndarray, *, niter: int = 0, seed: int = 1,
               anneal_iters: int = 0, device: int = 0):
@@ -188,15 +165,13 @@ class PolysemousIvfPq(_HtSearch, FaissIvfPq):
     @classmethod
     def adopt(cls, index: FaissIvfPq):
         """Takes over the handle of a FaissIvfPq (one that faiss_files loaded, say); `index` is closed to its holder."""
-        out = cls(index._h, index.metric, index.d, index.nlist, index.M)
-        index._h = None
+        out = cls(None, index.metric, index.d, index.nlist, index.M)
+        out._take(index)
         return out
 
 
 class PolysemousOpqIvfPq(_HtSearch, FaissOpqIvfPq):
     """FaissOpqIvfPq with polysemous training of the inner index and the filtered search."""
-
-    _prefix = "opq"
 
     @classmethod
     def train(cls, metric: DistanceMetric, nlist: int, M: int, d_out: int, train_vectors: np.ndarray, *, niter: int = 0,
@@ -210,20 +185,22 @@ class PolysemousOpqIvfPq(_HtSearch, FaissOpqIvfPq):
 
     @classmethod
     def adopt(cls, index: FaissOpqIvfPq):
-        out = cls(index._h, index.metric, index.d_in, index.d_out, index.nlist, index.M)
-        index._h = None
+        out = cls(None, index.metric, index.d_in, index.d_out, index.nlist, index.M)
+        out._take(index)
         return out
+
+
+_TWINS = {FaissIvfPq.FAISS_KIND: PolysemousIvfPq, FaissOpqIvfPq.FAISS_KIND: PolysemousOpqIvfPq}
 
 
 def adopt(index):
     """The Polysemous* twin of a FaissIvfPq / FaissOpqIvfPq, over the same handle."""
     if isinstance(index, _HtSearch):
         return index
-    if isinstance(index, FaissOpqIvfPq):
-        return PolysemousOpqIvfPq.adopt(index)
-    if isinstance(index, FaissIvfPq):
-        return PolysemousIvfPq.adopt(index)
-    raise TypeError(f"{type(index).__name__} has no product-quantiser codes to filter by")
+    twin = _TWINS.get(getattr(index, "FAISS_KIND", None))
+    if twin is None:
+        raise TypeError(f"{type(index).__name__} has no product-quantiser codes to filter by")
+    return twin.adopt(index)
 
 
 _FACTORY = re.compile(r"(?:OPQ(\d+)(?:_(\d+))?,)?IVF(\d+),PQ(\d+)(?:x8)?(np)?")

@@ -18,6 +18,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from . import ivfpq_ann, opq_ann
 from .dense_ann import DistanceMetric
 from .ivf_ann import IvfError, _rows
@@ -51,45 +52,39 @@ class RefineError(IvfError):
     pass
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_refine_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._refine_ready = True
-    return lib
+_lib = _binding.binder(PROTOS, "refine", load_library)
+_check = _binding.checker(RefineError, "refine_ann", "refine_last_error")
+
+_WRAP = {ivfpq_ann.FaissIvfPq.FAISS_KIND: "refine_index_wrap_ivfpq", opq_ann.FaissOpqIvfPq.FAISS_KIND: "refine_index_wrap_opq"}
 
 
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise RefineError(f"refine_ann error {rc}: {lib.refine_last_error().decode()}")
-
-
-class FaissRefineFlat:
+class FaissRefineFlat(_binding.Handle):
     """`<base>,RFlat` in an id map, resident in HBM: wrap() a trained, empty FaissIvfPq or FaissOpqIvfPq, add() rows (they go
     to the base and, as fp16, to the store), search().  The handle owns the base; `base` stays usable for its exports."""
 
+    _destroy, _lib = "refine_index_destroy", staticmethod(_lib)
+
     def __init__(self, handle, base):
+        base._disown()  # the C handle owns the base: it is destroyed with the refined index
         self._h, self.base = handle, base
         self.metric = base.metric
-        self.d = base.d_in if isinstance(base, opq_ann.FaissOpqIvfPq) else base.d  # the dimension of rows and queries
+        self.d = getattr(base, base._row_dim)  # the dimension of rows and queries
         self.nlist, self.M = base.nlist, base.M
 
     @classmethod
     def wrap(cls, base, k_factor: int = 1):
         """Takes the base over (its own close() becomes a no-op); the base must hold no row yet."""
+        fn = _WRAP.get(getattr(base, "FAISS_KIND", None))
+        if fn is None:
+            raise TypeError(f"a refined index wraps a FaissIvfPq or a FaissOpqIvfPq, not {type(base).__name__}")
+        base._owning()  # a base that another index has wrapped or adopted is refused before the library sees it
         lib = _lib()
         h = C.c_void_p()
-        if isinstance(base, opq_ann.FaissOpqIvfPq):
-            _check(lib, lib.refine_index_wrap_opq(base._h, int(k_factor), C.byref(h)))
-        elif isinstance(base, ivfpq_ann.FaissIvfPq):
-            _check(lib, lib.refine_index_wrap_ivfpq(base._h, int(k_factor), C.byref(h)))
-        else:
-            raise TypeError(f"a refined index wraps a FaissIvfPq or a FaissOpqIvfPq, not {type(base).__name__}")
-        base.close = lambda: None  # the handle is destroyed with the refined index
+        _check(lib, getattr(lib, fn)(base._h, int(k_factor), C.byref(h)))
         return cls(h, base)
+
+    def _closed(self) -> None:
+        self.base._h = None  # it went with the refined index
 
     def _info(self):
         n, d, metric, kf, kind = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -118,12 +113,8 @@ class FaissRefineFlat:
         """add_with_ids.  ids on every call or on none (ids = positions in the order added)."""
         lib = _lib()
         v = _rows(vectors, self.d)
-        idp = None
-        if ids is not None:
-            idp = np.ascontiguousarray(ids, np.int64)
-            if idp.shape != (v.shape[0],):
-                raise ValueError("one id per vector")
-        _check(lib, lib.refine_index_add(self._h, v.shape[0], v.ctypes.data, idp.ctypes.data if idp is not None else None))
+        idp = _binding.ids_or_none(ids, v.shape[0])
+        _check(lib, lib.refine_index_add(self._h, v.shape[0], v.ctypes.data, _binding.ptr(idp)))
 
     def search(self, queries: np.ndarray, k: int, nprobe: int, k_factor: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(ids [nq, k], distances [nq, k], counts [nq]): the k nearest by true distance of the base's k * k_factor
@@ -131,9 +122,7 @@ class FaissRefineFlat:
         lib = _lib()
         q = _rows(queries, self.d)
         nq = q.shape[0]
-        dist = np.zeros((nq, k), np.float32)
-        ids = np.zeros((nq, k), np.int64)
-        cnt = np.zeros(nq, np.int32)
+        ids, dist, cnt = _binding.result_triple(nq, k)
         if k_factor is None:
             _check(lib, lib.refine_search(self._h, nq, q.ctypes.data, k, nprobe, dist.ctypes.data, ids.ctypes.data, cnt.ctypes.data))
         else:
@@ -170,18 +159,6 @@ class FaissRefineFlat:
     def bytes_per_row(self) -> int:
         """Device bytes per row: the base's and the stored halves (padding to 8 halves aside)."""
         return self.base.bytes_per_row() + 2 * self.d
-
-    def close(self) -> None:
-        if self._h:
-            _lib().refine_index_destroy(self._h)
-            self._h = None
-            self.base._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _SUFFIX = re.compile(r"(.*PQ\d+(?:x8)?),(?:RFlat|Refine\(Flat\))")

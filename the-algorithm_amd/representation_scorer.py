@@ -13,6 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .simclusters_ann import load_library
 
 
@@ -44,15 +45,7 @@ PROTOS = {
 }
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_rsx_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._rsx_ready = True
-    return lib
+_lib = _binding.binder(PROTOS, "rsx", load_library)
 
 
 def simclusters_embedding(pairs: Sequence[Tuple[int, float]]):
@@ -72,24 +65,19 @@ def pair_scores(algorithm: ScoringAlgorithm, a_offsets, a_ids, a_scores, b_offse
     n = len(ao) - 1
     out = np.zeros(n, np.float64)
     p = lambda x: x.ctypes.data_as(C.c_void_p)
-    rc = lib.rsx_pair_scores(device, int(algorithm), n, p(ao), p(ai), p(asx), p(bo), p(bi), p(bsx), 1 if validate else 0, p(out))
-    if rc != 0:
-        raise RuntimeError(f"representation_scorer error {rc}: {lib.rsx_last_error().decode()}")
+    _check(lib, lib.rsx_pair_scores(device, int(algorithm), n, p(ao), p(ai), p(asx), p(bo), p(bi), p(bsx), 1 if validate else 0, p(out)))
     return out
 
 
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise RuntimeError(f"representation_scorer error {rc}: {lib.rsx_last_error().decode()}")
+_check = _binding.checker(RuntimeError, "representation_scorer", "rsx_last_error")
+_p = _binding.ptr
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-class EmbeddingStore:
+class EmbeddingStore(_binding.Handle):
     """Device-resident `ReadableStore[SimClustersEmbeddingId, SimClustersEmbedding]` of one
     (embeddingType, modelVersion): `embeddings` maps an internal id to its (clusterId, score) pairs."""
+
+    _destroy, _lib = "rsx_store_destroy", staticmethod(_lib)
 
     def __init__(self, embeddings: Dict[int, Sequence[Tuple[int, float]]], *, device: int = 0):
         lib = _lib()
@@ -104,17 +92,6 @@ class EmbeddingStore:
         v = np.concatenate(sc) if sc else np.zeros(0, np.float64)
         self._h = C.c_void_p()
         _check(lib, lib.rsx_store_build(device, len(ids), _p(ids), _p(o), _p(c), _p(v), C.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _lib().rsx_store_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def multi_get(algorithm: ScoringAlgorithm, store_a: EmbeddingStore, store_b: EmbeddingStore, pairs: Sequence[Tuple[int, int]]) -> List[Optional[float]]:

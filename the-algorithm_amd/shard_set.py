@@ -13,10 +13,11 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
+from . import binding as _binding
 from .dense_ann import DistanceMetric
-from .ivf_ann import FaissIvfFlat, IvfError, _rows
-from .ivfpq_ann import FaissIvfPq
-from .opq_ann import FaissOpqIvfPq
+from .ivf_ann import KIND_IVF_FLAT, KIND_IVF_PQ, KIND_OPQ_IVF_PQ, FaissIvfFlat, IvfError, _rows  # noqa: F401
+from .ivfpq_ann import FaissIvfPq  # noqa: F401
+from .opq_ann import FaissOpqIvfPq  # noqa: F401
 from .simclusters_ann import load_library
 
 _P = C.POINTER
@@ -33,8 +34,6 @@ PROTOS = {
     "shardset_destroy": (C.c_int, [C.c_void_p]),
 }
 
-# FAISS_KIND_* of include/faiss_files.h
-KIND_IVF_FLAT, KIND_IVF_PQ, KIND_OPQ_IVF_PQ = 1, 2, 3
 
 
 class ShardSetError(IvfError):
@@ -45,41 +44,25 @@ class ShardSetError(IvfError):
         self.code, self.message = code, message
 
 
-def _lib():
-    lib = load_library()
-    if not getattr(lib, "_shard_set_ready", False):
-        for name, (res, args) in PROTOS.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._shard_set_ready = True
-    return lib
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise ShardSetError(rc, lib.shardset_last_error().decode())
+_lib = _binding.binder(PROTOS, "shard_set", load_library)
+_check = _binding.checker(ShardSetError, "shard_set", "shardset_last_error", with_code=True)
+_ptr = _binding.ptr
 
 
 def kind_of(index) -> int:
     """The FAISS_KIND_* of an index object of the three families."""
-    if isinstance(index, FaissOpqIvfPq):
-        return KIND_OPQ_IVF_PQ
-    if isinstance(index, FaissIvfPq):
-        return KIND_IVF_PQ
-    if isinstance(index, FaissIvfFlat):
-        return KIND_IVF_FLAT
-    raise TypeError(f"{type(index).__name__} is not one of FaissIvfFlat, FaissIvfPq, FaissOpqIvfPq")
+    kind = getattr(index, "FAISS_KIND", None)
+    if kind not in (KIND_IVF_FLAT, KIND_IVF_PQ, KIND_OPQ_IVF_PQ):
+        raise TypeError(f"{type(index).__name__} is not one of FaissIvfFlat, FaissIvfPq, FaissOpqIvfPq")
+    return kind
 
 
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-class ShardSet:
+class ShardSet(_binding.Handle):
     """shard_set.h: create(), set_members() with loaded indexes (newest first), search().  The set keeps a reference to
     every member object, so a member is not collected while it serves; closing a member is the caller's, after it has
     left the set."""
+
+    _destroy, _lib = "shardset_destroy", staticmethod(_lib)
 
     def __init__(self, handle, metric: DistanceMetric, dimension: int, device: int):
         self._h, self.metric, self.dimension, self.device = handle, DistanceMetric(metric), int(dimension), device
@@ -118,9 +101,7 @@ class ShardSet:
         lib = _lib()
         q = _rows(queries, self.dimension)
         nq = q.shape[0]
-        dist = np.zeros((nq, max(k, 0)), np.float32)
-        ids = np.zeros((nq, max(k, 0)), np.int64)
-        cnt = np.zeros(nq, np.int32)
+        ids, dist, cnt = _binding.result_triple(nq, k, clamp=True)
         _check(lib, lib.shardset_search(self._h, nq, _ptr(q), k, nprobe, int(ht), _ptr(dist), _ptr(ids), _ptr(cnt)))
         return ids, dist, cnt
 
@@ -141,21 +122,10 @@ class ShardSet:
         s_dist = np.ascontiguousarray(np.stack([np.asarray(r[1], np.float32) for r in shard_results]))
         s_cnt = np.ascontiguousarray(np.stack([np.asarray(r[2], np.int32) for r in shard_results]))
         n_shards, nq, k_in = s_ids.shape
-        ids = np.zeros((nq, max(k, 0)), np.int64)
-        dist = np.zeros((nq, max(k, 0)), np.float32)
-        cnt = np.zeros(nq, np.int32)
+        ids, dist, cnt = _binding.result_triple(nq, k, clamp=True)
         _check(lib, lib.shardset_compose(device, n_shards, nq, k_in, _ptr(s_ids), _ptr(s_dist), _ptr(s_cnt), k, _ptr(ids), _ptr(dist),
                                          _ptr(cnt)))
         return ids, dist, cnt
 
-    def close(self) -> None:
-        if self._h:
-            _lib().shardset_destroy(self._h)
-            self._h = None
-            self._members = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _closed(self) -> None:
+        self._members = []

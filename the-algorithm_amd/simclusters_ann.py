@@ -21,6 +21,8 @@ from typing import Callable, Dict, Iterable, List, Mapping, Optional, Sequence, 
 
 import numpy as np
 
+from . import binding as _binding
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SANN_LIB_PATH") or os.path.join(_HERE, "libsimclusters_amd.so")  # (override: A/B builds)
 
@@ -257,10 +259,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
             "python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback."
         )
     lib = C.CDLL(p)
-    for name, (res, args) in _PROTOS.items():
-        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
+    _binding.attach(lib, _PROTOS)  # AttributeError if the .so lacks a declared symbol
     if path is None:
         _lib = lib
     return lib
