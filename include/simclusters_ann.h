@@ -558,7 +558,9 @@ int sann_debug_normalise(int32_t device, int32_t alg, int32_t n, const double *d
                          double lognorm, double *out);
 
 /* Audit hook: values[64 * n_waves] -- every group of 64 is sorted descending in place by one wavefront with the unit
- * kernel's in-register bitonic network (quad permutes, row shifts, gfx950 row / half-wave swaps). */
+ * kernel's in-register bitonic network (quad permutes, row shifts, gfx950 row / half-wave swaps).
+ * n_waves < 0: values holds -n_waves groups of 64 128-bit keys, four uint32 each (lo.lo, lo.hi, hi.lo, hi.hi); every
+ * group is sorted descending by (hi, lo) by one wavefront with the merge kernel's 128-bit network. */
 int sann_debug_wave_sort(int32_t device, int32_t n_waves, uint32_t *values);
 /* Audit hook: the fp32 pre-filter score the fast unit kernel gives a single-cluster candidate (posting score s[i],
  * cluster weight w[i]) under `alg`, by the same device function; out_forced[i] = 1 where the exact score is +inf / NaN

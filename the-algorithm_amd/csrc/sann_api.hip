@@ -2103,14 +2103,16 @@ int sann_merge_shards_cut(int32_t device, void *hip_stream, int32_t n_shards, in
 } ABI_CATCH
 
 int sann_debug_wave_sort(int32_t device, int32_t n_waves, uint32_t *values) try {
-  if (n_waves < 0 || (n_waves > 0 && !values)) return fail(SANN_EINVAL, "bad arguments");
+  // n_waves < 0: -n_waves groups of 64 128-bit keys, four dwords each (INT32_MIN has no positive twin)
+  if (n_waves == INT32_MIN || (n_waves != 0 && !values)) return fail(SANN_EINVAL, "bad arguments");
   if (n_waves == 0) return SANN_OK;
+  const size_t bytes = n_waves < 0 ? (size_t)-n_waves * 64 * 16 : (size_t)n_waves * 64 * 4;
   HIP_TRY(hipSetDevice(device));
   DevBuf d;
-  HIP_TRY(d.alloc((size_t)n_waves * 64 * 4));
-  HIP_TRY(hipMemcpy(d.p, values, (size_t)n_waves * 64 * 4, hipMemcpyHostToDevice));
+  HIP_TRY(d.alloc(bytes));
+  HIP_TRY(hipMemcpy(d.p, values, bytes, hipMemcpyHostToDevice));
   HIP_TRY(launch_debug_wave_sort(n_waves, d.as<uint32_t>(), nullptr));
-  HIP_TRY(hipMemcpy(values, d.p, (size_t)n_waves * 64 * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(values, d.p, bytes, hipMemcpyDeviceToHost));
   return SANN_OK;
 } ABI_CATCH
 

@@ -1351,9 +1351,21 @@ __global__ void debug_wave_sort_kernel(uint32_t *v) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   v[i] = wave_sort_desc_u32(v[i]);
 }
+// ... or, four dwords per key (lo.lo, lo.hi, hi.lo, hi.hi), with the merge kernel's wave_sort_desc_k128
+__global__ void debug_wave_sort_k128_kernel(uint4 *v) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const uint4 x = v[i];
+  uint64_t hi = ((uint64_t)x.w << 32) | x.z, lo = ((uint64_t)x.y << 32) | x.x;
+  wave_sort_desc_k128(hi, lo);
+  v[i] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+// n_waves < 0: -n_waves groups of 64 128-bit keys
 hipError_t launch_debug_wave_sort(int n_waves, uint32_t *v, hipStream_t stream) {
-  if (n_waves <= 0) return hipSuccess;
-  hipLaunchKernelGGL(debug_wave_sort_kernel, dim3(n_waves), dim3(64), 0, stream, v);
+  if (n_waves == 0) return hipSuccess;
+  if (n_waves < 0)
+    hipLaunchKernelGGL(debug_wave_sort_k128_kernel, dim3(-n_waves), dim3(64), 0, stream, (uint4 *)v);
+  else
+    hipLaunchKernelGGL(debug_wave_sort_kernel, dim3(n_waves), dim3(64), 0, stream, v);
   return hipGetLastError();
 }
 

@@ -509,9 +509,10 @@ __device__ inline int rank_among_runs(const ulonglong2 *runs, int R, int r, int 
 // staged entry, the WG = 256 samples are sorted (four in-register wave sorts + a rank merge: two barriers), and the
 // sample at the position the window's middle is expected at is tried -- one counting sweep per try, the next try moved
 // by the miss.  Returns false (after at most 6 tries, or when two neighbouring samples bracket the window) and leaves
-// the decision to lds_radix_cut; needs n >= WG.  s_tmp: WG entries, s_ctl: 4 ints.
+// the decision to lds_radix_cut; needs n >= WG.  s_tmp: WG entries, s_ctl: 4 ints.  On success my_count is the number of
+// entries i = tid, tid + WG, ... with key >= the threshold: the sweep that accepted it has just counted them.
 __device__ bool sample_cut(const uint64_t *hi, const uint64_t *lo, int n, int need, int budget, ulonglong2 *s_tmp, int *s_ctl,
-                           uint64_t &thr_hi, uint64_t &thr_lo) {
+                           uint64_t &thr_hi, uint64_t &thr_lo, int &my_count) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   // A window that is wide against n (a shard's merge: need = its cut list length, budget = 256 of ~380 staged) is hit
   // from 64 samples, which one wave sorts on its own: no rank merge, and the other waves go straight to the sweep.
@@ -551,6 +552,7 @@ __device__ bool sample_cut(const uint64_t *hi, const uint64_t *lo, int n, int ne
     if (C >= need && C <= budget) {
       thr_hi = t.x;
       thr_lo = t.y;
+      my_count = c;
       return true;
     }
     if (C < need) j_small = j; else j_big = j;
@@ -642,10 +644,15 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
   __shared__ uint8_t s_umap[MERGE_LDS];  // new entry -> unit (relative to the round's first unit; P <= 256)
   __shared__ ulonglong2 s_e2[SURV];  // survivors, packed {score key, id key}
   __shared__ uint64_t s_mm[2];
-  __shared__ unsigned s_hist[256];
   __shared__ int s_off[WG + 1];
-  __shared__ int s_fb[WG];
+  // where unit u's list lies, as ONE word: 2 * (index of the list's first element in its array - s_off[u]) + (1 = the general
+  // path's arrays cand_*2, 0 = cand_*).  A staged entry's address is then this word plus its flat index: no multiply per entry.
+  __shared__ int64_t s_list[WG];
   __shared__ int s_ctl[4];
+  // the radix cut's histogram (256 counters) lives in the survivor list's storage: s_e2 is free while a cut is sought
+  // (its entries were copied into the staging area; sample_cut borrows it the same way, and ends on a barrier)
+  unsigned *const s_hist = reinterpret_cast<unsigned *>(s_e2);
+  static_assert(SURV * sizeof(ulonglong2) >= 256 * sizeof(unsigned), "the histogram must fit the survivor list");
 
   const int tid = threadIdx.x;
   const int q = query_list ? query_list[blockIdx.x] : blockIdx.x;
@@ -662,19 +669,14 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
   // offsets of the unit lists in a flat index space (P <= 256: one thread per unit, wave scans)
   {
     int c = tid < P ? b.cand_cnt[unit0 + tid] : 0;
-    s_fb[tid] = tid < P ? b.unit_fb[unit0 + tid] : -1;
-    int incl = c;
-    const int lane = tid & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      int t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_ctl[tid >> 6] = incl;  // wave totals (WG/64 = 4 waves)
+    const int fb = tid < P ? b.unit_fb[unit0 + tid] : -1;
+    const int incl = wave_incl_scan_i32(c);  // (on the VALU: six DPP adds, no trip through the LDS crossbar)
+    if ((tid & 63) == 63) s_ctl[tid >> 6] = incl;  // wave totals (WG/64 = 4 waves)
     __syncthreads();
     int wbase = 0;
     for (int w = 0; w < (tid >> 6); w++) wbase += s_ctl[w];
     s_off[tid] = wbase + incl - c;
+    s_list[tid] = fb < 0 ? 2 * ((unit0 + tid) * b.cap - (wbase + incl - c)) : 2 * ((int64_t)fb * b.cap2 - (wbase + incl - c)) + 1;
     if (tid == WG - 1) s_off[WG] = wbase + incl;
     __syncthreads();
   }
@@ -716,13 +718,11 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
         kh[r] = CAND_DROPPED;
         kid[r] = 0;
         if (i < n_new && i < MERGE_LDS) {
-          const int u = u_begin + s_umap[i];
-          const int fb = s_fb[u];
-          const int j = base_off + i - s_off[u];
-          const uint64_t *key = fb < 0 ? b.cand_key + (unit0 + u) * b.cap : b.cand_key2 + (int64_t)fb * b.cap2;
-          const int64_t *id = fb < 0 ? b.cand_id + (unit0 + u) * b.cap : b.cand_id2 + (int64_t)fb * b.cap2;
-          kh[r] = key[j];
-          kid[r] = id[j];
+          const int64_t w = s_list[u_begin + s_umap[i]];
+          const bool general = (w & 1) != 0;
+          const int64_t j = (w >> 1) + (base_off + i);  // the entry's index in its array
+          kh[r] = (general ? b.cand_key2 : b.cand_key)[j];
+          kid[r] = (general ? b.cand_id2 : b.cand_id)[j];
         }
       }
       // Entries a fast unit handed over as (cluster, posting position) are fetched and scored here (score_deferred), RC of
@@ -748,16 +748,19 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
     __syncthreads();
     MSTAMP(2);  // staged (last round)
     uint64_t thi = 0, tlo = 0;
+    int c = 0;
+    bool counted = false;  // (uniform) c already holds this thread's survivors
     if (n > budget && k > 0) {
       // (s_e2 is free here: the previous round's survivors were copied into the staging area above)
-      if (!sample_cut(s_hi, s_lo, n, k, budget, s_e2, s_ctl, thi, tlo))
-        lds_radix_cut(s_hi, s_lo, n, k, budget, s_hist, s_ctl, s_mm, thi, tlo);
+      // A sample that is accepted leaves fewer than n entries at or above it, so it is no dropped entry's all-zero key, and
+      // no dropped entry is at or above it: the accepting sweep's count is the survivor count below.
+      counted = sample_cut(s_hi, s_lo, n, k, budget, s_e2, s_ctl, thi, tlo, c);
+      if (!counted) lds_radix_cut(s_hi, s_lo, n, k, budget, s_hist, s_ctl, s_mm, thi, tlo);
     }
     MSTAMP(3);  // cut found (last round)
     // survivors into s_e2: per-thread counts, a DPP prefix sum per wave, wave bases through LDS -- no atomics
     {
-      int c = 0;
-      if (k > 0)
+      if (k > 0 && !counted)
         for (int i = tid; i < n; i += WG) c += (s_hi[i] != 0ull && key_ge(s_hi[i], s_lo[i], thi, tlo)) ? 1 : 0;
       const int incl = wave_incl_scan_i32(c);
       if ((tid & 63) == 63) s_ctl[tid >> 6] = incl;
@@ -802,7 +805,9 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
   {
     int np = next_pow2(best_n);
     np = np < 64 ? 64 : np;
-    for (int i = best_n + tid; i < np; i += WG) s_e2[i] = make_ulonglong2(0ull, 0ull);
+    // padding: score key 0 lies below every real entry's, and the position makes the paddings pairwise distinct -- real
+    // keys are unique, so no two entries of s_e2 are equal and the merge rounds below need no tie rule
+    for (int i = best_n + tid; i < np; i += WG) s_e2[i] = make_ulonglong2(0ull, (uint64_t)(np - 1 - i));
     if (tid == 0) { s_mm[0] = 0ull; s_mm[1] = 0ull; }
     __syncthreads();
     const int R = np >> 6, lane = tid & 63, wv = tid >> 6;
@@ -830,12 +835,10 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
       // the other (the chains are all this phase waits for)
       const ulonglong2 *run[PER];
       int pos[PER];
-      bool second[PER];
 #pragma unroll
       for (int j = 0; j < PER; j++) {
         const int base = at[j] & ~(2 * L - 1);
-        second[j] = (at[j] & L) != 0;  // in the pair's second run: equal keys of the first run come before
-        run[j] = s_e2 + base + (second[j] ? 0 : L);
+        run[j] = s_e2 + base + ((at[j] & L) != 0 ? 0 : L);  // the other run of the pair
         pos[j] = 0;
       }
       for (int step = L >> 1; step >= 1; step >>= 1) {
@@ -844,14 +847,13 @@ __global__ __launch_bounds__(WG, 4) void merge_kernel(IndexView ix, BatchView b,
         for (int j = 0; j < PER; j++) v[j] = run[j][pos[j] + step - 1];
 #pragma unroll
         for (int j = 0; j < PER; j++) {
-          const bool before = v[j].x > mh[j] || (v[j].x == mh[j] && (v[j].y > ml[j] || (v[j].y == ml[j] && second[j])));
-          pos[j] += before ? step : 0;
+          pos[j] += key_gt(v[j].x, v[j].y, mh[j], ml[j]) ? step : 0;
         }
       }
 #pragma unroll
       for (int j = 0; j < PER; j++) {
         const ulonglong2 v = run[j][L - 1];
-        const bool before = v.x > mh[j] || (v.x == mh[j] && (v.y > ml[j] || (v.y == ml[j] && second[j])));
+        const bool before = key_gt(v.x, v.y, mh[j], ml[j]);
         const int cntb = pos[j] + ((pos[j] == L - 1 && before) ? 1 : 0);
         if (wv + j * (WG / 64) < R) at[j] = (at[j] & ~(2 * L - 1)) + (at[j] & (L - 1)) + cntb;
       }

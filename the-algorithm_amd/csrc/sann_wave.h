@@ -83,25 +83,61 @@ __device__ inline uint32_t wave_sort_desc_u32(uint32_t v) {
 
 
 // ---- 128-bit keys (hi, lo), one per lane: the merge kernel's (score key, id key) ---------------------------------------
-template <int J>
-__device__ inline uint64_t lane_xor_u64(uint64_t v) {
-  const uint32_t a = lane_xor<J>((uint32_t)v), b = lane_xor<J>((uint32_t)(v >> 32));
-  return ((uint64_t)b << 32) | a;
+// The network is paced by vector issue (profiles/NOTES.md, round 13), so a step spends vector instructions on three things
+// only: fetching the partner's four dwords, ONE 128-bit compare, and four selects.
+//   * which lanes keep the larger key is a compile-time pattern of (K, J): a 64-bit literal XOR-ed into the compare's lane
+//     mask on the scalar side -- no lane arithmetic, no mask held in (or spilled from) SGPRs;
+//   * `take = (other > mine) == keep_max` needs no second compare: the two lanes of a pair decide from the same two keys,
+//     and on equal keys either choice exchanges identical bits;
+//   * J = 1, 2, 8 are one DPP move per dword (quad permutes, row_ror:8 = l ^ 8 within a row of 16); J = 4 is two moves into
+//     one register under complementary bank masks; J = 16, 32 swap two copies of the key, after which the pair
+//     (r0, r1) IS (mine, other) in the even rows / the low half and (other, mine) in the others -- `r1 > r0` is then
+//     "other > mine" there and its negation here, and the select `sel ? r1 : r0` with sel = (r1 > r0) ^ ~keep_max serves both.
+template <int K, int J>
+constexpr uint64_t bitonic_keep_max_lanes() {
+  uint64_t m = 0;
+  for (int l = 0; l < 64; l++)
+    if (((l & K) == 0) == ((l & J) == 0)) m |= 1ull << l;
+  return m;
+}
+// lanes where a > b over four dwords, [3] the most significant: three 64-bit compares whose lane masks meet on the scalar side
+__device__ inline uint64_t k128_gt_lanes(const uint32_t (&a)[4], const uint32_t (&b)[4]) {
+  const uint64_t ah = ((uint64_t)a[3] << 32) | a[2], al = ((uint64_t)a[1] << 32) | a[0];
+  const uint64_t bh = ((uint64_t)b[3] << 32) | b[2], bl = ((uint64_t)b[1] << 32) | b[0];
+  return __builtin_amdgcn_ballot_w64(ah > bh) | (__builtin_amdgcn_ballot_w64(ah == bh) & __builtin_amdgcn_ballot_w64(al > bl));
 }
 template <int K, int J>
-__device__ inline void bitonic_step_k128(uint64_t &hi, uint64_t &lo) {
-  const int lane = SANN_WAVE_LANE();
-  const uint64_t ohi = lane_xor_u64<J>(hi), olo = lane_xor_u64<J>(lo);
-  const bool keep_max = ((lane & K) == 0) == ((lane & J) == 0);
-  const bool o_gt = ohi > hi || (ohi == hi && olo > lo);
-  const bool o_lt = ohi < hi || (ohi == hi && olo < lo);
-  const bool take = keep_max ? o_gt : o_lt;
-  hi = take ? ohi : hi;
-  lo = take ? olo : lo;
+__device__ inline void bitonic_step_k128(uint32_t (&m)[4]) {
+  constexpr uint64_t FLIP = ~bitonic_keep_max_lanes<K, J>();
+  uint32_t a[4], o[4];  // the select's "else" and "then" operands
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if constexpr (J == 1) {
+      a[i] = m[i]; o[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)m[i], 0xB1, 0xf, 0xf, true);  // quad_perm [1,0,3,2]
+    } else if constexpr (J == 2) {
+      a[i] = m[i]; o[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)m[i], 0x4E, 0xf, 0xf, true);  // quad_perm [2,3,0,1]
+    } else if constexpr (J == 4) {
+      // row_shl:4 (lane l reads l + 4) into banks 0, 2; row_shr:4 (l - 4) into banks 1, 3: every lane is written once
+      const int up = __builtin_amdgcn_mov_dpp((int)m[i], 0x104, 0xf, 0x5, false);
+      a[i] = m[i]; o[i] = (uint32_t)__builtin_amdgcn_update_dpp(up, (int)m[i], 0x114, 0xf, 0xa, false);
+    } else if constexpr (J == 8) {
+      a[i] = m[i]; o[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)m[i], 0x128, 0xf, 0xf, true);  // row_ror:8
+    } else if constexpr (J == 16) {
+      const auto r = __builtin_amdgcn_permlane16_swap(m[i], m[i], false, false);  // r[0] = rows (0,0,2,2), r[1] = rows (1,1,3,3)
+      a[i] = r[0]; o[i] = r[1];
+    } else {
+      const auto r = __builtin_amdgcn_permlane32_swap(m[i], m[i], false, false);  // r[0] = halves (lo,lo), r[1] = (hi,hi)
+      a[i] = r[0]; o[i] = r[1];
+    }
+  }
+  const bool sel = __builtin_amdgcn_inverse_ballot_w64(k128_gt_lanes(o, a) ^ FLIP);
+#pragma unroll
+  for (int i = 0; i < 4; i++) m[i] = sel ? o[i] : a[i];
 }
 // bitonic sort of one 128-bit key per lane, descending: lane i ends up with the wave's i-th largest
 __device__ inline void wave_sort_desc_k128(uint64_t &hi, uint64_t &lo) {
-#define S_(K, J) bitonic_step_k128<K, J>(hi, lo)
+  uint32_t m[4] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+#define S_(K, J) bitonic_step_k128<K, J>(m)
   S_(2, 1);
   S_(4, 2); S_(4, 1);
   S_(8, 4); S_(8, 2); S_(8, 1);
@@ -109,6 +145,8 @@ __device__ inline void wave_sort_desc_k128(uint64_t &hi, uint64_t &lo) {
   S_(32, 16); S_(32, 8); S_(32, 4); S_(32, 2); S_(32, 1);
   S_(64, 32); S_(64, 16); S_(64, 8); S_(64, 4); S_(64, 2); S_(64, 1);
 #undef S_
+  lo = ((uint64_t)m[1] << 32) | m[0];
+  hi = ((uint64_t)m[3] << 32) | m[2];
 }
 
 }  // namespace sann

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static issue budget of one unit_fast_kernel instantiation: instructions per region of its gfx950 listing.
+"""Static issue budget of one kernel instantiation (by default unit_fast_kernel): instructions per region of its gfx950 listing.
 
 The unit kernel is paced by instruction issue (profiles/NOTES.md, round 12), so what a change saves can be read off the
 compiler's listing before anything runs.  This tool compiles csrc/sann_fast.hip to a device listing with the Makefile's
@@ -15,8 +15,14 @@ order (the listing's order: a region may hold code of branches a unit does not t
 
 It classifies by mnemonic prefix and those few names only.  It is a report, not a gate.
 
-usage: unit_kernel_issue_budget.py [--args 128,12,64,0,false,true] [--listing FILE.s] [--keep FILE.s]
-       unit_kernel_issue_budget.py [--args ...] --compare OLD.s NEW.s
+Other kernels of the step are read the same way: --kernel NAME picks the function template, --source FILE.hip the file of
+csrc/ that is compiled, e.g.
+  --source sann_kernels.hip --kernel merge_kernel --args 512,1728
+  --source sann_kernels.hip --kernel merge_wave_kernel --args 4,8
+  --kernel desc_query_kernel --args 1                          (the descriptor kernel lives in sann_fast.hip)
+
+usage: unit_kernel_issue_budget.py [--kernel NAME] [--source FILE.hip] [--args 128,12,64,0,false,true] [--listing FILE.s] [--keep FILE.s]
+       unit_kernel_issue_budget.py [--kernel NAME] [--args ...] --compare OLD.s NEW.s
 """
 import argparse
 import os
@@ -30,6 +36,8 @@ CSRC = os.path.join(ROOT, "the-algorithm_amd", "csrc")
 COLUMNS = ("vector", "mul", "cmp64", "scalar", "lds", "global")
 MULS = ("v_mul_lo_u32", "v_mul_hi_u32", "v_mad_u64_u32")
 DEFAULT_ARGS = "128,12,64,0,false,true"
+DEFAULT_KERNEL = "unit_fast_kernel"
+DEFAULT_SOURCE = "sann_fast.hip"
 
 
 def mangled_args(args):
@@ -61,7 +69,7 @@ def classify(mnemonic):
     return []
 
 
-def parse_listing(text, kernel="unit_fast_kernel", args=DEFAULT_ARGS):
+def parse_listing(text, kernel=DEFAULT_KERNEL, args=DEFAULT_ARGS):
     """-> [ {column: count} per region ], regions split at s_barrier, of the function whose symbol holds the kernel's name
     followed by the mangled template arguments.  Raises LookupError if the listing has no such function."""
     want = kernel + mangled_args(args)
@@ -103,9 +111,9 @@ def makefile_flags():
     return flags.replace("$(ARCH)", arch).split()
 
 
-def compile_listing(out_path):
+def compile_listing(out_path, source=DEFAULT_SOURCE):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc] + makefile_flags() + ["-S", "--cuda-device-only", "-w", "-o", out_path, "sann_fast.hip"], check=True, cwd=CSRC)
+    subprocess.run([hipcc] + makefile_flags() + ["-S", "--cuda-device-only", "-w", "-o", out_path, source], check=True, cwd=CSRC)
 
 
 def table(regions):
@@ -126,15 +134,17 @@ def show(rows):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--args", default=DEFAULT_ARGS, help="template arguments of the instantiation: WG,U,NS,ABL,NORMS,IDF[,...]")
-    ap.add_argument("--listing", help="read this listing instead of compiling csrc/sann_fast.hip")
+    ap.add_argument("--kernel", default=DEFAULT_KERNEL, metavar="NAME", help="the kernel template's name (default %(default)s)")
+    ap.add_argument("--source", default=DEFAULT_SOURCE, metavar="FILE.hip", help="the file of csrc/ to compile (default %(default)s)")
+    ap.add_argument("--listing", help="read this listing instead of compiling the source file")
     ap.add_argument("--keep", help="compile and keep the listing here")
     ap.add_argument("--compare", nargs=2, metavar=("OLD.s", "NEW.s"))
     ap.add_argument("--new-args", help="with --compare: the instantiation's arguments in NEW.s, where they differ")
     a = ap.parse_args()
     if a.compare:
-        old = parse_listing(open(a.compare[0]).read(), args=a.args)
-        new = parse_listing(open(a.compare[1]).read(), args=a.new_args or a.args)
-        print("unit_fast_kernel<%s> -> <%s>: old / new per region (regions are split at s_barrier, in program order)" % (a.args, a.new_args or a.args))
+        old = parse_listing(open(a.compare[0]).read(), kernel=a.kernel, args=a.args)
+        new = parse_listing(open(a.compare[1]).read(), kernel=a.kernel, args=a.new_args or a.args)
+        print(a.kernel + "<%s> -> <%s>: old / new per region (regions are split at s_barrier, in program order)" % (a.args, a.new_args or a.args))
         rows = [("region",) + COLUMNS]
         empty = dict.fromkeys(COLUMNS, 0)
         for i in range(max(len(old), len(new))):
@@ -148,11 +158,11 @@ def main():
     if a.listing:
         text = open(a.listing).read()
     else:
-        path = a.keep or os.path.join(tempfile.mkdtemp(), "sann_fast.s")
-        compile_listing(path)
+        path = a.keep or os.path.join(tempfile.mkdtemp(), os.path.splitext(os.path.basename(a.source))[0] + ".s")
+        compile_listing(path, a.source)
         text = open(path).read()
-    print("unit_fast_kernel<%s>: instructions per region (regions are split at s_barrier, in program order)" % a.args)
-    show(table(parse_listing(text, args=a.args)))
+    print(a.kernel + "<%s>: instructions per region (regions are split at s_barrier, in program order)" % a.args)
+    show(table(parse_listing(text, kernel=a.kernel, args=a.args)))
     return 0
 
 
