@@ -15,7 +15,9 @@
 //               dependent memory trips -- at eight workgroups per CU (<= 64 VGPRs, 20 KB LDS, <= 80 SGPRs); the id form
 //               at 1536 postings runs as TWO-wave units, fourteen per CU (60 VGPRs, 11.3 KB LDS: see two_wave_unit):
 //   1. descriptors  header, (start, prefix) row, cluster weights and posting count in ONE trip; byte map flat posting
-//                   index -> cluster; per-cluster constants (fp64 weight, fp32 weight, and for the cosine forms the fp32
+//                   index -> cluster (two-wave units: one END BIT per non-empty cluster's stretch -- a posting's cluster is
+//                   then a count of the bits below it, its rank among the non-empty clusters -- and tables by rank);
+//                   per-cluster constants (fp64 weight, fp32 weight, and for the cosine forms the fp32
 //                   KEY of a single-cluster candidate: (s w) / sqrt(s s) = w, so such a candidate needs no arithmetic)
 //   2. gather       one 16-B global load per posting, consecutive lanes = consecutive postings of a sub-list; all of a
 //                   thread's loads are issued (inline asm: hipcc otherwise waits after each) before the single wait;
@@ -242,11 +244,25 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
   };
   constexpr int MCAP = (WG * U <= 1024) ? 64 : 128;
   constexpr int SHORT_NM = 12;  // match lists up to here are settled by every wave for itself; the sorted path starts above
-  __shared__ unsigned long long s_bloom[BLOOM_ALLOC];
+  // (LDS_HOLD: words behind the filter that nothing touches.  Without the byte map a two-wave unit of the 64-cluster stride
+  // needs 10.2 KB, and sixteen of them would fit a CU where fourteen run today (128 clusters: 11.3 KB, fourteen where
+  // thirteen run); whether more units per CU pay is a measurement of its own, so until then the allocation stays between
+  // a fifteenth and a fourteenth of the CU's 160 KB (between a fourteenth and a thirteenth).)
+  constexpr int LDS_HOLD = !B8K ? 0 : NS == 64 ? 128 : 48;
+  __shared__ unsigned long long s_bloom[BLOOM_ALLOC + LDS_HOLD];
   // posting j of the unit (flat index) lies at s_off[cluster of j] + j: the sub-list's start in the index MINUS the
   // postings of the unit in front of it (mod 2^32).  The two are only ever used as this difference.
-  __shared__ uint32_t s_off[NS];
-  __shared__ uint8_t s_map[WG * U];  // flat posting index -> cluster sequence number
+  // (two-wave units: s_off, s_w and s_wkey are indexed by the cluster's RANK among the unit's non-empty clusters, see 1.)
+  __shared__ uint32_t s_off[NS + (B8K ? 1 : 0)];
+  __shared__ uint8_t s_map[B8K ? 1 : WG * U];  // flat posting index -> cluster sequence number
+  // two-wave units, in place of the byte map: bit e is set when a non-empty cluster's stretch ENDS at flat index e.  The
+  // clusters of consecutive postings never decrease, so the end bits below a posting count the non-empty clusters in front
+  // of its own: its cluster's rank.  A wave's 64 lanes of one slot are one word.  s_cl[rank] = cluster sequence number.
+  // Word w is the pair s_end[2w], s_end[2w + 1]: the bits, and (number of ranks << 32) | end bits of the words in front
+  // of w -- one 16-byte read hands a slot all it needs.
+  constexpr int END_WORDS = WG * U / 64;
+  __shared__ __attribute__((aligned(16))) unsigned long long s_end[B8K ? 2 * END_WORDS : 2];
+  __shared__ uint8_t s_cl[B8K ? NS : 1];
   __shared__ double s_w[NS];
   __shared__ float s_w32[B8K ? 1 : NS];  // (fp32 weights: the keys of the other forms; the id form reads none)
   __shared__ uint32_t s_wkey[NS];  // cosine forms: the fp32 key of a single-cluster candidate of the cluster (0 = untrusted)
@@ -289,8 +305,22 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
 
   // ---- 0. clear ----------------------------------------------------------------------------
   if (tid < CTL_N) s_ctl[tid] = (tid == CTL_KMIN) ? -1 : 0;
+  if constexpr (B8K) {
+    // (a whole number of words per thread, said so: as the loop below hipcc compared tid with a bound in front of every
+    // store -- seven compares and branches per wave that never skip anything)
+    static_assert(BLOOM_ALLOC % WG == 0 && FBLOOM_WORDS <= WG);
+#pragma unroll
+    for (int i = 0; i < BLOOM_ALLOC / WG; i++) s_bloom[i * WG + tid] = 0ull;
+    if (tid < FBLOOM_WORDS) s_fbloom[tid] = 0ull;
+  } else {
   for (int i = tid; i < BLOOM_ALLOC; i += WG) s_bloom[i] = 0ull;
   for (int i = tid; i < FBLOOM_WORDS; i += WG) s_fbloom[i] = 0ull;
+  }
+  // (the end bits are cleared by wave 0, which also sets them: a wave's own LDS accesses keep their order)
+  if constexpr (B8K) {
+    static_assert(END_WORDS <= 64, "wave 0 clears the end-bit words, one lane each");
+    if (tid < END_WORDS) s_end[2 * tid] = 0ull;
+  }
 
   const bool overflow_n = h.n_scan > NS;  // uniform
   // ---- 1. descriptors ----------------------------------------------------------------------
@@ -305,6 +335,67 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
   {
     const uint2 *d = reinterpret_cast<const uint2 *>(b.desc) + (int64_t)unit * NS;
     const double *wq = b.scan_wq + (int64_t)q * NS;
+    if constexpr (B8K) {
+      // Two-wave units: ONE lane per cluster, all of them in wave 0 (lane c, and c + 64 at the 128-cluster stride), and no
+      // loop.  A cluster is non-empty when the next prefix lies above its own (a padding entry (0, T) never is); its rank
+      // r is the number of non-empty clusters in front of it, a ballot and a count of the bits below the lane.  The
+      // unit's tables are written at r -- rank order is cluster order, so whatever compares or sorts sequence numbers
+      // inside the unit keeps its meaning, and the cluster itself (s_cl[r]) is looked up at the hand-over only.  The
+      // cluster's end bit is one non-returning LDS OR; an oversized unit gathers nothing and sets no bit past the words.
+      // s_off has a spare entry behind the last rank, a copy of it: a slot past the unit's end counts every end bit and
+      // must still load from inside the column (it re-reads the unit's last posting, as it always did).
+      if (tid < 64) {
+        // (the words' clear above, by this wave's lanes, before this wave's ORs below)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        constexpr int R = NS / 64;
+        uint2 v[R];
+        uint32_t nxt[R];
+        double w[R];
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+          const int c = tid + 64 * i;
+          v[i] = d[c];
+          nxt[i] = d[i + 1 < R ? c + 1 : (c + 1 < NS ? c + 1 : c)].y;  // (the row's last lane takes T below)
+          w[i] = wq[c];
+        }
+        uint32_t next[R], rank[R];
+        bool nonempty[R];
+        uint32_t in_front = 0u;
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+          asm volatile("" : "+v"(nxt[i]));  // keeps the select on Tv below the loads above
+          next[i] = (i + 1 == R && tid == 63) ? Tv : nxt[i];
+          nonempty[i] = next[i] > v[i].y;
+          const unsigned long long m = __builtin_amdgcn_ballot_w64(nonempty[i]);
+          rank[i] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, in_front));
+          in_front += (uint32_t)__popcll(m);
+        }
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+          if (nonempty[i]) {
+            const uint32_t r = rank[i], e = next[i] - 1u;
+            s_off[r] = v[i].x - v[i].y;
+            if (r + 1u == in_front) s_off[in_front] = v[i].x - v[i].y;  // (the last rank's lane alone)
+            s_cl[r] = (uint8_t)(tid + 64 * i);
+            s_w[r] = w[i];
+            s_wkey[r] = cosine_cluster_key(h.alg, w[i], inv_l2_32);
+            if (e < (uint32_t)(WG * U)) atomicOr(&s_end[2 * (e >> 6)], 1ull << (e & 63u));
+          }
+        }
+        // ... and counts them, for both waves: lane l takes word l, and a scan leaves the end bits of the words in front
+        // of it (behind the wave's own ORs: no barrier; the workgroup's barrier below publishes the pairs)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int pc = tid < END_WORDS ? __popcll(s_end[2 * (tid < END_WORDS ? tid : 0)]) : 0;
+        const int incl = wave_incl_scan_i32(pc);
+        // (bit 31: the word lies wholly past the unit's end -- see the gather)
+        const uint32_t past = (uint32_t)(64 * tid) >= Tv ? 0x80000000u : 0u;
+        if (tid < END_WORDS) s_end[2 * tid + 1] = ((unsigned long long)in_front << 32) | (past | (uint32_t)(incl - pc));
+      }
+    } else {
     // four lanes per cluster: lane part (0..3) fills a quarter of the cluster's stretch of the map
 #pragma unroll
     for (int t0 = 0; t0 < 4 * NS; t0 += WG) {
@@ -327,6 +418,7 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
       uint32_t next = last ? Tv : nxt;
       next = next < (uint32_t)(WG * U) ? next : (uint32_t)(WG * U);
       for (uint32_t i = v.y + part; i < next; i += 4) s_map[i] = (uint8_t)c;
+    }
     }
   }
   if (overflow_n) Tv = 0u;
@@ -359,7 +451,7 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
   // in scratch memory, re-reading them in every later phase.
   float nrm32[NORMS ? U : 1];  // offline forms: the tweet's full norm, fp32
   float s32[IDF ? 1 : U];  // posting score, fp32 (the id form has none)
-  int seq[U];     // cluster sequence number; bit 16 = group representative (low bits: match-list entry); < 0 = no candidate here
+  int seq[U];     // cluster sequence number (two-wave units: the cluster's rank, see 1.); bit 16 = group representative (low bits: match-list entry); < 0 = no candidate here
   int live = 0;
   uint32_t hsh[U];  // table_hash of the tweet id (Bloom word and bits): lives until the duplicate phase has looked at it
 #pragma unroll
@@ -379,6 +471,7 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     std::conditional_t<IDF, u32x2, u32x4> raw[U];
+    [[maybe_unused]] uint32_t n_ranks = 0u;  // two-wave units: the unit's non-empty clusters (uniform)
     // Every slot loads, unconditionally (a slot the unit does not reach re-reads the unit's last posting: one cache
     // line for the whole wave): the asm outputs then have no other definition they would have to be merged with --
     // a merge is a register copy placed right behind the load, i.e. a read of registers the load has not written yet.
@@ -386,9 +479,24 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const uint32_t j = (uint32_t)(u * WG + tid);
-        const uint32_t jj = j < Tg ? j : Tg - 1;
-        const int c = (int)s_map[jj];
-        seq[u] = (j < Tg) ? c : -1;
+        const uint32_t jj = B8K ? (j < Tg - 1 ? j : Tg - 1) : (j < Tg ? j : Tg - 1);  // (the former: one v_min, no compare to share)
+        int c;
+        if constexpr (B8K) {
+          // A wave's 64 lanes of slot u are the 64 bits of end word 2u + wave: one 16-byte LDS read at a wave-uniform
+          // address, and the rank is the count in front of the word plus the bits below the lane (v_mbcnt).  A posting
+          // past the unit's end has every end bit below it: its rank is the number of ranks -- the spare entry of s_off,
+          // and the filters' sign of a slot without a posting (no compare with T, no select here).  A word wholly past
+          // the unit's end carries bit 31 in its count: the filters below skip such slots, so the rank itself must say
+          // "no candidate" (negative); the table index drops the bit (two bits leave with the shift to a byte address).
+          const int w = 2 * (2 * u + (tid >> 6));
+          const unsigned long long ends = s_end[w], info = s_end[w + 1];
+          seq[u] = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ends >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends, (uint32_t)info));
+          if (u == 0) n_ranks = (uint32_t)__builtin_amdgcn_readfirstlane((int)(info >> 32));
+          c = (int)((uint32_t)seq[u] & 0x3fffffffu);
+        } else {
+          c = (int)s_map[jj];
+          seq[u] = (j < Tg) ? c : -1;
+        }
         if constexpr (NARROW) {
           // (the launcher's promise: 8 * n_postings < 2^32; the column's base is uniform and stays in scalar registers)
           const uint32_t off = (s_off[c] + jj) << 3;
@@ -437,7 +545,8 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
             const long long idv = (long long)(((unsigned long long)raw[u].y << 32) | raw[u].x);
             const bool excluded = h.excl_enabled != 0 && idv == h.src_excl;  // :90
             const bool in_window = idv >= h.earliest && idv <= h.latest;     // :91
-            const bool keep = seq[u] >= 0 && !excluded && in_window;
+            // (seq[u] is still the gather's rank: the number of ranks, or above, where the slot has no posting)
+            const bool keep = (uint32_t)seq[u] < n_ranks && !excluded && in_window;
             seq[u] = keep ? seq[u] : -1;
             hsh[u] = bloom_carry(idv);
             // wave count, identical in all lanes: of a fresh compare (hipcc makes a ballot of `keep` itself, or of anything
@@ -1028,7 +1137,9 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
       key = v >= *(const volatile double *)&hq->min_score ? score_key(v) : CAND_DROPPED;  // :125 (false for NaN)
     } else {
       const uint32_t pos = s_off[c] + (uint32_t)e;
-      idv = (long long)(((unsigned long long)(uint32_t)c << 32) | pos);
+      // (two-wave units: c is a rank up to here, and here alone the cluster is named)
+      const uint32_t cl = B8K ? (uint32_t)s_cl[B8K ? c : 0] : (uint32_t)c;
+      idv = (long long)(((unsigned long long)cl << 32) | pos);
     }
     cand_key[obase + i] = key;
     cand_id[obase + i] = idv;
