@@ -392,7 +392,9 @@ typedef struct sann_batcher_stats {
 } sann_batcher_stats_t;
 int sann_batcher_create(sann_index_t *index, const sann_batcher_options_t *options /* NULL = defaults, original variant */,
                         sann_batcher_t **out);
-/* Runs whatever was submitted, then stops the dispatchers.  Tickets nobody collected are dropped. */
+/* Runs whatever was submitted, then stops the dispatchers.  Tickets nobody collected are dropped.  A caller blocked in
+ * sann_wait (or inside sann_poll) when this is called gets its answer and returns before the object is freed: destroy waits
+ * for the callers inside.  No call may START on a batcher once destroy has been called. */
 int sann_batcher_destroy(sann_batcher_t *batcher);
 /* One getTweetCandidates request.  cluster_ids / scores: the source embedding (copied: reusable on return).  The out arrays
  * are the caller's and must stay valid until the ticket is collected; out_capacity >= min(maxNumResults, 1000).

@@ -158,3 +158,108 @@ def test_embedding_buffer_limits_close_and_grow_the_open_batch(pkg, oracle):
     finally:
         mb.close()
         index.close()
+
+
+def _alone(pkg, index, r, variant=None):
+    """The request through sann_get_tweet_candidates, one query, one caller: (ids, scores, map_size)."""
+    e_c, e_s, cfg, src, now = r
+    kw = {} if variant is None else {"variant": variant}
+    ids, sc, cnt, msz = pkg.simclusters_ann.get_tweet_candidates(
+        index, np.array([0, len(e_c)], np.int64), e_c, e_s, cfg, now_ms=now, source_tweet_ids=np.array([src or 0], np.int64),
+        has_source_tweet=np.array([src is not None], np.uint8), **kw)
+    return ids[0, :cnt[0]].copy(), sc[0, :cnt[0]].copy(), int(msz[0])
+
+
+def test_destroy_answers_the_callers_blocked_in_wait(pkg):
+    """Eight threads sleep in sann_wait on a batch that nothing but its two-second deadline would close; the batcher is
+    destroyed from the main thread.  Destroy runs what was submitted and waits for the callers inside: each of the eight
+    returns SANN_OK with the rows its request gets alone, and none touches the freed object."""
+    import time
+    co = pkg.corpus.make_corpus(20_000, 600, seed=22, index_cap=400)
+    index = pkg.ClusterTweetIndex(co.cluster_ids, co.list_offsets, co.tweet_ids, co.scores)
+    reqs = _requests(pkg, co, 8, 6)
+    want = [_alone(pkg, index, r) for r in reqs]
+    mb = pkg.MicroBatcher(index, max_batch=64, max_wait_us=2_000_000)
+    outs, errs, entering = [None] * 8, [], [threading.Event() for _ in range(8)]
+
+    def caller(t):
+        try:
+            r = reqs[t]
+            ticket, outs[t] = mb.submit(r[0], r[1], r[2], now_ms=r[4], source_tweet_id=r[3])
+            entering[t].set()
+            mb.wait(ticket)
+        except Exception as e:  # noqa: BLE001
+            errs.append(e)
+            entering[t].set()
+
+    ths = [threading.Thread(target=caller, args=(t,)) for t in range(8)]
+    for th in ths:
+        th.start()
+    for ev in entering:
+        assert ev.wait(30)
+    time.sleep(0.02)  # (from the flag to the native call is a few bytecodes: every caller is inside sann_wait now)
+    t0 = time.monotonic()
+    mb.close()
+    for th in ths:
+        th.join(30)
+    assert not any(th.is_alive() for th in ths), "a caller is still blocked after destroy returned"
+    assert time.monotonic() - t0 < 2.0, "the batch left by its deadline, not by the destroy"
+    assert not errs, errs[0]
+    for t in range(8):
+        n = int(outs[t][2][0])
+        assert n == len(want[t][0]) and int(outs[t][3][0]) == want[t][2]
+        assert np.array_equal(outs[t][0][:n], want[t][0]) and np.array_equal(outs[t][1][:n].view(np.int64), want[t][1].view(np.int64))
+    index.close()
+
+
+def test_concurrent_callers_each_get_their_own_status_and_message(pkg):
+    """Four threads in sann_get_tweet_candidates at once, fifty rounds: two valid requests, and two that fail validation
+    inside the submission engine with different statuses and messages (legacy variant: maxNumResults above 1000; an unknown
+    algorithm).  A job's message is taken where its status turns bad, so nobody gets a neighbour's."""
+    co = pkg.corpus.make_corpus(20_000, 600, seed=22, index_cap=400)
+    index = pkg.ClusterTweetIndex(co.cluster_ids, co.list_offsets, co.tweet_ids, co.scores)
+    legacy = pkg.simclusters_ann.Variant.legacy
+    good = _requests(pkg, co, 2, 9)
+    for i, alg in enumerate((pkg.ScoringAlgorithm.CosineSimilarity, pkg.ScoringAlgorithm.LogCosineSimilarity)):
+        good[i][2].annAlgorithm = alg  # (forms the legacy variant has)
+    e_c, e_s, _, _, now = good[0]
+    too_many = (e_c, e_s, pkg.SimClustersANNConfig(maxNumResults=1001), None, now)
+    no_such = (e_c, e_s, pkg.SimClustersANNConfig(maxNumResults=50, annAlgorithm=99), None, now)
+    expect_error = {2: "legacy variant: max_num_results above 1000", 3: "legacy variant: ann_algorithm must be dot product, cosine or log cosine"}
+    calls = [good[0], good[1], too_many, no_such]
+    want = [_alone(pkg, index, r, legacy) for r in good]
+    codes = {}
+    for t in (2, 3):
+        with pytest.raises(pkg.simclusters_ann.SannError) as ei:
+            _alone(pkg, index, calls[t], legacy)
+        codes[t] = ei.value.code
+        assert expect_error[t] in str(ei.value)
+    assert codes[2] != codes[3]
+    rounds, bad, gate = 50, [], threading.Barrier(4)
+
+    def caller(t):
+        try:
+            for rnd in range(rounds):
+                gate.wait(30)
+                try:
+                    got = _alone(pkg, index, calls[t], legacy)
+                except pkg.simclusters_ann.SannError as e:
+                    if t < 2 or e.code != codes[t] or not str(e).endswith(expect_error[t]):
+                        bad.append((rnd, t, str(e)))
+                    continue
+                if t >= 2:
+                    bad.append((rnd, t, "no error"))
+                elif not (np.array_equal(got[0], want[t][0]) and np.array_equal(got[1].view(np.int64), want[t][1].view(np.int64))
+                          and got[2] == want[t][2]):
+                    bad.append((rnd, t, "another answer than the single caller's"))
+        except Exception as e:  # noqa: BLE001
+            bad.append((-1, t, repr(e)))
+            gate.abort()
+
+    ths = [threading.Thread(target=caller, args=(t,)) for t in range(4)]
+    for th in ths:
+        th.start()
+    for th in ths:
+        th.join()
+    assert not bad, bad[:5]
+    index.close()

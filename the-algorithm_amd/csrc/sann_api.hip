@@ -30,6 +30,7 @@
 #include "sann_host.h"
 #include "sann_kernels.h"
 #include "abi_guard.h"
+#include "handoff.h"
 
 using namespace sann;
 
@@ -1631,12 +1632,59 @@ struct EngineJob {
   int slot = 0;
   int stage = 0;  // 1 kernels enqueued, 2 copies enqueued
   bool zero_copy = false;  // the merge kernel writes the answer straight into the caller's pinned arrays
+  // The job's status: this is the only place it changes.  The first failure stays, with the message of THAT failure (the engine
+  // thread's g_err as it stands when the failing call returns, not when the job retires: by then another job may have failed).
   int rc = SANN_OK;
   std::string msg;
-  std::mutex m;
-  std::condition_variable cv;
-  bool done = false;
+  void set(int status, const std::string &why = g_err) noexcept {
+    if (rc != SANN_OK || status == SANN_OK) return;
+    rc = status;
+    try { msg = why; } catch (...) {}  // (no memory for the text: the status still travels)
+  }
+  // The caller sleeps here, in its own stack frame: it owns the job and its arguments until wait() returns, the engine owns the
+  // batch object.  Completing is the engine's last access to the job.
+  handoff::Completion done;
 };
+
+// The index's pool of batch objects, one per concurrent call of the boundary functions.  Take one (or make one) ...
+static int pool_take(sann_index *ix, sann_batch **out) {
+  sann_batch *b = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(ix->pool_mu);
+    if (!ix->pool.empty()) {
+      b = ix->pool.back();
+      ix->pool.pop_back();
+    }
+  }
+  if (!b) {
+    b = new (std::nothrow) sann_batch();
+    if (!b) return fail(SANN_ENOMEM, "out of host memory");
+    b->ix = ix;
+  }
+  *out = b;
+  return SANN_OK;
+}
+// ... and give it back after a call that ended with `rc` on stream `st`.  At most 16 are kept, and only after SANN_OK /
+// SANN_EINVAL / SANN_ELIMIT (a device error may have left the object in an unknown state).  One that is not kept is deleted
+// after its stream has drained.  The calling thread's error message is left as it was.
+static void pool_give_back(sann_index *ix, sann_batch *b, int rc, hipStream_t st) noexcept {
+  if (rc == SANN_OK || rc == SANN_EINVAL || rc == SANN_ELIMIT) {
+    std::lock_guard<std::mutex> lk(ix->pool_mu);
+    if (ix->pool.size() < 16) {
+      try {
+        ix->pool.push_back(b);
+        return;
+      } catch (...) {  // (no memory to grow the pool: not kept)
+      }
+    }
+  }
+  std::string keep;
+  keep.swap(g_err);
+  (void)hipSetDevice(ix->device);
+  (void)hipStreamSynchronize(st);
+  delete b;
+  g_err.swap(keep);
+}
 
 struct sann_engine {
   sann_index *ix;
@@ -1649,59 +1697,31 @@ struct sann_engine {
   hipStream_t streams[kStreams] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t copied[kStreams] = {nullptr, nullptr, nullptr, nullptr};
 
-  void finish_job(EngineJob *j) {
-    std::string keep = g_err;
-    {  // the batch object goes back to the pool (a device error may have left it in an unknown state: dropped then)
-      if (j->b && j->zero_copy) {  // (the caller's arrays are the caller's again)
+  // The batch object goes back to the pool, then the caller is woken: after complete() the job is the caller's again (it may
+  // already be gone), so nothing of *j is read afterwards.
+  void finish_job(EngineJob *j) noexcept {
+    if (j->b) {
+      if (j->zero_copy) {  // (the caller's arrays are the caller's again)
         j->b->bound_ids = j->b->bound_scores = j->b->bound_counts = j->b->bound_map_sizes = nullptr;
         j->b->bound_nq = j->b->bound_stride = 0;
       }
-      bool pooled = false;
-      if (j->b && (j->rc == SANN_OK || j->rc == SANN_EINVAL || j->rc == SANN_ELIMIT)) {
-        std::lock_guard<std::mutex> lk(ix->pool_mu);
-        if (ix->pool.size() < 16) {
-          ix->pool.push_back(j->b);
-          pooled = true;
-        }
-      }
-      if (!pooled && j->b) {
-        (void)hipStreamSynchronize(streams[j->slot]);
-        delete j->b;
-      }
+      pool_give_back(ix, j->b, j->rc, streams[j->slot]);
       j->b = nullptr;
     }
-    if (j->rc != SANN_OK) j->msg = keep;
-    {
-      std::lock_guard<std::mutex> lk(j->m);
-      j->done = true;
-    }
-    j->cv.notify_one();
+    j->done.complete(j->rc, std::move(j->msg));
   }
 
   // reset + kernels of a job on stream `slot`, its unit kernel behind `prev`'s
   void submit(EngineJob *j, int slot, sann_batch *prev, bool pipeline_empty) {
     j->slot = slot;
     sann_batch *b = nullptr;
-    {
-      std::lock_guard<std::mutex> lk(ix->pool_mu);
-      if (!ix->pool.empty()) {
-        b = ix->pool.back();
-        ix->pool.pop_back();
-      }
-    }
-    if (!b) {
-      b = new (std::nothrow) sann_batch();
-      if (!b) {
-        j->rc = fail(SANN_ENOMEM, "out of host memory");
-        return;
-      }
-      b->ix = ix;
-    }
+    j->set(pool_take(ix, &b));
+    if (j->rc != SANN_OK) return;
     j->b = b;
     b->variant = j->variant;
     hipStream_t st = streams[slot];
-    j->rc = batch_reset(b, st, j->now_ms, j->nq, j->emb_offsets, j->emb_cluster_ids, j->emb_scores, j->source_tweet_ids,
-                        j->has_source_tweet, j->configs, j->n_configs, j->scan_offsets, j->scan_cluster_ids, j->now_ms_q);
+    j->set(batch_reset(b, st, j->now_ms, j->nq, j->emb_offsets, j->emb_cluster_ids, j->emb_scores, j->source_tweet_ids,
+                       j->has_source_tweet, j->configs, j->n_configs, j->scan_offsets, j->scan_cluster_ids, j->now_ms_q));
     // Zero copy (round 3), for a SMALL call (<= 256 queries) that finds the pipeline EMPTY -- the latency case, a single request
     // or a thin micro-batch: when the caller's four arrays are pinned (sann_host_alloc) and laid out at the batch's own stride,
     // the merge kernel is pointed at them and writes every query's rows home as it finishes them (one query: 0.107 against
@@ -1733,7 +1753,7 @@ struct sann_engine {
         j->zero_copy = true;
       }
     }
-    if (j->rc == SANN_OK) j->rc = sann_batch_run_after(b, st, prev, 0);
+    if (j->rc == SANN_OK) j->set(sann_batch_run_after(b, st, prev, 0));
     if (j->rc == SANN_OK) j->stage = 1;
   }
 
@@ -1746,67 +1766,87 @@ struct sann_engine {
     std::deque<EngineJob *> inflight;  // oldest first; at most kStreams
     int next_slot = 0;
     std::unique_lock<std::mutex> lk(mu);
-    for (;;) {
-      // submit what is waiting, up to two jobs ahead of the one whose answer is being collected
-      while (!queue.empty() && (int)inflight.size() < kStreams) {
-        EngineJob *j = queue.front();
-        queue.pop_front();
+    bool finished = false;
+    while (!finished) {
+      EngineJob *held = nullptr;  // the job in this thread's hands: the one an exception fails
+      handoff::guarded(SANN_ENOMEM, SANN_EINTERNAL, [&] {
+        // submit what is waiting, up to two jobs ahead of the one whose answer is being collected
+        while (!queue.empty() && (int)inflight.size() < kStreams) {
+          EngineJob *j = held = queue.front();
+          queue.pop_front();
+          lk.unlock();
+          sann_batch *prev = nullptr;
+          for (auto it = inflight.rbegin(); it != inflight.rend(); ++it)
+            if ((*it)->stage == 1 && (*it)->b) { prev = (*it)->b; break; }
+          const double t_s = trace_on() ? trace_now() : 0.0;
+          submit(j, next_slot, prev, inflight.empty());
+          if (trace_on()) { g_trace_us[0] += trace_now() - t_s; g_trace_calls++; }
+          if (j->rc != SANN_OK) finish_job(j);
+          else {
+            inflight.push_back(j);
+            next_slot = (next_slot + 1) % kStreams;
+          }
+          held = nullptr;
+          lk.lock();
+        }
+        if (inflight.empty()) {
+          if (stop) finished = true;
+          else cv.wait(lk);
+          return;
+        }
+        const bool more_queued = !queue.empty();
         lk.unlock();
-        sann_batch *prev = nullptr;
-        for (auto it = inflight.rbegin(); it != inflight.rend(); ++it)
-          if ((*it)->stage == 1 && (*it)->b) { prev = (*it)->b; break; }
-        const double t_s = trace_on() ? trace_now() : 0.0;
-        submit(j, next_slot, prev, inflight.empty());
-        if (trace_on()) { g_trace_us[0] += trace_now() - t_s; g_trace_calls++; }
-        if (j->rc != SANN_OK) finish_job(j);
-        else {
-          inflight.push_back(j);
-          next_slot = (next_slot + 1) % kStreams;
+        // 1. the oldest job whose kernels are still out: wait for them, settle, send its answer home.  This comes BEFORE the wait
+        //    for an older job's copy: the copy of job A (6.6 MB over PCIe, ~150 us) then flies while the engine waits for job B's
+        //    kernels, instead of the two waits adding up (round 3, first form: 150 + 90 + 40 us of engine time per job = 0.28 ms
+        //    per call whatever the number of callers)
+        EngineJob *k1 = nullptr;
+        for (EngineJob *c : inflight)
+          if (c->stage == 1) { k1 = c; break; }
+        if (k1) {
+          held = k1;
+          hipStream_t st = streams[k1->slot];
+          const double t_f = trace_on() ? trace_now() : 0.0;
+          k1->set(sann_batch_finish(k1->b, st));
+          const double t_r = trace_on() ? trace_now() : 0.0;
+          if (k1->rc == SANN_OK && !k1->zero_copy)
+            k1->set(results_impl(k1->b, st, k1->out_ids, k1->out_scores, k1->out_stride, k1->out_counts, k1->out_map_sizes, false,
+                                 /* by_kernel = */ !memcpy_when_busy() || inflight.size() < (size_t)kStreams));
+          if (trace_on()) { g_trace_us[2] += t_r - t_f; g_trace_us[1] += trace_now() - t_r; }
+          k1->stage = 2;  // (a failed job has nothing in flight: it retires below without a wait to speak of)
+          held = nullptr;
         }
+        // 2. retire, in submission order, the jobs whose copies have arrived; block on the front's copy only when there is nothing
+        //    else to do (no kernels out, nothing queued)
+        while (!inflight.empty() && inflight.front()->stage == 2) {
+          EngineJob *f = held = inflight.front();
+          bool other_work = more_queued && (int)inflight.size() < kStreams;  // (a queued job that has a slot to go to)
+          for (EngineJob *c : inflight) other_work = other_work || c->stage == 1;
+          if (f->rc == SANN_OK) {
+            // (the stream holds nothing but this job: a slot is reused only after its job has left `inflight`)
+            if (other_work && hipStreamQuery(streams[f->slot]) == hipErrorNotReady) break;
+            const double t_w = trace_on() ? trace_now() : 0.0;
+            if (hipStreamSynchronize(streams[f->slot]) != hipSuccess) f->set(fail(SANN_EDEVICE, "hipStreamSynchronize"));
+            if (trace_on()) g_trace_us[3] += trace_now() - t_w;
+          }
+          inflight.pop_front();
+          finish_job(f);
+          held = nullptr;
+        }
+        held = nullptr;  // (the front job stays in flight)
         lk.lock();
-      }
-      if (inflight.empty()) {
-        if (stop) break;
-        cv.wait(lk);
-        continue;
-      }
-      const bool more_queued = !queue.empty();
-      lk.unlock();
-      // 1. the oldest job whose kernels are still out: wait for them, settle, send its answer home.  This comes BEFORE the wait
-      //    for an older job's copy: the copy of job A (6.6 MB over PCIe, ~150 us) then flies while the engine waits for job B's
-      //    kernels, instead of the two waits adding up (round 3, first form: 150 + 90 + 40 us of engine time per job = 0.28 ms
-      //    per call whatever the number of callers)
-      EngineJob *k1 = nullptr;
-      for (EngineJob *c : inflight)
-        if (c->stage == 1) { k1 = c; break; }
-      if (k1) {
-        hipStream_t st = streams[k1->slot];
-        const double t_f = trace_on() ? trace_now() : 0.0;
-        k1->rc = sann_batch_finish(k1->b, st);
-        const double t_r = trace_on() ? trace_now() : 0.0;
-        if (k1->rc == SANN_OK && !k1->zero_copy)
-          k1->rc = results_impl(k1->b, st, k1->out_ids, k1->out_scores, k1->out_stride, k1->out_counts, k1->out_map_sizes, false,
-                                /* by_kernel = */ !memcpy_when_busy() || inflight.size() < (size_t)kStreams);
-        if (trace_on()) { g_trace_us[2] += t_r - t_f; g_trace_us[1] += trace_now() - t_r; }
-        k1->stage = 2;  // (a failed job has nothing in flight: it retires below without a wait to speak of)
-      }
-      // 2. retire, in submission order, the jobs whose copies have arrived; block on the front's copy only when there is nothing
-      //    else to do (no kernels out, nothing queued)
-      while (!inflight.empty() && inflight.front()->stage == 2) {
-        EngineJob *f = inflight.front();
-        bool other_work = more_queued && (int)inflight.size() < kStreams;  // (a queued job that has a slot to go to)
-        for (EngineJob *c : inflight) other_work = other_work || c->stage == 1;
-        if (f->rc == SANN_OK) {
-          // (the stream holds nothing but this job: a slot is reused only after its job has left `inflight`)
-          if (other_work && hipStreamQuery(streams[f->slot]) == hipErrorNotReady) break;
-          const double t_w = trace_on() ? trace_now() : 0.0;
-          if (hipStreamSynchronize(streams[f->slot]) != hipSuccess) f->rc = fail(SANN_EDEVICE, "hipStreamSynchronize");
-          if (trace_on()) g_trace_us[3] += trace_now() - t_w;
+      }, [&](int status, const char *msg) {
+        // An exception (no memory, mostly) in the submit, the finish or the retirement of `held`: that job fails with the
+        // classified status, leaves `inflight` if it was there, and is completed (finish_job drains its stream before the batch
+        // object goes, so whatever it had enqueued is over before its caller wakes); the loop goes on with the other jobs.
+        if (held) {
+          held->set(status, handoff::text(msg));
+          auto it = std::find(inflight.begin(), inflight.end(), held);
+          if (it != inflight.end()) inflight.erase(it);
+          finish_job(held);
         }
-        inflight.pop_front();
-        finish_job(f);
-      }
-      lk.lock();
+        if (!lk.owns_lock()) lk.lock();
+      });
     }
     lk.unlock();
     for (int i = 0; i < kStreams; i++) {
@@ -1865,27 +1905,13 @@ int sann_candidates_pooled(sann_index_t *index, int32_t variant, int64_t now_ms,
       e->queue.push_back(&j);
     }
     e->cv.notify_one();
-    {
-      std::unique_lock<std::mutex> lk(j.m);
-      j.cv.wait(lk, [&] { return j.done; });
-    }
-    if (j.rc != SANN_OK) return fail(j.rc, j.msg);
+    j.done.wait();
+    if (j.done.status() != SANN_OK) return fail(j.done.status(), j.done.message());
     return SANN_OK;
   }
+  HIP_TRY(hipSetDevice(index->device));
   sann_batch *b = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(index->pool_mu);
-    if (!index->pool.empty()) {
-      b = index->pool.back();
-      index->pool.pop_back();
-    }
-  }
-  if (!b) {
-    HIP_TRY(hipSetDevice(index->device));
-    b = new (std::nothrow) sann_batch();
-    if (!b) return fail(SANN_ENOMEM, "out of host memory");
-    b->ix = index;
-  }
+  if (int rc = pool_take(index, &b)) return rc;
   if (!b->own_stream) {
     hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -1896,39 +1922,23 @@ int sann_candidates_pooled(sann_index_t *index, int32_t variant, int64_t now_ms,
   b->variant = variant;
   hipStream_t st = b->own_stream;
   // SANN_TRACE_CALLS=1: wall time per stage of this call, summed over the process (printed by sann_debug_call_trace)
-  static const bool trace = [] { const char *e = getenv("SANN_TRACE_CALLS"); return e && e[0] == '1'; }();
-  auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_a = trace ? now_us() : 0.0;
+  const double t_a = trace_on() ? trace_now() : 0.0;
   int rc = batch_reset(b, st, now_ms, nq, emb_offsets, emb_cluster_ids, emb_scores, source_tweet_ids, has_source_tweet,
                        configs, n_configs, scan_offsets, scan_cluster_ids, now_ms_q);
-  const double t_b = trace ? now_us() : 0.0;
+  const double t_b = trace_on() ? trace_now() : 0.0;
   if (rc == SANN_OK) rc = sann_batch_run(b, st);
-  const double t_c = trace ? now_us() : 0.0;
+  const double t_c = trace_on() ? trace_now() : 0.0;
   // (the copies of the answer are enqueued when the kernels have finished: a copy that waits for its own stream's kernels sits
   // in the copy engine's queue in front of the other callers' copies -- measured 1.16 ms instead of 0.33 ms per call, four callers)
   if (rc == SANN_OK) rc = sann_batch_finish(b, st);
-  const double t_d = trace ? now_us() : 0.0;
+  const double t_d = trace_on() ? trace_now() : 0.0;
   if (rc == SANN_OK) rc = results_impl(b, st, out_ids, out_scores, out_stride, out_counts, out_map_sizes);
-  if (trace) {
-    const double t_e = now_us();
+  if (trace_on()) {
+    const double t_e = trace_now();
     g_trace_us[0] += t_b - t_a; g_trace_us[1] += t_c - t_b; g_trace_us[2] += t_d - t_c; g_trace_us[3] += t_e - t_d;
     g_trace_calls++;
   }
-  std::string keep = g_err;
-  bool pooled = false;
-  if (rc == SANN_OK || rc == SANN_EINVAL || rc == SANN_ELIMIT) {  // a device error may have left the object in an unknown state
-    std::lock_guard<std::mutex> lk(index->pool_mu);
-    if (index->pool.size() < 16) {
-      index->pool.push_back(b);
-      pooled = true;
-    }
-  }
-  if (!pooled) {
-    (void)hipSetDevice(index->device);
-    (void)hipStreamSynchronize(st);
-    delete b;
-  }
-  if (rc != SANN_OK) g_err = keep;
+  pool_give_back(index, b, rc, st);
   return rc;
 }
 extern "C" {
@@ -1989,21 +1999,10 @@ int sann_heavy_rank(sann_index_t *index, const struct rsx_store *source_store, c
   light.max_tweet_candidate_age_hours = c.max_tweet_candidate_age_hours;
   light.min_tweet_candidate_age_hours = c.min_tweet_candidate_age_hours;
   light.ann_algorithm = !c.enable_partial_normalization ? SANN_ALG_DOT_PRODUCT : (c.ranking_algorithm == 6 ? SANN_ALG_LOG_COSINE : SANN_ALG_COSINE);
-  sann_batch *b = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(index->pool_mu);
-    if (!index->pool.empty()) {
-      b = index->pool.back();
-      index->pool.pop_back();
-    }
-  }
   HIP_TRY(hipSetDevice(index->device));
-  if (!b) {
-    b = new (std::nothrow) sann_batch();
-    if (!b) return fail(SANN_ENOMEM, "out of host memory");
-    b->ix = index;
-  }
-  int rc = SANN_OK;
+  sann_batch *b = nullptr;
+  int rc = pool_take(index, &b);
+  if (rc != SANN_OK) return rc;
   if (!b->own_stream && hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking) != hipSuccess) rc = fail(SANN_EDEVICE, "hipStreamCreateWithFlags");
   hipStream_t st = b->own_stream;
   b->variant = SANN_VARIANT_LEGACY;
@@ -2035,20 +2034,7 @@ int sann_heavy_rank(sann_index_t *index, const struct rsx_store *source_store, c
       dev(hipStreamSynchronize(st), "hipStreamSynchronize");
     }
   }
-  std::string keep = g_err;
-  bool pooled = false;
-  if (rc == SANN_OK || rc == SANN_EINVAL || rc == SANN_ELIMIT) {
-    std::lock_guard<std::mutex> lk(index->pool_mu);
-    if (index->pool.size() < 16) {
-      index->pool.push_back(b);
-      pooled = true;
-    }
-  }
-  if (!pooled) {
-    (void)hipStreamSynchronize(st);
-    delete b;
-  }
-  if (rc != SANN_OK) g_err = keep;
+  pool_give_back(index, b, rc, st);
   return rc;
 } ABI_CATCH
 
