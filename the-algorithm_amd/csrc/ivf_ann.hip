@@ -358,6 +358,8 @@ int ivf_internal::search_device_out(ivf_index *ix, int32_t nq, const float *d_qu
   return search_rows(ix, nq, d_queries, k, nprobe, d_dist, d_ids, d_counts, true);
 } ABI_CATCH
 
+ivf_hq::State *ivf_internal::hnsw_quantizer(ivf_index *ix) { return hq_state(ix); }  // ivf_hnsw_quantizer_internal.h
+
 int ivf_internal::device_of(const ivf_index *ix) { return ix->device; }
 int64_t ivf_internal::last_control_bytes(const ivf_index *ix) { return ix->last_ctl; }
 

@@ -3,7 +3,9 @@
 // layout of the lists up to the payload scatter, the steps of a search around the scan launch, the select step's key load
 // (the sort itself is survivor_topk.h's), the steps of an add and of a restore around the payload, and the exports.  Where
 // the two indexes differ the difference is an argument: the rows of a list block, a payload buffer and its row bytes, or a
-// callable (the payload scatter, the scan launch).  Failures go through the error channel of ivf_error.h (host_error.h with
+// callable (the payload scatter, the scan launch).  The coarse step -- assign_rows and the first half of probe_chunk -- is
+// the exhaustive search over the centroids, or, with an HNSW quantizer attached (ivf_hnsw_quantizer_internal.h), the walk
+// of a graph over them.  Failures go through the error channel of ivf_error.h (host_error.h with
 // the IVF_* codes).  A source includes this once, as it does ivf_kernels.h;
 // everything is file-local.  Its host functions instantiate the hipcub sorts and scans, so only the index sources include
 // it (the two above and grouped_ann.hip, whose cell is the caller's group: IvfBase without a coarse quantizer, cell_bits
@@ -19,9 +21,11 @@
 #include <vector>
 
 #include "../../include/dense_ann.h"
+#include "../../include/hnsw_ann.h"
 #include "../../include/ivf_ann.h"
 #include "ann_by_id_internal.h"
 #include "ivf_error.h"
+#include "ivf_hnsw_quantizer_internal.h"
 #include "ivf_kernels.h"
 #include "ivf_restore.h"
 
@@ -33,6 +37,12 @@ namespace {
     int rc_ = (expr);                                            \
     if (rc_) return fail(rc_, std::string("coarse quantizer: ") + dann_last_error()); \
   } while (0)
+// a call into hnsw_ann.hip (the HNSW coarse quantizer): the same numbers again, its message is in hnsw_last_error()
+#define HQCALL(expr)                                             \
+  do {                                                           \
+    int rc_ = (expr);                                            \
+    if (rc_) return fail(rc_, std::string("HNSW coarse quantizer: ") + hnsw_last_error()); \
+  } while (0)
 
 // what an ivf_index and an ivfpq_index both hold; each adds its payload (rows or codes), its list payload and its own scratch
 struct IvfBase {
@@ -41,6 +51,8 @@ struct IvfBase {
   int64_t n = 0;
   int ids_mode = -1;  // -1: no add yet; 0: ids are positions; 1: ids given
   dann_index *coarse = nullptr;
+  ivf_hq::State hq;  // the optional HNSW coarse quantizer (ivf_hnsw_quantizer_internal.h); hq.graph is owned
+  Buf hq_lastq, hq_missing;  // the prepared queries of the last search that walked; the missing probes of a chunk
   // per row, in the order added
   Buf cell, ids;
   // the lists: every list starts on a block of `lblock` rows (layout_lists); lrank[slot] is the slot's rank in id order
@@ -55,12 +67,14 @@ struct IvfBase {
   Buf probes;
   int32_t last_nq = 0, last_nprobe = 0, last_rounds = 0;
   int64_t last_rows = 0;
+  int64_t chunk_pairs = 0;  // the (cell, query) pairs of the last chunk that name a cell: all of them, but for a short walk
   int64_t last_ctl = 0;  // control bytes the search read back: round flags, row and group counts (never an answer)
   float t_coarse = 0, t_scan = 0, t_sel = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   RestoreState rs;  // faiss_restore.h
   ~IvfBase() {
     if (coarse) (void)dann_index_destroy(coarse);
+    if (hq.graph) (void)hnsw_index_destroy(hq.graph);
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -140,7 +154,26 @@ int exclusive_sum(IvfBase *ix, const uint32_t *in, uint32_t *out, int n) {
 }
 
 // the nearest centroid of each of n fp16 rows (the coarse search with k = 1, CHUNK rows at a time) -> cell[0 .. n)
+// With an HNSW quantizer attached: the walk with k = 1 at the index's quantizer_ef, as Faiss's add goes through the quantizer.
+int assign_rows_walk(IvfBase *ix, const _Float16 *flat, int64_t n, int32_t *cell) {
+  const int d = ix->d, ef = ix->hq.ef;
+  for (int64_t r0 = 0; r0 < n; r0 += CHUNK) {
+    const int m = (int)std::min<int64_t>(CHUNK, n - r0);
+    ann_by_id::HnswTarget tgt;
+    HQCALL(ann_by_id::hnsw_open(ix->hq.graph, m, 1, ef, false, &tgt));
+    hipLaunchKernelGGL(hq_rows_kernel, dim3(blocks_for((int64_t)m * (tgt.dpad >> 3))), dim3(256), 0, 0, flat + (size_t)r0 * d, m, d,
+                       tgt.dpad, tgt.q);
+    ITRY(hipGetLastError());
+    ann_by_id::DeviceResult res;
+    HQCALL(ann_by_id::hnsw_search_prepared(ix->hq.graph, m, 1, ef, &res));
+    hipLaunchKernelGGL(cells_kernel, dim3(blocks_for(m)), dim3(256), 0, 0, res.ids, m, cell + r0);
+    ITRY(hipGetLastError());
+  }
+  ITRY(hipDeviceSynchronize());
+  return IVF_OK;
+}
 int assign_rows(IvfBase *ix, const _Float16 *flat, const float *sumsq, int64_t n, int32_t *cell) {
+  if (ix->hq.graph) return assign_rows_walk(ix, flat, n, cell);
   ann_by_id::DannTarget tgt;
   DCALL(ann_by_id::dann_open(ix->coarse, 1, false, &tgt));
   ITRY(ix->c_dist.reserve((size_t)CHUNK * sizeof(float)));
@@ -250,6 +283,13 @@ int search_begin(IvfBase *ix, int32_t nq, int32_t k, int32_t *nprobe) {
   ix->last_rounds = 0;
   ix->last_ctl = 0;
   ix->t_coarse = ix->t_scan = ix->t_sel = 0;
+  ix->hq.evals = ix->hq.expansions = ix->hq.missing = 0;
+  ix->hq.last_q_n = 0;
+  if (ix->hq.graph) {
+    ITRY(ix->hq_lastq.reserve((size_t)nq * ix->d * sizeof(_Float16)));
+    ITRY(ix->hq_missing.reserve(sizeof(uint32_t)));
+    ix->hq.last_q = ix->hq_lastq.p;
+  }
   return IVF_OK;
 }
 // chunk(q0, m) over the queries, CHUNK at a time
@@ -258,9 +298,12 @@ int search_chunks(IvfBase *ix, int32_t nq, Chunk chunk) {
   for (int32_t q0 = 0; q0 < nq; q0 += CHUNK)
     if (int rc = chunk(q0, std::min<int32_t>(CHUNK, nq - q0))) return rc;
   ix->last_nq = nq;
+  if (ix->hq.graph) ix->hq.last_q_n = nq;
   return IVF_OK;
 }
 
+// With an HNSW quantizer attached (ix->hq.graph) the coarse search is the graph's walk with k = nprobe at quantizer_ef, and
+// a probe the walk did not find is exported as -1 and scanned by nobody (hq_probes_kernel); chunk_pairs counts the rest.
 // The first step of a chunk, from event 0: the queries (on the host, or on the device already) -> fp16 rows at q16 and,
 // with qfrag != NULL, the fragments of the flat scan; the coarse search for their nprobe nearest centroids; the probe
 // export; the (cell, query) pairs sorted by cell (pair_cell_s, pair_q_s) and the queries per cell (per_cell).  rows_acc is
@@ -270,10 +313,15 @@ int probe_chunk(IvfBase *ix, int32_t q0, int32_t nq, const float *queries, bool 
   const int d = ix->d, nlist = ix->nlist;
   const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
+  const bool walk = ix->hq.graph != nullptr;  // the HNSW quantizer: the graph is walked, the centroids are not scanned
   ann_by_id::DannTarget tgt;
-  DCALL(ann_by_id::dann_open(ix->coarse, nprobe, false, &tgt));
   ann_by_id::DannChunk ch;
-  DCALL(ann_by_id::dann_chunk_open(ix->coarse, nq, nprobe, &ch));
+  if (!walk || qfrag) {  // (the flat scan's fragments are written beside the exhaustive search's)
+    DCALL(ann_by_id::dann_open(ix->coarse, nprobe, false, &tgt));
+    DCALL(ann_by_id::dann_chunk_open(ix->coarse, nq, nprobe, &ch));
+  }
+  ann_by_id::HnswTarget wt;
+  if (walk) HQCALL(ann_by_id::hnsw_open(ix->hq.graph, nq, nprobe, ix->hq.ef, false, &wt));
   if (!on_device) ITRY(ix->stage.reserve((size_t)nq * d * sizeof(float)));
   ITRY(ix->qsumsq.reserve((size_t)((nq + 31) / 32 * 32) * sizeof(float)));
   ITRY(ix->c_dist.reserve((size_t)np * sizeof(float)));
@@ -300,21 +348,51 @@ int probe_chunk(IvfBase *ix, int32_t q0, int32_t nq, const float *queries, bool 
   hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, on_device ? queries : ix->stage.as<float>(),
                      (int64_t)nq, d, ix->metric == IVF_METRIC_COSINE ? 1 : 0, q16, ix->qsumsq.as<float>());
   ITRY(hipGetLastError());
-  hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, q16, ix->qsumsq.as<float>(), nq, d,
-                     tgt.S, ch.qf, ch.qsumsq, qfrag);
-  ITRY(hipGetLastError());
-  int64_t d2h = 0;
-  DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, nq, nprobe, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
-                                              ix->c_cnt.as<int32_t>(), &d2h));
-  ix->last_ctl += d2h;
+  if (!walk || qfrag) {
+    hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, q16, ix->qsumsq.as<float>(), nq, d,
+                       tgt.S, ch.qf, ch.qsumsq, qfrag);
+    ITRY(hipGetLastError());
+  }
+  ix->chunk_pairs = np;
+  if (walk) {
+    // the walk for the nprobe nearest cells of every query, answers left on the device; a walk may find fewer
+    hipLaunchKernelGGL(hq_rows_kernel, dim3(blocks_for((int64_t)nq * (wt.dpad >> 3))), dim3(256), 0, st, q16, nq, d, wt.dpad, wt.q);
+    ITRY(hipGetLastError());
+    ITRY(hipMemcpyAsync(ix->hq_lastq.as<_Float16>() + (size_t)q0 * d, q16, (size_t)nq * d * sizeof(_Float16), hipMemcpyDeviceToDevice, st));
+    ann_by_id::DeviceResult res;
+    HQCALL(ann_by_id::hnsw_search_prepared(ix->hq.graph, nq, nprobe, ix->hq.ef, &res));
+    ix->last_ctl += res.h2d_bytes + res.d2h_bytes;
+    int64_t evals = 0, expansions = 0;
+    HQCALL(hnsw_last_stats(ix->hq.graph, &evals, &expansions, nullptr, nullptr));
+    ix->hq.evals += evals;
+    ix->hq.expansions += expansions;
+    ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
+    ITRY(hipMemsetAsync(ix->rows_acc.p, 0, 8, st));
+    ITRY(hipMemsetAsync(ix->hq_missing.p, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(hq_probes_kernel, dim3(blocks_for(np)), dim3(256), 0, st, res.ids, res.counts, nq, nprobe,
+                       ix->probes.as<int32_t>() + (size_t)q0 * nprobe, ix->pair_cell.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
+                       ix->per_cell.as<uint32_t>(), ix->hq_missing.as<uint32_t>());
+    ITRY(hipGetLastError());
+    uint32_t missing = 0;
+    ITRY(hipMemcpyAsync(&missing, ix->hq_missing.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    ITRY(hipStreamSynchronize(st));
+    ix->last_ctl += (int64_t)sizeof(uint32_t);
+    ix->hq.missing += missing;
+    ix->chunk_pairs = np - (int64_t)missing;  // the pairs of the missing probes sort behind these
+  } else {
+    int64_t d2h = 0;
+    DCALL(ann_by_id::dann_chunk_search_prepared(ix->coarse, nq, nprobe, ix->c_dist.as<float>(), ix->c_ids.as<int64_t>(),
+                                                ix->c_cnt.as<int32_t>(), &d2h));
+    ix->last_ctl += d2h;
 
-  // inversion: (cell, query) pairs sorted by cell
-  ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
-  ITRY(hipMemsetAsync(ix->rows_acc.p, 0, 8, st));
-  hipLaunchKernelGGL(probes_kernel, dim3(blocks_for(np)), dim3(256), 0, st, ix->c_ids.as<int64_t>(), nq, nprobe,
-                     ix->probes.as<int32_t>() + (size_t)q0 * nprobe, ix->pair_cell.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
-                     ix->per_cell.as<uint32_t>());
-  ITRY(hipGetLastError());
+    // inversion: (cell, query) pairs sorted by cell
+    ITRY(hipMemsetAsync(ix->per_cell.p, 0, (size_t)nlist * 4, st));
+    ITRY(hipMemsetAsync(ix->rows_acc.p, 0, 8, st));
+    hipLaunchKernelGGL(probes_kernel, dim3(blocks_for(np)), dim3(256), 0, st, ix->c_ids.as<int64_t>(), nq, nprobe,
+                       ix->probes.as<int32_t>() + (size_t)q0 * nprobe, ix->pair_cell.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
+                       ix->per_cell.as<uint32_t>());
+    ITRY(hipGetLastError());
+  }
   return sort_by_cell(ix, ix->pair_cell.as<uint32_t>(), ix->pair_cell_s.as<uint32_t>(), ix->pair_q.as<uint32_t>(),
                       ix->pair_q_s.as<uint32_t>(), np);
 }
@@ -533,6 +611,17 @@ int last_stats(const IvfBase *ix, int64_t *rows_scanned, int32_t *rounds, float 
   if (scan_ms) *scan_ms = ix->t_scan;
   if (select_ms) *select_ms = ix->t_sel;
   return IVF_OK;
+}
+
+// the index's HNSW quantizer state, with what ivf_hnsw_quantizer.hip needs to know of the index
+ivf_hq::State *hq_state(IvfBase *ix) {
+  if (!ix) return nullptr;
+  ix->hq.device = ix->device;
+  ix->hq.metric = ix->metric;
+  ix->hq.d = ix->d;
+  ix->hq.nlist = ix->nlist;
+  ix->hq.coarse = ix->coarse;
+  return &ix->hq;
 }
 
 }  // namespace

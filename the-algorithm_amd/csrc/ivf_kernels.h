@@ -140,6 +140,42 @@ __global__ void probes_kernel(const int64_t *__restrict__ ids, int m, int nprobe
   pair_q[e] = (uint32_t)(e / nprobe);
   atomicAdd(&per_cell[c], 1u);
 }
+// ---------------------------------------------------------------------------------------------
+// the HNSW coarse quantizer (include/ivf_hnsw_quantizer.h): the graph over the centroids is walked instead of scanned
+// ---------------------------------------------------------------------------------------------
+// fp16 rows [m][d] -> the prepared-query rows of the graph, [m][dpad] with the padding zeroed: what hnsw_search prepares
+// from the same values (L2 and InnerProduct round an fp16 value to itself).  One thread per (row, 8-half piece); d is a
+// multiple of 16, so a piece lies inside the row or in the padding.
+__global__ void hq_rows_kernel(const _Float16 *__restrict__ flat, int m, int d, int dpad, _Float16 *__restrict__ q) {
+  const int pieces = dpad >> 3;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)m * pieces) return;
+  const int row = (int)(e / pieces), c = (int)(e % pieces);
+  half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c * 8 < d) v = *(const half8 *)&flat[(size_t)row * d + c * 8];
+  *(half8 *)&q[(size_t)row * dpad + c * 8] = v;
+}
+// probes_kernel for a walk's answer, which may be short: ids [m][nprobe] with counts[q] of them found.  A probe the walk
+// did not find is exported as -1; its pair carries the cell number MAX_NLIST, which sorts behind every cell, is counted
+// in no per_cell entry and so is read by no scan.  *missing counts them (an integer: any order gives the sum).
+__global__ void hq_probes_kernel(const int64_t *__restrict__ ids, const int32_t *__restrict__ counts, int m, int nprobe,
+                                 int32_t *__restrict__ probes, uint32_t *__restrict__ pair_cell, uint32_t *__restrict__ pair_q,
+                                 uint32_t *__restrict__ per_cell, uint32_t *__restrict__ missing) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)m * nprobe) return;
+  const int q = (int)(e / nprobe), j = (int)(e % nprobe);
+  pair_q[e] = (uint32_t)q;
+  if (j < counts[q]) {
+    const uint32_t c = (uint32_t)ids[e];
+    probes[e] = (int32_t)c;
+    pair_cell[e] = c;
+    atomicAdd(&per_cell[c], 1u);
+  } else {
+    probes[e] = -1;
+    pair_cell[e] = (uint32_t)MAX_NLIST;
+    atomicAdd(missing, 1u);
+  }
+}
 // one thread per cell: its groups of <= 32 queries, and its share of the rows scanned (integers: any order gives the sum)
 __global__ void groups_kernel(const uint32_t *__restrict__ per_cell, const uint32_t *__restrict__ pstart,
                               const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ sizes, int nlist,

@@ -572,11 +572,11 @@ int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq,
 int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
                  float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po, int32_t ht, bool out_on_device) {
   const int d = ix->d, nlist = ix->nlist;
-  const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
   ITRY(ix->q16.reserve((size_t)nq * d * sizeof(_Float16)));
   if (int rc = probe_chunk(ix, q0, nq, queries, on_device, k, nprobe, ix->q16.as<_Float16>(), nullptr)) return rc;
-  // one workgroup per pair
+  // one workgroup per pair that names a cell: all nq * nprobe of them, but for an HNSW quantizer's short walks (ivf_core.h)
+  const int64_t pairs = ix->chunk_pairs;
   hipLaunchKernelGGL(rows_scanned_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(),
                      ix->sizes.as<uint32_t>(), nlist, ix->rows_acc.as<unsigned long long>());
   ITRY(hipGetLastError());
@@ -609,10 +609,10 @@ int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, 
   if (int rc = scan_rounds(ix, nq, k, [&](int round, hipStream_t s) -> int {
         if (ht > 0) {
           h.scored = round == 0 ? ix->scored_acc.as<unsigned long long>() : nullptr;
-          hipLaunchKernelGGL(adc_scan_ht_kernel, dim3((unsigned)np), dim3(256), adc_ht_lds_bytes(ix->M, d), s, a, h);
+          hipLaunchKernelGGL(adc_scan_ht_kernel, dim3((unsigned)pairs), dim3(256), adc_ht_lds_bytes(ix->M, d), s, a, h);
           ITRY(hipGetLastError());
         } else if (ix->n > 0) {
-          hipLaunchKernelGGL(adc_scan_kernel, dim3((unsigned)np), dim3(256), adc_lds_bytes(ix->M, d), s, a);
+          hipLaunchKernelGGL(adc_scan_kernel, dim3((unsigned)pairs), dim3(256), adc_lds_bytes(ix->M, d), s, a);
           ITRY(hipGetLastError());
         }
         return IVF_OK;
@@ -767,6 +767,8 @@ int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_dev
 // the device-rows seam (ivf_device_rows.h)
 // ---------------------------------------------------------------------------------------------
 int64_t ivfpq_internal::slab_rows(int d) { return stage_slab_rows(d); }
+
+ivf_hq::State *ivfpq_internal::hnsw_quantizer(ivfpq_index *ix) { return hq_state(ix); }  // ivf_hnsw_quantizer_internal.h
 
 int ivfpq_internal::train_device(int32_t device, int32_t metric, int32_t d, int32_t nlist, int32_t M, int64_t n_train,
                                  const float *d_rows, int32_t niter, uint64_t seed, ivfpq_index **out) try {
