@@ -37,8 +37,7 @@ CASES = [("L2", 2000, 24, 8, 40, 64, 1, "gpu"), ("Cosine", 2000, 40, 16, 60, 64,
          ("Cosine", 20000, 24, 8, 40, 2000, 0, "load")]
 
 
-@pytest.mark.parametrize("metric,n,d,max_m,efc,nu,batch,builder", CASES)
-def test_update_is_the_restated_graph(pkg, oracle, metric, n, d, max_m, efc, nu, batch, builder):
+def _update_case(pkg, oracle, metric, n, d, max_m, efc, nu, batch, builder):
     m = getattr(pkg.dense_ann.DistanceMetric, metric)
     Hnsw = pkg.hnsw_ann.Hnsw
     rng = np.random.default_rng(n + d + max_m)
@@ -81,6 +80,18 @@ def test_update_is_the_restated_graph(pkg, oracle, metric, n, d, max_m, efc, nu,
             assert np.array_equal(dist[r, :cnt[r]].view(np.int32), od.view(np.int32))
     finally:
         ix.close()
+
+
+@pytest.mark.parametrize("metric,n,d,max_m,efc,nu,batch,builder", CASES)
+def test_update_is_the_restated_graph(pkg, oracle, metric, n, d, max_m, efc, nu, batch, builder):
+    _update_case(pkg, oracle, metric, n, d, max_m, efc, nu, batch, builder)
+
+
+def test_update_with_the_undo_log_is_the_restated_graph(pkg, oracle, monkeypatch):
+    """The first case again with the undo log of large indexes forced on (bitmaps of 1 MB and more keep one): the relink
+    kernel then finds its bitmaps clean and does not wipe them, and the update's walks undo their own marks."""
+    monkeypatch.setenv("HNSW_DEBUG_VLOG", "1")  # (read when the construction scratch is reserved: set before the build)
+    _update_case(pkg, oracle, *CASES[0])
 
 
 def test_upsert_is_update_then_append(pkg):

@@ -1,4 +1,4 @@
-// hnsw_graph_host.h -- the one host form of an HNSW graph: the device layout itself (hnsw_ann.hip: SearchArgs) plus one
+// hnsw_graph_host.h -- the one host form of an HNSW graph: the device layout itself (hnsw_walk.h: SearchArgs) plus one
 // "the reference's map holds the key HnswNode(level, item)" flag per row of storage.  A loaded graph is laid out into it, the
 // host builder's result is (hnsw_host_builder.h), an export is emitted from it.  Pure C++: tests/hnsw_graph_host_check.cpp
 // runs it under the sanitizers.
