@@ -180,7 +180,8 @@ struct ivf_index : IvfBase {
   // the lists' payload
   Buf lf, lbias;
   // per-call scratch: the queries, and the groups of a search
-  Buf qf, pstart, ngrp, gstart, groups;
+  Buf qf;
+  GroupTable gt;
 };
 
 namespace {
@@ -223,32 +224,14 @@ int build_coarse(ivf_index *ix, const float *d_cent, bool stored = false) {
 // itself; otherwise it writes the index's own and finish_chunk brings them to the host.
 int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
                  float *out_dist, int64_t *out_ids, int32_t *out_counts, bool out_on_device) {
-  const int d = ix->d, S = d >> 4, nlist = ix->nlist;
+  const int d = ix->d, S = d >> 4;
   hipStream_t st = 0;
   const int nq_pad = (nq + 31) / 32 * 32;
   ITRY(ix->qf.reserve((size_t)nq_pad * d * sizeof(_Float16) * 2));  // the fp16 rows, then the scan's fragments
-  ITRY(ix->pstart.reserve((size_t)nlist * 4));
-  ITRY(ix->ngrp.reserve((size_t)nlist * 4));
-  ITRY(ix->gstart.reserve((size_t)nlist * 4));
   _Float16 *q16 = ix->qf.as<_Float16>(), *qfrag = q16 + (size_t)nq_pad * d;
   if (int rc = probe_chunk(ix, q0, nq, queries, on_device, k, nprobe, q16, qfrag)) return rc;
-
-  // the pairs of a cell cut into groups of <= 32 queries
-  hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), nlist, 32u,
-                     ix->ngrp.as<uint32_t>());
-  ITRY(hipGetLastError());
-  if (int rc = exclusive_sum(ix, ix->per_cell.as<uint32_t>(), ix->pstart.as<uint32_t>(), nlist)) return rc;
-  if (int rc = exclusive_sum(ix, ix->ngrp.as<uint32_t>(), ix->gstart.as<uint32_t>(), nlist)) return rc;
-  uint32_t last[2] = {0, 0};
-  ITRY(hipMemcpy(&last[0], ix->gstart.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
-  ITRY(hipMemcpy(&last[1], ix->ngrp.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
-  const uint32_t n_groups = last[0] + last[1];
-  ix->last_ctl += 8;
-  ITRY(ix->groups.reserve((size_t)n_groups * sizeof(Group)));
-  hipLaunchKernelGGL(groups_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), ix->pstart.as<uint32_t>(),
-                     ix->gstart.as<uint32_t>(), ix->sizes.as<uint32_t>(), nlist, ix->groups.as<Group>(),
-                     ix->rows_acc.as<unsigned long long>());
-  ITRY(hipGetLastError());
+  if (int rc = build_groups(ix, ix->gt)) return rc;
+  const uint32_t n_groups = ix->gt.n_groups;
 
   // scan rounds
   ScanArgs a;
@@ -257,7 +240,7 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, bo
   a.boff = ix->boff.as<uint32_t>();
   a.nblk = ix->nblk.as<uint32_t>();
   a.qf = qfrag;
-  a.groups = ix->groups.as<Group>();
+  a.groups = ix->gt.groups.as<Group>();
   a.pair_q = ix->pair_q_s.as<uint32_t>();
   a.tau = ix->tau.as<float>();
   a.cnt = ix->cnt.as<uint32_t>();

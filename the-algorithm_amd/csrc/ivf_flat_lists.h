@@ -1,6 +1,8 @@
 // ivf_flat_lists.h -- the payload scatter and the select step of flat (fp16-row) lists, shared by the two indexes whose
 // lists hold rows as MFMA A fragments: ivf_ann.hip (cell = nearest centroid) and grouped_ann.hip (cell = the caller's
-// group).  A source includes this once, after ivf_core.h.  Everything is file-local.
+// group); and the group table of a search chunk, shared by ivf_ann.hip and ivfsq_ann.hip (whose lists hold code bytes in
+// the same fragment order and whose answers go through the same select step).  A source includes this once, after
+// ivf_core.h.  Everything is file-local.
 #pragma once
 #include "ivf_core.h"
 
@@ -29,6 +31,38 @@ __global__ void scatter_rows_kernel(const _Float16 *__restrict__ flat, const flo
     lbias[slot] = metric == IVF_METRIC_L2 ? -0.5f * sumsq[src] : 0.0f;
     lrank[slot] = rank;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the group table of a chunk, for the scans that run one workgroup per Group (ivf_ann.hip, ivfsq_ann.hip): after
+// probe_chunk, the pairs of a cell cut into groups of <= 32 queries; the rows scanned are counted into rows_acc.
+// ---------------------------------------------------------------------------------------------
+struct GroupTable {
+  Buf pstart, ngrp, gstart, groups;
+  uint32_t n_groups = 0;
+};
+int build_groups(IvfBase *ix, GroupTable &gt) {
+  const int nlist = ix->nlist;
+  hipStream_t st = 0;
+  ITRY(gt.pstart.reserve((size_t)nlist * 4));
+  ITRY(gt.ngrp.reserve((size_t)nlist * 4));
+  ITRY(gt.gstart.reserve((size_t)nlist * 4));
+  hipLaunchKernelGGL(blocks_of_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), nlist, 32u,
+                     gt.ngrp.as<uint32_t>());
+  ITRY(hipGetLastError());
+  if (int rc = exclusive_sum(ix, ix->per_cell.as<uint32_t>(), gt.pstart.as<uint32_t>(), nlist)) return rc;
+  if (int rc = exclusive_sum(ix, gt.ngrp.as<uint32_t>(), gt.gstart.as<uint32_t>(), nlist)) return rc;
+  uint32_t last[2] = {0, 0};
+  ITRY(hipMemcpy(&last[0], gt.gstart.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
+  ITRY(hipMemcpy(&last[1], gt.ngrp.as<uint32_t>() + (nlist - 1), 4, hipMemcpyDeviceToHost));
+  gt.n_groups = last[0] + last[1];
+  ix->last_ctl += 8;
+  ITRY(gt.groups.reserve((size_t)gt.n_groups * sizeof(Group)));
+  hipLaunchKernelGGL(groups_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(), gt.pstart.as<uint32_t>(),
+                     gt.gstart.as<uint32_t>(), ix->sizes.as<uint32_t>(), nlist, gt.groups.as<Group>(),
+                     ix->rows_acc.as<unsigned long long>());
+  ITRY(hipGetLastError());
+  return IVF_OK;
 }
 
 // per query: sort survivors by (score desc, rank in id order asc), emit the k nearest as distances (dense_ann.hip's select
