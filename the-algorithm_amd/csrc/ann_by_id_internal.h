@@ -12,8 +12,19 @@
 
 struct hnsw_index;
 struct dann_index;
+struct ann_store;
 
 namespace ann_by_id {
+
+// A built store as the by-id queries of the inverted-file family read it (faiss_by_id.hip): the (key, position) table sorted
+// by key and the fp32 rows [n][d], all on `device`.  The pointers live as long as the store.
+struct StoreView {
+  int device = 0, d = 0;
+  int64_t n = 0;
+  const int64_t *keys = nullptr, *kpos = nullptr;
+  const float *rows = nullptr;
+};
+int store_view(const ann_store *store, StoreView *out);
 
 // What the index shows of itself: where prepared queries go, and (own_keys) its rows and key -> position table as a producer.
 struct HnswTarget {

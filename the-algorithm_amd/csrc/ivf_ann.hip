@@ -222,14 +222,14 @@ int build_coarse(ivf_index *ix, const float *d_cent, bool stored = false) {
 
 // One chunk of a search.  out_on_device: out_dist / out_ids / out_counts are device buffers, which the select launch writes
 // itself; otherwise it writes the index's own and finish_chunk brings them to the host.
-int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
-                 float *out_dist, int64_t *out_ids, int32_t *out_counts, bool out_on_device) {
+int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, const int64_t *pos, int32_t k,
+                 int32_t nprobe, float *out_dist, int64_t *out_ids, int32_t *out_counts, bool out_on_device) {
   const int d = ix->d, S = d >> 4;
   hipStream_t st = 0;
   const int nq_pad = (nq + 31) / 32 * 32;
   ITRY(ix->qf.reserve((size_t)nq_pad * d * sizeof(_Float16) * 2));  // the fp16 rows, then the scan's fragments
   _Float16 *q16 = ix->qf.as<_Float16>(), *qfrag = q16 + (size_t)nq_pad * d;
-  if (int rc = probe_chunk(ix, q0, nq, queries, on_device, k, nprobe, q16, qfrag)) return rc;
+  if (int rc = probe_chunk(ix, q0, nq, queries, on_device, pos, k, nprobe, q16, qfrag)) return rc;
   if (int rc = build_groups(ix, ix->gt)) return rc;
   const uint32_t n_groups = ix->gt.n_groups;
 
@@ -265,14 +265,15 @@ int search_chunk(ivf_index *ix, int32_t q0, int32_t nq, const float *queries, bo
   return finish_chunk(ix, nq, k, rounds, out_dist, out_ids, out_counts);
 }
 
-// ivf_search, over host queries into host buffers or over device queries into device buffers
+// ivf_search, over host queries into host buffers or over device queries into device buffers; pos != NULL: the device
+// queries are the rows pos[0 .. nq) of the store whose first row is `queries` (probe_chunk), a chunk's positions at pos + q0
 int search_rows(ivf_index *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist, int64_t *out_ids,
-                int32_t *out_counts, bool on_device) {
+                int32_t *out_counts, bool on_device, const int64_t *pos = nullptr) {
   if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
   if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
   return search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
-    return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, out_dist + (size_t)q0 * k,
-                        out_ids + (size_t)q0 * k, out_counts + q0, on_device);
+    return search_chunk(ix, q0, m, pos ? queries : queries + (size_t)q0 * ix->d, on_device, pos ? pos + q0 : nullptr, k, nprobe,
+                        out_dist + (size_t)q0 * k, out_ids + (size_t)q0 * k, out_counts + q0, on_device);
   });
 }
 
@@ -343,8 +344,16 @@ int ivf_internal::search_device_out(ivf_index *ix, int32_t nq, const float *d_qu
 
 ivf_hq::State *ivf_internal::hnsw_quantizer(ivf_index *ix) { return hq_state(ix); }  // ivf_hnsw_quantizer_internal.h
 
+int ivf_internal::search_store_out(ivf_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k,
+                                   int32_t nprobe, float *d_dist, int64_t *d_ids, int32_t *d_counts) try {
+  if (!d_pos) return fail(IVF_EINVAL, "null argument");
+  return search_rows(ix, nq, d_store_rows, k, nprobe, d_dist, d_ids, d_counts, true, d_pos);
+} ABI_CATCH
+
 int ivf_internal::device_of(const ivf_index *ix) { return ix->device; }
 int64_t ivf_internal::last_control_bytes(const ivf_index *ix) { return ix->last_ctl; }
+int64_t ivf_internal::last_control_upload_bytes(const ivf_index *ix) { return ix->last_ctl_up; }
+std::shared_ptr<void> &ivf_internal::by_id_scratch(ivf_index *ix) { return ix->by_id; }
 
 // ---------------------------------------------------------------------------------------------
 // restoring a saved index (faiss_restore.h)

@@ -69,6 +69,8 @@ struct IvfBase {
   int64_t last_rows = 0;
   int64_t chunk_pairs = 0;  // the (cell, query) pairs of the last chunk that name a cell: all of them, but for a short walk
   int64_t last_ctl = 0;  // control bytes the search read back: round flags, row and group counts (never an answer)
+  int64_t last_ctl_up = 0;  // the part of last_ctl that went up instead: an HNSW quantizer's second-pass query list
+  std::shared_ptr<void> by_id;  // the by-id scratch of this index (faiss_by_id.hip), freed with it
   float t_coarse = 0, t_scan = 0, t_sel = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   RestoreState rs;  // faiss_restore.h
@@ -281,7 +283,7 @@ int search_begin(IvfBase *ix, int32_t nq, int32_t k, int32_t *nprobe) {
   ix->last_nprobe = *nprobe;
   ix->last_rows = 0;
   ix->last_rounds = 0;
-  ix->last_ctl = 0;
+  ix->last_ctl = ix->last_ctl_up = 0;
   ix->t_coarse = ix->t_scan = ix->t_sel = 0;
   ix->hq.evals = ix->hq.expansions = ix->hq.missing = 0;
   ix->hq.last_q_n = 0;
@@ -308,8 +310,11 @@ int search_chunks(IvfBase *ix, int32_t nq, Chunk chunk) {
 // with qfrag != NULL, the fragments of the flat scan; the coarse search for their nprobe nearest centroids; the probe
 // export; the (cell, query) pairs sorted by cell (pair_cell_s, pair_q_s) and the queries per cell (per_cell).  rows_acc is
 // zeroed for the caller's count of the rows scanned.
-int probe_chunk(IvfBase *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe, _Float16 *q16,
-                _Float16 *qfrag) {
+// The queries come from one of three places: nq host rows at `queries`; nq device rows there (on_device); or, with pos !=
+// NULL, rows of a device-resident store read through a position list (a by-id query, include/faiss_by_id.h): `queries` is
+// the store's first row and query i is its row pos[i], prepared by store_rows_pos_kernel with no fp32 copy in between.
+int probe_chunk(IvfBase *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, const int64_t *pos, int32_t k,
+                int32_t nprobe, _Float16 *q16, _Float16 *qfrag) {
   const int d = ix->d, nlist = ix->nlist;
   const int64_t np = (int64_t)nq * nprobe;
   hipStream_t st = 0;
@@ -345,8 +350,13 @@ int probe_chunk(IvfBase *ix, int32_t q0, int32_t nq, const float *queries, bool 
   // coarse: the nprobe nearest centroids of every query
   ITRY(hipEventRecord(ix->ev[0], st));
   if (!on_device) ITRY(hipMemcpyAsync(ix->stage.p, queries, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, on_device ? queries : ix->stage.as<float>(),
-                     (int64_t)nq, d, ix->metric == IVF_METRIC_COSINE ? 1 : 0, q16, ix->qsumsq.as<float>());
+  if (pos) {
+    hipLaunchKernelGGL(store_rows_pos_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, queries, pos, (int64_t)nq, d,
+                       ix->metric == IVF_METRIC_COSINE ? 1 : 0, q16, ix->qsumsq.as<float>());
+  } else {
+    hipLaunchKernelGGL(store_rows_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, on_device ? queries : ix->stage.as<float>(),
+                       (int64_t)nq, d, ix->metric == IVF_METRIC_COSINE ? 1 : 0, q16, ix->qsumsq.as<float>());
+  }
   ITRY(hipGetLastError());
   if (!walk || qfrag) {
     hipLaunchKernelGGL(frag_rows_kernel, dim3(blocks_for((int64_t)nq * (d >> 3))), dim3(256), 0, st, q16, ix->qsumsq.as<float>(), nq, d,
@@ -362,6 +372,7 @@ int probe_chunk(IvfBase *ix, int32_t q0, int32_t nq, const float *queries, bool 
     ann_by_id::DeviceResult res;
     HQCALL(ann_by_id::hnsw_search_prepared(ix->hq.graph, nq, nprobe, ix->hq.ef, &res));
     ix->last_ctl += res.h2d_bytes + res.d2h_bytes;
+    ix->last_ctl_up += res.h2d_bytes;
     int64_t evals = 0, expansions = 0;
     HQCALL(hnsw_last_stats(ix->hq.graph, &evals, &expansions, nullptr, nullptr));
     ix->hq.evals += evals;

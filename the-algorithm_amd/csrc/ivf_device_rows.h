@@ -1,4 +1,5 @@
-// ivf_device_rows.h -- the seam between the OPQ pre-transform (opq_ann.hip) and the two inverted-file indexes.
+// ivf_device_rows.h -- the seam between the OPQ pre-transform (opq_ann.hip), the shard set (shard_set.hip), the by-id queries
+// (faiss_by_id.hip) and the inverted-file indexes.
 //
 // ivf_index_train, ivfpq_index_train, ivfpq_index_add and ivfpq_search are each "bring host rows to the device" followed
 // by work on device rows; the second halves are the functions below, which the public entry points share with
@@ -9,9 +10,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 
 struct ivf_index;
 struct ivfpq_index;
+struct ivfsq_index;
+struct shardset;
 
 namespace ivf_internal __attribute__((visibility("hidden"))) {
 
@@ -24,11 +28,35 @@ int train_device(int32_t device, int32_t metric, int32_t d, int32_t nlist, int64
 // words (round flags, the rows counter, the two group counts) leaves the device.  The bytes are ivf_search's.
 int search_device_out(ivf_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *d_dist, int64_t *d_ids,
                       int32_t *d_counts);
+// search_device_out over rows of a device-resident store read through a position list: query i is the fp32 row
+// d_store_rows + d_pos[i] * d (a by-id query, include/faiss_by_id.h; every position is inside the store).  The rows are
+// prepared where they lie (ivf_kernels.h: store_rows_pos_kernel), with no fp32 copy in between; the bytes are ivf_search's
+// over a copy of the rows.  The same entry exists below for every member of the family.
+int search_store_out(ivf_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k, int32_t nprobe,
+                     float *d_dist, int64_t *d_ids, int32_t *d_counts);
 int device_of(const ivf_index *ix);
-// the control bytes the last search read back (answers not counted)
+// the control bytes the last search moved (answers not counted), and the part of them that went up (an HNSW quantizer's
+// second-pass query list; 0 for the exhaustive quantizer)
 int64_t last_control_bytes(const ivf_index *ix);
+int64_t last_control_upload_bytes(const ivf_index *ix);
+std::shared_ptr<void> &by_id_scratch(ivf_index *ix);  // the by-id scratch of this index (freed with it)
 
 }  // namespace ivf_internal
+
+namespace ivfsq_internal __attribute__((visibility("hidden"))) {
+
+// ivfsq_search over queries that are on the device, or over rows of a store (as ivf_internal's two above), the answer left
+// in the caller's device buffers.
+int search_device_out(ivfsq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *d_dist, int64_t *d_ids,
+                      int32_t *d_counts);
+int search_store_out(ivfsq_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k, int32_t nprobe,
+                     float *d_dist, int64_t *d_ids, int32_t *d_counts);
+int device_of(const ivfsq_index *ix);
+int64_t last_control_bytes(const ivfsq_index *ix);
+int64_t last_control_upload_bytes(const ivfsq_index *ix);
+std::shared_ptr<void> &by_id_scratch(ivfsq_index *ix);
+
+}  // namespace ivfsq_internal
 
 namespace ivfpq_internal __attribute__((visibility("hidden"))) {
 
@@ -60,7 +88,11 @@ int search_device_ht(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_
 // search_device_ht with the answer left in the caller's device buffers, as ivf_internal::search_device_out leaves it.
 int search_device_out(ivfpq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht, float *d_dist,
                       int64_t *d_ids, int32_t *d_counts);
+int search_store_out(ivfpq_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k, int32_t nprobe,
+                     int32_t ht, float *d_dist, int64_t *d_ids, int32_t *d_counts);
 int64_t last_control_bytes(const ivfpq_index *ix);
+int64_t last_control_upload_bytes(const ivfpq_index *ix);
+std::shared_ptr<void> &by_id_scratch(ivfpq_index *ix);
 
 // After a search_device that stood in for a search with ht <= 0: every scanned row counts as scored (ivfpq_last_ht_stats).
 int search_stats_unfiltered(ivfpq_index *ix);
@@ -100,7 +132,31 @@ int search_positions(opq_index *ix, int32_t nq, const float *d_queries, int32_t 
 // in the caller's device buffers as ivf_internal::search_device_out leaves it.
 int search_device_out(opq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, int32_t ht, float *d_dist,
                       int64_t *d_ids, int32_t *d_counts);
+// search_device_out over rows of a store [.][d_in] read through a position list: the transform's tile load goes through
+// the list (opq_transform_kernel<true>), its output feeds the inner index's device search as above.
+int search_store_out(opq_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k, int32_t nprobe,
+                     int32_t ht, float *d_dist, int64_t *d_ids, int32_t *d_counts);
 int device_of(const opq_index *ix);
 int64_t last_control_bytes(const opq_index *ix);
+int64_t last_control_upload_bytes(const opq_index *ix);
+std::shared_ptr<void> &by_id_scratch(opq_index *ix);
 
 }  // namespace opq_internal
+
+namespace shardset_internal __attribute__((visibility("hidden"))) {
+
+// shardset_search over rows of a store [.][dimension] read through a position list, the answer left in the caller's device
+// buffers d_dist / d_ids [nq][k] and d_counts [nq]: a chunk's rows are copied once into the set's query buffer, in the
+// layout shardset_search uploads, and every member searches them there.  Refuses what shardset_search refuses; the
+// set's last stats describe this search (its upload is 0).
+int search_store_out(shardset *set, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k, int32_t nprobe,
+                     int32_t ht, float *d_dist, int64_t *d_ids, int32_t *d_counts);
+// ht > 0 with an IVF-Flat member: the refusal of shardset_search, before any device work
+int check_ht(const shardset *set, int32_t ht);
+int device_of(const shardset *set);
+int dimension_of(const shardset *set);
+int64_t last_control_bytes(const shardset *set);
+int64_t last_control_upload_bytes(const shardset *set);
+std::shared_ptr<void> &by_id_scratch(shardset *set);
+
+}  // namespace shardset_internal

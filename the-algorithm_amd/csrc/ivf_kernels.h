@@ -31,12 +31,9 @@ struct Group {
 // rows (fp32, row-major) -> fp16 rows (row-major) and the sum of squares of the stored halves.  One wave per row; the
 // arithmetic of dense_ann.hip's prep_rows_kernel (Cosine: divide by the fp32 norm, then round).
 // ---------------------------------------------------------------------------------------------
-__global__ void store_rows_kernel(const float *__restrict__ src, int64_t n, int d, int normalise, _Float16 *__restrict__ flat,
-                                  float *__restrict__ sumsq) {
-  int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float *x = src + row * d;
+// The preparation of one row by one wave: x is the row's d fp32 values, wherever they lie; flat / sumsq as below.
+__device__ __forceinline__ void store_row(const float *__restrict__ x, int64_t row, int d, int normalise, int lane,
+                                          _Float16 *__restrict__ flat, float *__restrict__ sumsq) {
   double ss = 0;
   for (int k = lane; k < d; k += 64) ss += (double)x[k] * (double)x[k];
   ss = wave_sum(ss);
@@ -54,6 +51,33 @@ __global__ void store_rows_kernel(const float *__restrict__ src, int64_t n, int 
   }
   ss16 = wave_sum(ss16);
   if (lane == 0) sumsq[row] = (float)ss16;
+}
+__global__ void store_rows_kernel(const float *__restrict__ src, int64_t n, int d, int normalise, _Float16 *__restrict__ flat,
+                                  float *__restrict__ sumsq) {
+  int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  int lane = threadIdx.x & 63;
+  if (row >= n) return;
+  store_row(src + row * d, row, d, normalise, lane, flat, sumsq);
+}
+// store_rows_kernel over a position list: row i is rows + pos[i] * d (a by-id query's embedding in the store,
+// include/faiss_by_id.h).  The row is gathered into LDS with 16-byte loads (d is a multiple of 16 here, hipMalloc's alignment
+// does the rest), and from there store_row runs as above: every lane sums the elements lane, lane + 64, ... it sums there, in
+// that order, so flat and sumsq are the bytes store_rows_kernel gives for a copy of the row.  256 threads, one wave per row;
+// every position is in the store (the resolve step's, compacted).
+__global__ __launch_bounds__(256) void store_rows_pos_kernel(const float *__restrict__ rows, const int64_t *__restrict__ pos, int64_t n,
+                                                             int d, int normalise, _Float16 *__restrict__ flat,
+                                                             float *__restrict__ sumsq) {
+  __shared__ __attribute__((aligned(16))) float stage[4][MAX_D];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + w;
+  float *x = stage[w];
+  if (row < n) {
+    const float4 *s4 = (const float4 *)(rows + pos[row] * d);
+    for (int c = lane; c < (d >> 2); c += 64) ((float4 *)x)[c] = s4[c];
+  }
+  __syncthreads();
+  if (row >= n) return;
+  store_row(x, row, d, normalise, lane, flat, sumsq);
 }
 
 // fp16 rows -> the B-operand fragments of a query chunk: the coarse search's (S_c k-steps, zeroed by dann_chunk_open) and,

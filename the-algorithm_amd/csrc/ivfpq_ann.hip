@@ -569,12 +569,13 @@ int train_codebooks(ivfpq_index *ix, const _Float16 *tflat, const float *tsumsq,
 
 // One chunk of a search.  out_on_device (without po): out_dist / out_ids / out_counts are device buffers, which the select
 // launch writes itself; otherwise it writes the index's own and finish_chunk brings them to the host.
-int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe,
-                 float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po, int32_t ht, bool out_on_device) {
+int search_chunk(ivfpq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, const int64_t *pos, int32_t k,
+                 int32_t nprobe, float *out_dist, int64_t *out_ids, int32_t *out_counts, const PosOut *po, int32_t ht,
+                 bool out_on_device) {
   const int d = ix->d, nlist = ix->nlist;
   hipStream_t st = 0;
   ITRY(ix->q16.reserve((size_t)nq * d * sizeof(_Float16)));
-  if (int rc = probe_chunk(ix, q0, nq, queries, on_device, k, nprobe, ix->q16.as<_Float16>(), nullptr)) return rc;
+  if (int rc = probe_chunk(ix, q0, nq, queries, on_device, pos, k, nprobe, ix->q16.as<_Float16>(), nullptr)) return rc;
   // one workgroup per pair that names a cell: all nq * nprobe of them, but for an HNSW quantizer's short walks (ivf_core.h)
   const int64_t pairs = ix->chunk_pairs;
   hipLaunchKernelGGL(rows_scanned_kernel, dim3(blocks_for(nlist)), dim3(256), 0, st, ix->per_cell.as<uint32_t>(),
@@ -732,9 +733,12 @@ int train_rows_polysemous(int32_t device, int32_t metric, int32_t d, int32_t nli
   return IVF_OK;
 }
 
-// ivfpq_search, over host queries or over queries that are on the device; out_on_device: the three outputs are device buffers
+// ivfpq_search, over host queries or over queries that are on the device; out_on_device: the three outputs are device buffers;
+// pos != NULL: the device queries are the rows pos[0 .. nq) of the store whose first row is `queries` (probe_chunk), a
+// chunk's positions at pos + q0
 int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_device, int32_t k, int32_t nprobe, float *out_dist,
-                int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr, int32_t ht = 0, bool out_on_device = false) {
+                int64_t *out_ids, int32_t *out_counts, const PosOut *po = nullptr, int32_t ht = 0, bool out_on_device = false,
+                const int64_t *pos = nullptr) {
   if (!ix || !queries) return fail(IVF_EINVAL, "null argument");
   if (po ? !po->pos || !po->rank || !po->cnt : !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
   if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
@@ -746,7 +750,8 @@ int search_rows(ivfpq_index_t *ix, int32_t nq, const float *queries, bool on_dev
     ITRY(hipMemset(ix->scored_acc.p, 0, 8));
   }
   if (int rc = search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
-        return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, on_device, k, nprobe, po ? nullptr : out_dist + (size_t)q0 * k,
+        return search_chunk(ix, q0, m, pos ? queries : queries + (size_t)q0 * ix->d, on_device, pos ? pos + q0 : nullptr, k, nprobe,
+                            po ? nullptr : out_dist + (size_t)q0 * k,
                             po ? nullptr : out_ids + (size_t)q0 * k, po ? nullptr : out_counts + q0, po, ht, out_on_device);
       }))
     return rc;
@@ -837,7 +842,18 @@ int ivfpq_internal::search_device_out(ivfpq_index *ix, int32_t nq, const float *
   return IVF_OK;
 } ABI_CATCH
 
+int ivfpq_internal::search_store_out(ivfpq_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k,
+                                     int32_t nprobe, int32_t ht, float *d_dist, int64_t *d_ids, int32_t *d_counts) try {
+  if (!d_pos) return fail(IVF_EINVAL, "null argument");
+  if (int rc = search_rows(ix, nq, d_store_rows, true, k, nprobe, d_dist, d_ids, d_counts, nullptr, std::max(ht, 0), true, d_pos))
+    return rc;
+  if (ht <= 0) ix->last_scored = ix->last_rows;
+  return IVF_OK;
+} ABI_CATCH
+
 int64_t ivfpq_internal::last_control_bytes(const ivfpq_index *ix) { return ix->last_ctl; }
+int64_t ivfpq_internal::last_control_upload_bytes(const ivfpq_index *ix) { return ix->last_ctl_up; }
+std::shared_ptr<void> &ivfpq_internal::by_id_scratch(ivfpq_index *ix) { return ix->by_id; }
 
 int ivfpq_internal::search_stats_unfiltered(ivfpq_index *ix) {
   if (!ix) return fail(IVF_EINVAL, "null index");

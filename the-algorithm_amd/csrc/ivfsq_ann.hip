@@ -44,6 +44,7 @@
 #include "../../include/ivf_ann.h"
 #include "../../include/ivfsq_ann.h"
 #include "ivf_core.h"
+#include "ivf_device_rows.h"
 #include "ivf_flat_lists.h"
 
 namespace {
@@ -365,16 +366,18 @@ int train_ranges(ivfsq_index *ix, const _Float16 *tflat, int64_t n, std::vector<
   return IVF_OK;
 }
 
-// One chunk of a search.
-int search_chunk(ivfsq_index *ix, int32_t q0, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist,
-                 int64_t *out_ids, int32_t *out_counts) {
+// One chunk of a search.  on_device / pos: where the queries are (probe_chunk).  out_on_device: out_dist / out_ids /
+// out_counts are device buffers, which the select launch writes itself; otherwise it writes the index's own and
+// finish_chunk brings them to the host.
+int search_chunk(ivfsq_index *ix, int32_t q0, int32_t nq, const float *queries, bool on_device, const int64_t *pos, int32_t k,
+                 int32_t nprobe, float *out_dist, int64_t *out_ids, int32_t *out_counts, bool out_on_device) {
   const int d = ix->d, S = d >> 4;
   hipStream_t st = 0;
   const int nq_pad = (nq + 31) / 32 * 32;
   ITRY(ix->q16.reserve((size_t)nq * d * sizeof(_Float16)));
   ITRY(ix->sfrag.reserve((size_t)nq_pad * d * sizeof(_Float16)));
   ITRY(ix->bq.reserve((size_t)nq * sizeof(float)));
-  if (int rc = probe_chunk(ix, q0, nq, queries, false, k, nprobe, ix->q16.as<_Float16>(), nullptr)) return rc;
+  if (int rc = probe_chunk(ix, q0, nq, queries, on_device, pos, k, nprobe, ix->q16.as<_Float16>(), nullptr)) return rc;
   hipLaunchKernelGGL(sq_query_kernel, dim3(blocks_for(nq, 4)), dim3(256), 0, st, ix->q16.as<_Float16>(), nq, d, ix->vmin.as<float>(),
                      ix->step.as<float>(), ix->sfrag.as<_Float16>(), ix->bq.as<float>());
   ITRY(hipGetLastError());
@@ -407,12 +410,45 @@ int search_chunk(ivfsq_index *ix, int32_t q0, int32_t nq, const float *queries, 
 
   hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(512), SELECT_LDS, st, ix->surv.as<Survivor>(), ix->done_cnt.as<uint32_t>(),
                      ix->qsumsq.as<float>(), ix->lrank.as<uint32_t>(), ix->ids_sorted.as<int64_t>(), ix->metric, k,
-                     ix->o_dist.as<float>(), ix->o_ids.as<int64_t>(), ix->o_cnt.as<int32_t>());
+                     out_on_device ? out_dist : ix->o_dist.as<float>(), out_on_device ? out_ids : ix->o_ids.as<int64_t>(),
+                     out_on_device ? out_counts : ix->o_cnt.as<int32_t>());
   ITRY(hipGetLastError());
+  if (out_on_device) return finish_chunk(ix, nq, k, rounds, nullptr, nullptr, nullptr);
   return finish_chunk(ix, nq, k, rounds, out_dist, out_ids, out_counts);
 }
 
+// ivfsq_search, over host queries into host buffers or over device queries into device buffers; pos != NULL: the device
+// queries are the rows pos[0 .. nq) of the store whose first row is `queries` (probe_chunk), a chunk's positions at pos + q0
+int search_rows(ivfsq_index *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist, int64_t *out_ids,
+                int32_t *out_counts, bool on_device, const int64_t *pos = nullptr) {
+  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+  if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
+  return search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
+    return search_chunk(ix, q0, m, pos ? queries : queries + (size_t)q0 * ix->d, on_device, pos ? pos + q0 : nullptr, k, nprobe,
+                        out_dist + (size_t)q0 * k, out_ids + (size_t)q0 * k, out_counts + q0, on_device);
+  });
+}
+
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// the device-rows seam (ivf_device_rows.h)
+// ---------------------------------------------------------------------------------------------
+int ivfsq_internal::search_device_out(ivfsq_index *ix, int32_t nq, const float *d_queries, int32_t k, int32_t nprobe, float *d_dist,
+                                      int64_t *d_ids, int32_t *d_counts) try {
+  return search_rows(ix, nq, d_queries, k, nprobe, d_dist, d_ids, d_counts, true);
+} ABI_CATCH
+
+int ivfsq_internal::search_store_out(ivfsq_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k,
+                                     int32_t nprobe, float *d_dist, int64_t *d_ids, int32_t *d_counts) try {
+  if (!d_pos) return fail(IVF_EINVAL, "null argument");
+  return search_rows(ix, nq, d_store_rows, k, nprobe, d_dist, d_ids, d_counts, true, d_pos);
+} ABI_CATCH
+
+int ivfsq_internal::device_of(const ivfsq_index *ix) { return ix->device; }
+int64_t ivfsq_internal::last_control_bytes(const ivfsq_index *ix) { return ix->last_ctl; }
+int64_t ivfsq_internal::last_control_upload_bytes(const ivfsq_index *ix) { return ix->last_ctl_up; }
+std::shared_ptr<void> &ivfsq_internal::by_id_scratch(ivfsq_index *ix) { return ix->by_id; }
 
 extern "C" {
 
@@ -498,12 +534,7 @@ int ivfsq_index_add(ivfsq_index_t *ix, int64_t n, const float *vectors, const in
 
 int ivfsq_search(ivfsq_index_t *ix, int32_t nq, const float *queries, int32_t k, int32_t nprobe, float *out_dist, int64_t *out_ids,
                  int32_t *out_counts) try {
-  if (!ix || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
-  if (int rc = search_begin(ix, nq, k, &nprobe)) return rc;
-  return search_chunks(ix, nq, [&](int32_t q0, int32_t m) -> int {
-    return search_chunk(ix, q0, m, queries + (size_t)q0 * ix->d, k, nprobe, out_dist + (size_t)q0 * k, out_ids + (size_t)q0 * k,
-                        out_counts + q0);
-  });
+  return search_rows(ix, nq, queries, k, nprobe, out_dist, out_ids, out_counts, false);
 } ABI_CATCH
 
 int ivfsq_index_info(const ivfsq_index_t *ix, int64_t *n, int32_t *d, int32_t *metric, int32_t *nlist) try {

@@ -68,9 +68,13 @@ __device__ __forceinline__ float row_norm(const float *__restrict__ x, int d, in
 }
 
 // Y[row][j] = the FMA chain over i ascending of A[j][i] * x[row][i] (x divided by its norm first when normalise).
-// grid (row tiles, output tiles), 256 threads.
-__global__ __launch_bounds__(256) void opq_transform_kernel(const float *__restrict__ A, const float *__restrict__ X, int64_t n,
-                                                            int d_in, int d_out, int normalise, float *__restrict__ Y) {
+// grid (row tiles, output tiles), 256 threads.  POS: row r of the input is X + pos[r] * d_in -- a row of a device-resident
+// store read through a position list (a by-id query, include/faiss_by_id.h); the norms and the tile load go through the
+// list, everything after the load is the same statement, so Y is what the plain kernel gives for a copy of those rows.
+template <bool POS>
+__global__ __launch_bounds__(256) void opq_transform_kernel(const float *__restrict__ A, const float *__restrict__ X,
+                                                            const int64_t *__restrict__ pos, int64_t n, int d_in, int d_out,
+                                                            int normalise, float *__restrict__ Y) {
   __shared__ __attribute__((aligned(16))) float s_x[KS][LDT];
   __shared__ __attribute__((aligned(16))) float s_a[KS][LDT];
   __shared__ float s_norm[TR];
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(256) void opq_transform_kernel(const float *__restr
   if (normalise) {
     for (int r = w; r < TR; r += 4) {  // (row0 + r < n is the same for every lane of the wave)
       float norm = 1.0f;
-      if (row0 + r < n) norm = row_norm(X + (size_t)(row0 + r) * d_in, d_in, lane);
+      if (row0 + r < n) norm = row_norm(X + (size_t)(POS ? pos[row0 + r] : row0 + r) * d_in, d_in, lane);
       if (lane == 0) s_norm[r] = norm;
     }
     __syncthreads();
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(256) void opq_transform_kernel(const float *__restr
       float xv = 0.0f, av = 0.0f;
       if (kk < kmax) {
         if (row0 + r < n) {
-          xv = X[(size_t)(row0 + r) * d_in + i0 + kk];
+          xv = X[(size_t)(POS ? pos[row0 + r] : row0 + r) * d_in + i0 + kk];
           if (normalise) xv = xv / s_norm[r];
         }
         if (j0 + r < d_out) av = A[(size_t)(j0 + r) * d_in + i0 + kk];
@@ -335,6 +339,7 @@ struct opq_index {
   std::vector<double> err;
   float tr_transform = 0, tr_pq = 0, tr_corr = 0, tr_proc = 0, tr_inner = 0;  // the training
   Buf stage, y;                                                               // per-call scratch
+  std::shared_ptr<void> by_id;                                                // the by-id scratch (faiss_by_id.hip)
   float t_transform = 0;                                                      // the last search
   hipEvent_t ev[2] = {nullptr, nullptr};
   ~opq_index() {
@@ -379,11 +384,17 @@ int set_matrix(opq_index *ix, const float *A) {
   return IVF_OK;
 }
 
-// n device rows [n][d_in] -> [n][d_out] by the matrix of the index
-int transform(opq_index *ix, const float *d_x, int64_t n, bool normalise, float *d_y, hipStream_t st = 0) {
+// n device rows [n][d_in] -> [n][d_out] by the matrix of the index; d_pos != NULL: row r is d_x + d_pos[r] * d_in
+int transform(opq_index *ix, const float *d_x, int64_t n, bool normalise, float *d_y, hipStream_t st = 0,
+              const int64_t *d_pos = nullptr) {
   if (n == 0) return IVF_OK;
-  hipLaunchKernelGGL(opq_transform_kernel, dim3(blocks_for(n, TR), blocks_for(ix->d_out, TJ)), dim3(256), 0, st, ix->A.as<float>(),
-                     d_x, n, ix->d_in, ix->d_out, normalise ? 1 : 0, d_y);
+  const dim3 grid(blocks_for(n, TR), blocks_for(ix->d_out, TJ));
+  if (d_pos)
+    hipLaunchKernelGGL(opq_transform_kernel<true>, grid, dim3(256), 0, st, ix->A.as<float>(), d_x, d_pos, n, ix->d_in, ix->d_out,
+                       normalise ? 1 : 0, d_y);
+  else
+    hipLaunchKernelGGL(opq_transform_kernel<false>, grid, dim3(256), 0, st, ix->A.as<float>(), d_x, (const int64_t *)nullptr, n,
+                       ix->d_in, ix->d_out, normalise ? 1 : 0, d_y);
   ITRY(hipGetLastError());
   return IVF_OK;
 }
@@ -519,15 +530,16 @@ int opq_internal::add_slab(opq_index *ix, int64_t r0, int64_t m, const float *d_
 } ABI_CATCH
 
 namespace {
-// the first half of a search over device queries [nq][d_in]: prepared and transformed where they lie into ix->y, timed
-int transform_queries(opq_index *ix, const float *d_queries, int32_t nq) {
+// the first half of a search over device queries [nq][d_in]: prepared and transformed where they lie into ix->y, timed;
+// d_pos != NULL: query i is row d_pos[i] of the store whose first row is d_queries
+int transform_queries(opq_index *ix, const float *d_queries, int32_t nq, const int64_t *d_pos = nullptr) {
   if (!ix || !d_queries) return fail(IVF_EINVAL, "null argument");
   if (nq < 1) return fail(IVF_EINVAL, "nq must be positive");
   ITRY(hipSetDevice(ix->device));
   ix->t_transform = 0;
   ITRY(ix->y.reserve((size_t)nq * ix->d_out * sizeof(float)));
   ITRY(hipEventRecord(ix->ev[0], 0));
-  if (int rc = transform(ix, d_queries, nq, ix->metric == IVF_METRIC_COSINE, ix->y.as<float>())) return rc;
+  if (int rc = transform(ix, d_queries, nq, ix->metric == IVF_METRIC_COSINE, ix->y.as<float>(), 0, d_pos)) return rc;
   ITRY(hipEventRecord(ix->ev[1], 0));
   ITRY(hipDeviceSynchronize());
   float ms = 0;
@@ -551,8 +563,18 @@ int opq_internal::search_device_out(opq_index *ix, int32_t nq, const float *d_qu
   return IVF_OK;
 } ABI_CATCH
 
+int opq_internal::search_store_out(opq_index *ix, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k,
+                                   int32_t nprobe, int32_t ht, float *d_dist, int64_t *d_ids, int32_t *d_counts) try {
+  if (!d_pos) return fail(IVF_EINVAL, "null argument");
+  if (int rc = transform_queries(ix, d_store_rows, nq, d_pos)) return rc;
+  PCALL(ivfpq_internal::search_device_out(ix->inner, nq, ix->y.as<float>(), k, nprobe, ht, d_dist, d_ids, d_counts));
+  return IVF_OK;
+} ABI_CATCH
+
 int opq_internal::device_of(const opq_index *ix) { return ix->device; }
 int64_t opq_internal::last_control_bytes(const opq_index *ix) { return ivfpq_internal::last_control_bytes(ix->inner); }
+int64_t opq_internal::last_control_upload_bytes(const opq_index *ix) { return ivfpq_internal::last_control_upload_bytes(ix->inner); }
+std::shared_ptr<void> &opq_internal::by_id_scratch(opq_index *ix) { return ix->by_id; }
 
 namespace {
 int train_index(int32_t device, int32_t metric, int32_t d_in, int32_t d_out, int32_t nlist, int32_t M, int64_t n_train,

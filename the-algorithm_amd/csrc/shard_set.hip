@@ -18,6 +18,9 @@
 //     b.id)) for every distance that is not NaN.  The network is sized to the next power of two >= the entries the
 //     workgroup's queries really hold, not to k + k_in.  For small k a workgroup takes several queries side by side: a
 //     bitonic network whose every merge starts with a mirrored step sorts all its aligned segments ascending at once.
+//   * A by-id search (include/faiss_by_id.h, through shardset_internal::search_store_out) differs in the two ends of a chunk
+//     alone: gather_rows_kernel copies the chunk's rows out of the device-resident store into the query buffer instead of the
+//     upload, and the running answer is copied device to device into the caller's buffers instead of the download.
 //   * shardset_compose is the same kernel over host runs: the runs of one shard are uploaded and folded, shard by shard.
 #include <hip/hip_runtime.h>
 
@@ -171,6 +174,19 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_kernel(FoldArgs a) {
   }
 }
 
+// rows [m][d] of a device-resident store read through a position list -> the set's query buffer, the layout a search
+// uploads.  One thread per 16-byte piece when d is a multiple of 4 (hipMalloc's alignment does the rest), else per float.
+__global__ void gather_rows_kernel(const float *__restrict__ rows, const int64_t *__restrict__ pos, int64_t m, int d, int vec,
+                                   float *__restrict__ out) {
+  const int per = vec ? d >> 2 : d;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= m * per) return;
+  const int64_t r = e / per;
+  const int c = (int)(e - r * per);
+  if (vec) ((float4 *)(out + r * d))[c] = ((const float4 *)(rows + pos[r] * d))[c];
+  else out[r * d + c] = rows[pos[r] * d + c];
+}
+
 // the running answer of a chunk: two (dist, ids, cnt) buffers that swap roles at every fold
 struct Running {
   Buf dist[2], ids[2], cnt[2];
@@ -220,6 +236,19 @@ struct Running {
     ITRY(hipMemcpy(out_counts, cnt[cur].p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
     return IVF_OK;
   }
+  // the answer of the chunk -> the caller's device buffers; with nothing folded: counts 0
+  int copy_out(int32_t nq, int32_t k, float *d_dist, int64_t *d_ids, int32_t *d_counts) {
+    if (cur < 0) {
+      ITRY(hipMemset(d_dist, 0, (size_t)nq * k * sizeof(float)));
+      ITRY(hipMemset(d_ids, 0, (size_t)nq * k * sizeof(int64_t)));
+      ITRY(hipMemset(d_counts, 0, (size_t)nq * sizeof(int32_t)));
+      return IVF_OK;
+    }
+    ITRY(hipMemcpy(d_dist, dist[cur].p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToDevice));
+    ITRY(hipMemcpy(d_ids, ids[cur].p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToDevice));
+    ITRY(hipMemcpy(d_counts, cnt[cur].p, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToDevice));
+    return IVF_OK;
+  }
 };
 
 struct Member {
@@ -235,8 +264,9 @@ struct shardset {
   Buf dq, a_dist, a_ids, a_cnt;
   Running run;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  int64_t h2d = 0, d2h_ctl = 0, d2h_res = 0;
+  int64_t h2d = 0, d2h_ctl = 0, d2h_res = 0, ctl_up = 0;  // (ctl_up: the part of d2h_ctl that went up, ivf_device_rows.h)
   float t_search = 0, t_fold = 0;
+  std::shared_ptr<void> by_id;  // the by-id scratch of this set (faiss_by_id.hip), freed with it
   ~shardset() {
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -279,28 +309,33 @@ int member_search(shardset *s, size_t i, int32_t nq, int32_t k, int32_t nprobe, 
   const float *q = s->dq.as<float>();
   int rc;
   const char *msg;
-  int64_t ctl;
+  int64_t ctl, up;
   if (m.kind == FAISS_KIND_IVF_FLAT) {
     rc = ivf_internal::search_device_out((ivf_index_t *)m.h, nq, q, k, nprobe, dd, di, dc);
     msg = ivf_last_error();
     ctl = ivf_internal::last_control_bytes((ivf_index_t *)m.h);
+    up = ivf_internal::last_control_upload_bytes((ivf_index_t *)m.h);
   } else if (m.kind == FAISS_KIND_IVF_PQ) {
     rc = ivfpq_internal::search_device_out((ivfpq_index_t *)m.h, nq, q, k, nprobe, ht, dd, di, dc);
     msg = ivfpq_last_error();
     ctl = ivfpq_internal::last_control_bytes((ivfpq_index_t *)m.h);
+    up = ivfpq_internal::last_control_upload_bytes((ivfpq_index_t *)m.h);
   } else {
     rc = opq_internal::search_device_out((opq_index_t *)m.h, nq, q, k, nprobe, ht, dd, di, dc);
     msg = opq_last_error();
     ctl = opq_internal::last_control_bytes((opq_index_t *)m.h);
+    up = opq_internal::last_control_upload_bytes((opq_index_t *)m.h);
   }
   if (rc) return fail(rc, "member " + std::to_string(i) + ": " + msg);
   s->d2h_ctl += ctl;
+  s->ctl_up += up;
   return IVF_OK;
 }
 
-// one chunk of <= CHUNK queries: upload, every member's search and fold, download
-int search_chunk(shardset *s, int32_t nq, const float *queries, int32_t k, int32_t nprobe, int32_t ht, float *out_dist, int64_t *out_ids,
-                 int32_t *out_counts) {
+// one chunk of <= CHUNK queries: upload (or, with pos, the gather out of the store whose first row is `queries`), every
+// member's search and fold, download (or, with out_on_device, the copy into the caller's device buffers)
+int search_chunk(shardset *s, int32_t nq, const float *queries, const int64_t *pos, int32_t k, int32_t nprobe, int32_t ht,
+                 float *out_dist, int64_t *out_ids, int32_t *out_counts, bool out_on_device) {
   hipStream_t st = 0;
   const size_t qbytes = (size_t)nq * s->dimension * sizeof(float);
   ITRY(s->dq.reserve(qbytes));
@@ -308,8 +343,16 @@ int search_chunk(shardset *s, int32_t nq, const float *queries, int32_t k, int32
   ITRY(s->a_ids.reserve((size_t)nq * k * sizeof(int64_t)));
   ITRY(s->a_cnt.reserve((size_t)nq * sizeof(int32_t)));
   if (int rc = s->run.reserve(nq, k)) return rc;
-  ITRY(hipMemcpy(s->dq.p, queries, qbytes, hipMemcpyHostToDevice));
-  s->h2d += (int64_t)qbytes;
+  if (pos) {
+    const int d = s->dimension, vec = d % 4 == 0 ? 1 : 0;
+    const int64_t pieces = (int64_t)nq * (vec ? d >> 2 : d);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, queries, pos, (int64_t)nq, d, vec,
+                       s->dq.as<float>());
+    ITRY(hipGetLastError());
+  } else {
+    ITRY(hipMemcpy(s->dq.p, queries, qbytes, hipMemcpyHostToDevice));
+    s->h2d += (int64_t)qbytes;
+  }
   for (size_t i = 0; i < s->members.size(); ++i) {
     ITRY(hipEventRecord(s->ev[0], st));
     if (int rc = member_search(s, i, nq, k, nprobe, ht)) return rc;
@@ -323,12 +366,52 @@ int search_chunk(shardset *s, int32_t nq, const float *queries, int32_t k, int32
     s->t_search += ts;
     s->t_fold += tf;
   }
+  if (out_on_device) return s->run.copy_out(nq, k, out_dist, out_ids, out_counts);
   if (int rc = s->run.download(nq, k, out_dist, out_ids, out_counts)) return rc;
   s->d2h_res += (int64_t)nq * k * 12 + (int64_t)nq * 4;
   return IVF_OK;
 }
 
+// shardset_search over host queries, or (pos) over rows of a store into device buffers
+int search_rows(shardset *set, int32_t nq, const float *queries, const int64_t *pos, int32_t k, int32_t nprobe, int32_t ht,
+                float *out_dist, int64_t *out_ids, int32_t *out_counts) {
+  if (!set || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
+  if (int rc = check_limits(nq, k, nprobe)) return rc;
+  if (int rc = shardset_internal::check_ht(set, ht)) return rc;
+  ITRY(hipSetDevice(set->device));
+  set->h2d = set->d2h_ctl = set->d2h_res = set->ctl_up = 0;
+  set->t_search = set->t_fold = 0;
+  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
+    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
+    if (int rc = search_chunk(set, m, pos ? queries : queries + (size_t)q0 * set->dimension, pos ? pos + q0 : nullptr, k, nprobe, ht,
+                              out_dist + (size_t)q0 * k, out_ids + (size_t)q0 * k, out_counts + q0, pos != nullptr))
+      return rc;
+  }
+  return IVF_OK;
+}
+
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// the by-id seam (ivf_device_rows.h)
+// ---------------------------------------------------------------------------------------------
+int shardset_internal::check_ht(const shardset *set, int32_t ht) {
+  if (ht > 0)
+    for (size_t i = 0; i < set->members.size(); ++i)
+      if (set->members[i].kind == FAISS_KIND_IVF_FLAT)
+        return fail(IVF_EINVAL, "member " + std::to_string(i) + " is an IVF-Flat index, which has no polysemous codes: ht cannot be set");
+  return IVF_OK;
+}
+int shardset_internal::search_store_out(shardset *set, int32_t nq, const float *d_store_rows, const int64_t *d_pos, int32_t k,
+                                        int32_t nprobe, int32_t ht, float *d_dist, int64_t *d_ids, int32_t *d_counts) try {
+  if (!d_pos) return fail(IVF_EINVAL, "null argument");
+  return search_rows(set, nq, d_store_rows, d_pos, k, nprobe, ht, d_dist, d_ids, d_counts);
+} ABI_CATCH
+int shardset_internal::device_of(const shardset *set) { return set->device; }
+int shardset_internal::dimension_of(const shardset *set) { return set->dimension; }
+int64_t shardset_internal::last_control_bytes(const shardset *set) { return set->d2h_ctl; }
+int64_t shardset_internal::last_control_upload_bytes(const shardset *set) { return set->ctl_up; }
+std::shared_ptr<void> &shardset_internal::by_id_scratch(shardset *set) { return set->by_id; }
 
 extern "C" {
 
@@ -397,22 +480,7 @@ int shardset_info(const shardset_t *set, int32_t *n_members, int32_t *dimension,
 
 int shardset_search(shardset_t *set, int32_t nq, const float *queries, int32_t k, int32_t nprobe, int32_t ht, float *out_dist,
                     int64_t *out_ids, int32_t *out_counts) try {
-  if (!set || !queries || !out_dist || !out_ids || !out_counts) return fail(IVF_EINVAL, "null argument");
-  if (int rc = check_limits(nq, k, nprobe)) return rc;
-  if (ht > 0)
-    for (size_t i = 0; i < set->members.size(); ++i)
-      if (set->members[i].kind == FAISS_KIND_IVF_FLAT)
-        return fail(IVF_EINVAL, "member " + std::to_string(i) + " is an IVF-Flat index, which has no polysemous codes: ht cannot be set");
-  ITRY(hipSetDevice(set->device));
-  set->h2d = set->d2h_ctl = set->d2h_res = 0;
-  set->t_search = set->t_fold = 0;
-  for (int32_t q0 = 0; q0 < nq; q0 += CHUNK) {
-    const int32_t m = std::min<int32_t>(CHUNK, nq - q0);
-    if (int rc = search_chunk(set, m, queries + (size_t)q0 * set->dimension, k, nprobe, ht, out_dist + (size_t)q0 * k,
-                              out_ids + (size_t)q0 * k, out_counts + q0))
-      return rc;
-  }
-  return IVF_OK;
+  return search_rows(set, nq, queries, nullptr, k, nprobe, ht, out_dist, out_ids, out_counts);
 } ABI_CATCH
 
 int shardset_last_stats(const shardset_t *set, int64_t *h2d_bytes, int64_t *d2h_bytes, int64_t *d2h_result_bytes, float *search_ms,
