@@ -272,9 +272,13 @@ int sann_batch_run(sann_batch_t *batch, void *hip_stream);
 
 /* The same for batches kept in flight on different streams: the dominant (unit) kernel of `batch` does not start
  * before that of `after` (a batch enqueued earlier with this function on another stream; NULL = no predecessor)
- * has finished -- a cross-stream event, no host wait.  Everything else overlaps: this batch's descriptor kernel
- * and its unit kernel run beside `after`'s merge kernel, and the host's wait in sann_batch_finish is off the
- * GPU's critical path.  Per-launch kernel durations stay meaningful because unit kernels never run side by side. */
+ * has finished -- a cross-stream wait on the GPU, no host wait.  On the fast path what it waits on is the completion
+ * signal of `after`'s unit dispatch itself (after_merge = 0), not a marker recorded behind it, and between that wait
+ * and this batch's merge kernel the stream carries the unit dispatch alone: nothing but the wait stands between one
+ * unit kernel's end and the next one's start.  Everything else overlaps: this batch's descriptor kernel runs beside
+ * `after`'s unit kernel, its unit kernel beside `after`'s merge kernel, and the host's wait in sann_batch_finish is
+ * off the GPU's critical path.  Per-launch kernel durations stay meaningful because unit kernels never run side by
+ * side. */
 int sann_batch_run_after(sann_batch_t *batch, void *hip_stream, sann_batch_t *after, int32_t after_merge);
 /* Wait for the batch, re-running on the general path whatever the fast path flagged. After
  * this returns SANN_OK the device results are final and exact. */
@@ -290,10 +294,13 @@ int sann_batch_results(sann_batch_t *batch, int64_t *out_ids, double *out_scores
 int sann_batch_device_results(sann_batch_t *batch, void **d_ids, void **d_scores, void **d_counts,
                               void **d_map_sizes, int32_t *stride);
 int sann_batch_stats(sann_batch_t *batch, sann_batch_stats_t *stats);
-/* Measurement: sann_batch_run brackets kernels with HIP events on the launch stream and sann_batch_finish
- * adds the elapsed times to running totals.  enable = 1: the unit (gather + accumulate + select) kernel only --
- * two events per run, what a timed region should carry (every event costs the stream ~5 us); enable = 2: the
- * descriptor, unit and merge kernels (four events).  0 = off.  Resets the totals. */
+/* Measurement: sann_batch_run times kernels with HIP events on the launch stream and sann_batch_finish adds the
+ * elapsed times to running totals.  enable = 1: the unit (gather + accumulate + select) kernel only, what a timed
+ * region should carry: on the fast path the two events are stamped by the unit dispatch itself (hipExtLaunchKernel's
+ * startEvent / stopEvent), so they put no packet on the stream, and the duration is the kernel's own -- without a
+ * marker's cost and, as <hip/hip_ext.h> says of such a pair, without the system-scope release behind the kernel.
+ * (The general path records two markers around its kernels, ~5 us of the stream each.)  enable = 2: the descriptor,
+ * unit and merge kernels, bracketed by four recorded markers; for one batch at a time.  0 = off.  Resets the totals. */
 int sann_batch_set_profiling(sann_batch_t *batch, int32_t enable);
 int sann_batch_kernel_times(sann_batch_t *batch, double *unit_ms_total, double *merge_ms_total, int32_t *n_runs);
 /* Total of the descriptor kernel (fast path only) over the same runs. */

@@ -1081,16 +1081,28 @@ static int batch_run(sann_batch_t *b, void *hip_stream, bool chained, sann_batch
     HIP_TRY(hipMemsetAsync(b->status.p, 0, ((size_t)b->nq + 2) * 4, st));
     HIP_TRY(hipMemsetAsync(b->unit_fb.p, 0xFF, (size_t)b->n_units * 4, st));
   }
+  // Fast path, profiling levels 0 and 1: the unit dispatch stamps its own events (launch_unit_fast), so between the wait
+  // for the predecessor and the merge kernel the stream carries the dispatch and nothing else -- every marker packet there
+  // would stand between one unit kernel's end and the next one's start.  Level 2 (one batch at a time) keeps its markers.
+  const bool own_events = b->use_fast && !(b->profiling && !b->prof_unit_only);
   {
     if (b->profiling && !(b->prof_unit_only && b->use_fast)) HIP_TRY(hipEventRecord(b->ev[0], st));
     if (b->use_fast) {
       hipError_t e = launch_desc(b->ix->view(), b->view(), b->n_units, b->fast.max_n_scan, b->fast.k_local, st);
       if (e != hipSuccess) return fail(SANN_EDEVICE, std::string("launch_desc: ") + hipGetErrorString(e));
-      // the descriptor kernel may run beside anything; the dominant kernel waits for its predecessor's
+      // The descriptor kernel may run beside anything; the dominant kernel waits for its predecessor's.  (Beside a
+      // predecessor's unit kernel that fills every CU the descriptor kernel gets its slots only in that kernel's tail
+      // and ends with it; a library-owned stream of the highest priority did not change that and its two extra hops
+      // cost 2 us of the step: profiles/NOTES.md, round 15.)
       if (after && after != b && after->unit_done_recorded)
         HIP_TRY(hipStreamWaitEvent(st, whole ? after->ev_all_done : after->last_unit_done, 0));
-      if (b->profiling) HIP_TRY(hipEventRecord(b->ev[3], st));
-      e = launch_unit_fast(b->ix->view(), b->view(), b->fast, b->n_units, st);
+      if (own_events) {
+        e = launch_unit_fast(b->ix->view(), b->view(), b->fast, b->n_units, st, b->profiling ? b->ev[3] : nullptr,
+                             b->profiling ? b->ev[1] : chained ? b->ev_unit_done : nullptr);
+      } else {
+        HIP_TRY(hipEventRecord(b->ev[3], st));
+        e = launch_unit_fast(b->ix->view(), b->view(), b->fast, b->n_units, st);
+      }
       if (e != hipSuccess) return fail(SANN_EDEVICE, std::string("launch_unit_fast: ") + hipGetErrorString(e));
       b->id_form_ran = b->fast.id_form != 0;
       // (launch_unit_fast's geometries: <64, 4>, <128, 4>, then 256 threads)
@@ -1105,9 +1117,9 @@ static int batch_run(sann_batch_t *b, void *hip_stream, bool chained, sann_batch
       if (rc != SANN_OK) return rc;
     }
   }
-  if (b->profiling) HIP_TRY(hipEventRecord(b->ev[1], st));
+  if (b->profiling && !own_events) HIP_TRY(hipEventRecord(b->ev[1], st));
   if (chained) {  // the profiling bracket's closing event doubles as the marker (an event costs the stream ~5 us)
-    if (!b->profiling) HIP_TRY(hipEventRecord(b->ev_unit_done, st));
+    if (!b->profiling && !own_events) HIP_TRY(hipEventRecord(b->ev_unit_done, st));
     b->last_unit_done = b->profiling ? b->ev[1] : b->ev_unit_done;
     b->unit_done_recorded = true;
   }

@@ -45,6 +45,7 @@
 // Build rule (csrc/Makefile, tools/check_unit_kernel_resources.py): no instantiation of unit_fast_kernel may use
 // scratch.  hipcc (ROCm 7.2) was seen to place a VGPR spill store in FRONT of the `s_or_b64 exec` that re-joins a
 // divergent branch, so lanes that sat the branch out reloaded garbage: results differed from run to run.
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -1159,30 +1160,32 @@ __global__ __launch_bounds__(WG, (two_wave_unit<WG, U, IDF> ? 7 : WG < 256 ? 2 :
 }
 
 template <int WG, int U>
-static hipError_t launch_one(const IndexView &ix, const BatchView &b, const FastParams &fp, hipStream_t stream) {
+static hipError_t launch_one(const IndexView &ix, const BatchView &b, const FastParams &fp, hipStream_t stream,
+                             hipEvent_t start, hipEvent_t stop) {
   const int nq8 = (b.nq + 7) / 8 * 8;
   const int n_blocks = nq8 * ix.P;
   if (b.desc_stride != desc_row_stride(fp.max_n_scan)) return hipErrorInvalidValue;  // (the kernel's NS is the row stride)
   if (fp.use_norms) {
     if (fp.max_n_scan <= 64)
-      hipLaunchKernelGGL((unit_fast_kernel<WG, U, 64, 0, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+      hipExtLaunchKernelGGL((unit_fast_kernel<WG, U, 64, 0, true>), dim3(n_blocks), dim3(WG), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
     else
-      hipLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX, 0, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+      hipExtLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX, 0, true>), dim3(n_blocks), dim3(WG), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
   } else if (fp.id_form) {
     if (!ix.ids) return hipErrorInvalidValue;  // (set only for an index that has the column)
     if (fp.max_n_scan <= 64)
-      hipLaunchKernelGGL((unit_fast_kernel<WG, U, 64, 0, false, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+      hipExtLaunchKernelGGL((unit_fast_kernel<WG, U, 64, 0, false, true>), dim3(n_blocks), dim3(WG), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
     else
-      hipLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX, 0, false, true>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+      hipExtLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX, 0, false, true>), dim3(n_blocks), dim3(WG), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
   } else if (fp.max_n_scan <= 64)
-    hipLaunchKernelGGL((unit_fast_kernel<WG, U, 64>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+    hipExtLaunchKernelGGL((unit_fast_kernel<WG, U, 64>), dim3(n_blocks), dim3(WG), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
   else
-    hipLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX>), dim3(n_blocks), dim3(WG), 0, stream, ix, b, fp.k_local, n_blocks);
+    hipExtLaunchKernelGGL((unit_fast_kernel<WG, U, NSCAN_MAX>), dim3(n_blocks), dim3(WG), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
   return hipGetLastError();
 }
 
 // the two-wave unit of 1536 postings exists in the id form only (FastParams::two_wave is never set without id_form)
-static hipError_t launch_two_wave(const IndexView &ix, const BatchView &b, const FastParams &fp, hipStream_t stream) {
+static hipError_t launch_two_wave(const IndexView &ix, const BatchView &b, const FastParams &fp, hipStream_t stream,
+                                  hipEvent_t start, hipEvent_t stop) {
   const int nq8 = (b.nq + 7) / 8 * 8;
   const int n_blocks = nq8 * ix.P;
   if (b.desc_stride != desc_row_stride(fp.max_n_scan)) return hipErrorInvalidValue;
@@ -1191,13 +1194,13 @@ static hipError_t launch_two_wave(const IndexView &ix, const BatchView &b, const
   if (!fp.wide_offsets && unit_offsets_wide(ix.n_postings)) return hipErrorInvalidValue;
   if (fp.wide_offsets) {
     if (fp.max_n_scan <= 64)
-      hipLaunchKernelGGL((unit_fast_kernel<128, 12, 64, 0, false, true, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+      hipExtLaunchKernelGGL((unit_fast_kernel<128, 12, 64, 0, false, true, true>), dim3(n_blocks), dim3(128), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
     else
-      hipLaunchKernelGGL((unit_fast_kernel<128, 12, NSCAN_MAX, 0, false, true, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+      hipExtLaunchKernelGGL((unit_fast_kernel<128, 12, NSCAN_MAX, 0, false, true, true>), dim3(n_blocks), dim3(128), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
   } else if (fp.max_n_scan <= 64)
-    hipLaunchKernelGGL((unit_fast_kernel<128, 12, 64, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+    hipExtLaunchKernelGGL((unit_fast_kernel<128, 12, 64, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
   else
-    hipLaunchKernelGGL((unit_fast_kernel<128, 12, NSCAN_MAX, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, ix, b, fp.k_local, n_blocks);
+    hipExtLaunchKernelGGL((unit_fast_kernel<128, 12, NSCAN_MAX, 0, false, true>), dim3(n_blocks), dim3(128), 0, stream, start, stop, 0, ix, b, fp.k_local, n_blocks);
   return hipGetLastError();
 }
 
@@ -1509,19 +1512,22 @@ hipError_t launch_debug_approx(int alg, int n, const double *s, const double *w,
 }
 
 // fp.unit_capacity = postings one unit may hold = WG * U
+// `start` / `stop` (either may be null) are stamped by the dispatch itself, from its completion signal: the pair times the
+// kernel, and `stop` is what another stream's hipStreamWaitEvent waits on -- no marker packet on this stream for either.
 hipError_t launch_unit_fast(const IndexView &ix, const BatchView &b, const FastParams &fp, int n_units,
-                            hipStream_t stream) {
+                            hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
   if (n_units <= 0) return hipSuccess;
   if (b.cap < FAST_SCAP) return hipErrorInvalidValue;
   switch (fp.unit_capacity) {
-    case 256: return launch_one<64, 4>(ix, b, fp, stream);
-    case 512: return launch_one<128, 4>(ix, b, fp, stream);
-    case 768: return launch_one<256, 3>(ix, b, fp, stream);
-    case 1024: return launch_one<256, 4>(ix, b, fp, stream);
-    case 1536: return fp.two_wave ? launch_two_wave(ix, b, fp, stream) : launch_one<256, 6>(ix, b, fp, stream);
-    case 2048: return launch_one<256, 8>(ix, b, fp, stream);
-    case 3072: return launch_one<256, 12>(ix, b, fp, stream);
-    case 4096: return launch_one<256, 16>(ix, b, fp, stream);
+    case 256: return launch_one<64, 4>(ix, b, fp, stream, start, stop);
+    case 512: return launch_one<128, 4>(ix, b, fp, stream, start, stop);
+    case 768: return launch_one<256, 3>(ix, b, fp, stream, start, stop);
+    case 1024: return launch_one<256, 4>(ix, b, fp, stream, start, stop);
+    case 1536:
+      return fp.two_wave ? launch_two_wave(ix, b, fp, stream, start, stop) : launch_one<256, 6>(ix, b, fp, stream, start, stop);
+    case 2048: return launch_one<256, 8>(ix, b, fp, stream, start, stop);
+    case 3072: return launch_one<256, 12>(ix, b, fp, stream, start, stop);
+    case 4096: return launch_one<256, 16>(ix, b, fp, stream, start, stop);
     default: return hipErrorInvalidValue;
   }
 }

@@ -82,6 +82,6 @@ hipError_t launch_cut(const IndexView &ix, int M, uint32_t *out, hipStream_t str
 hipError_t launch_desc(const IndexView &ix, const BatchView &b, int n_units, int max_n_scan, int k_local_floor, hipStream_t stream);
 hipError_t launch_unit_ablation(const IndexView &ix, const BatchView &b, const FastParams &fp, int abl, hipStream_t stream);
 hipError_t launch_unit_fast(const IndexView &ix, const BatchView &b, const FastParams &fp, int n_units,
-                            hipStream_t stream);
+                            hipStream_t stream, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 }  // namespace sann
